@@ -10,6 +10,11 @@ batch 4096 per GPU, fp32), one process per GPU.
 A step = dynamic_mask (on device) -> forward -> backward -> gradient exchange (N>1) ->
 AdamW (dense groups fused; tables row-sparse with exact lazy replay) -> schedule -> zero_grad,
 over one batch already resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, ...).
+--full adds what takes runs of its own: the per-kernel pass (HIP events around every kernel class of the step
+run eagerly; `kernels`, `roofline`, `step_mfma_frac`, PMC traffic) and the CPU baseline (`cpu_baseline`,
+unless --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 """
 import argparse
 import json
@@ -151,7 +156,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--rows", type=int, default=1 << 22, help="synthetic training rows resident in HBM")
     ap.add_argument("--uniform", action="store_true", help="uniform ids inside a field instead of Zipf(1.1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass (kernels / roofline figures) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float32): loss, accuracy and the "
+                         "weights it left, embedding tables as a fixed sample of rows")
     ap.add_argument("--preroll", type=int, default=400,
                     help="untimed real training steps before the warm-up, so that the lazy table optimizer "
                          "carries a realistic replay debt (rows re-touched after long gaps)")
@@ -204,8 +214,40 @@ def build(args, device, rank):
 
 def mfp_step(tr, X, Y):
     """The Trainer's own step: captured hipGraph replay after 3 eager steps (1 GPU), eager with
-    the RCCL gradient exchange otherwise."""
-    return tr.run_step("mfp", X, Y)[0]
+    the RCCL gradient exchange otherwise.  -> (loss, masked-feature accuracy), device scalars."""
+    return tr.run_step("mfp", X, Y)
+
+
+DUMP_WHOLE_MAX = 1 << 22     # state entries up to this many elements are dumped whole ...
+DUMP_ROWS = 4096             # ... larger ones (the V-row tables) as these many rows, drawn with a fixed seed
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr, loss, acc, write=True):
+    """What the timed path computed in its last step, as float32 .npy files: `loss.npy` and `acc_ratio.npy`
+    (what Trainer.run_step returns) and `state.<key>.npy` for every floating-point entry of the model's
+    state_dict (the reference's checkpoint layout) after the step.  Lazy table rows are brought up to date
+    first, as a checkpoint does (every rank: the replicas replay together).  An entry above DUMP_WHOLE_MAX
+    elements is sampled: DUMP_ROWS distinct rows, ascending, from np.random.default_rng(0) over its row count,
+    so that the same arguments give the same rows on every run."""
+    tr.optimizer.flush()
+    torch.cuda.synchronize()
+    if not write:
+        return
+    arrays = {"loss": loss.detach().float().reshape(1), "acc_ratio": torch.as_tensor(acc).detach().float().reshape(1)}
+    for k, v in tr.model.state_dict().items():
+        if not v.is_floating_point():
+            continue
+        if v.numel() > DUMP_WHOLE_MAX:
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=min(DUMP_ROWS, v.shape[0]), replace=False))
+            v = v.detach()[torch.from_numpy(rows).to(v.device)]
+        arrays[f"state.{k}"] = v.detach().float()
+    total = sum(a.numel() * 4 for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes would exceed {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(cfg, ids, labels, feat_count, batch, steps):
@@ -443,11 +485,12 @@ def main():
     for _ in range(args.steps):
         # the batch is cut from the HBM-resident split inside the timed region: its row numbers (a slice of
         # the epoch's device permutation) go to the step, whose mask kernel reads the rows through them
-        loss = mfp_step(tr, *next_batch())
+        loss, acc = mfp_step(tr, *next_batch())
     parallel.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    staged = [next_batch() for _ in range(max(5, min(20, args.steps)))]      # for the per-kernel pass below
+    if args.dump_outputs:       # (its table flush leaves --full's per-kernel pass below no replay debt)
+        dump_outputs(args.dump_outputs, tr, loss, acc, write=rank == 0)
     dp_info = None
     if graphed:     # host-side phases of the data-parallel step (this rank), microseconds per step
         names = ("launch", "counts", "tail_capture", "dense_allreduce", "tail")
@@ -463,9 +506,52 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
-    # per-kernel durations: HIP events on the launch stream around every kernel class, taken on
-    # the same step run eagerly right after the timed region (a graph replay has no
-    # per-kernel launch points to bracket; kernel durations do not depend on the launch mode)
+    timers = kernel_pass(tr, [next_batch() for _ in range(max(5, min(20, args.steps)))]) if args.full else None
+    if torch.distributed.is_initialized():
+        parallel.barrier()
+        torch.distributed.destroy_process_group()
+    if rank != 0:
+        return
+    final_loss = float(loss.detach())
+    from mapx import ops as _ops
+    out = {
+        "metric": "pretrain samples/sec (DCNv2+MFP, Avazu, bs4096)", "value": world * B * args.steps / dt,
+        "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"DCNv2+MFP pretrain step, {args.workload}-shaped synthetic ids "
+                               f"({'uniform' if args.uniform else 'Zipf(1.1)'} per field), F={cfg.num_fields}, "
+                               f"V={cfg.input_size}, E=16, H=1000x3, cross x3, P=32, K=25, mask_ratio 0.3"
+                               + (", bf16 GEMM operands / activations over fp32 master weights, tables and optimizer"
+                                  if args.dtype == "bf16" else
+                                  (", fp32 GEMMs as three fp16 MFMAs per product (operands scaled by per-tensor magnitude records "
+                                   "and cut into two fp16 pieces, fp32 accumulation; weights cut once per optimizer step)"
+                                   if _ops.H2 else
+                                   ", fp32 GEMMs as six bf16 MFMAs per product (operands cut into three bf16 pieces, fp32 accumulation)")),
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
+                   "launch": ("eager" if not tr.use_graph else
+                              "hipGraph replay of mask + forward + backward; pack and merge + optimizer replayed per message size, RCCL calls eager"
+                              if dp_path else "hipGraph replay of the whole step"),
+                   "table_optimizer": "row-sparse AdamW with lazy replay of untouched rows, "
+                                      + f"{args.preroll} untimed pre-roll steps"},
+    }
+    if args.full:
+        out.update(kernel_figures(timers.summary(), args, dt, max(5, min(20, args.steps))))
+    out["final_loss"] = final_loss
+    if dp_info:
+        out["dp"] = dp_info
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        del tr
+        torch.cuda.empty_cache()
+        out["cpu_baseline"] = cpu_baseline(cfg, ids, labels, feat_count, B, args.cpu_steps)
+    print(json.dumps(out))
+
+
+def kernel_pass(tr, staged):
+    """--full: per-kernel durations.  HIP events on the launch stream around every kernel class, taken on
+    the same step run eagerly right after the timed region (a graph replay has no
+    per-kernel launch points to bracket; kernel durations do not depend on the launch mode)."""
+    from mapx import ops
     ops.serialize_streams = True          # no side streams: every kernel is timed running alone
     for t in tr.optimizer.tables:         # ... and in program order: no row update squeezed in front of the
         t.early_ok = False                # cross tower's GEMMs (it leaves them a cold L2: +14 us each)
@@ -479,14 +565,11 @@ def main():
         timers.calibrate()
     torch.cuda.synchronize()
     ops.serialize_streams = False
-    ksteps = max(5, min(20, args.steps))
-    if torch.distributed.is_initialized():
-        parallel.barrier()
-        torch.distributed.destroy_process_group()
-    if rank != 0:
-        return
-    final_loss = float(loss.detach())
-    ksum = timers.summary()
+    return timers
+
+
+def kernel_figures(ksum, args, dt, ksteps):
+    """--full: the per-kernel table and the roofline figures of the line, from kernel_pass's summary."""
     kernels = {}
     # kernels whose work depends on the data (how many DISTINCT / stale rows a batch touches): the
     # a-priori byte count is only an upper bound, so their rate is priced with the HBM bytes the
@@ -530,26 +613,7 @@ def main():
                                                                          "peak_is", "frac_of_f32_mfma_peak", "mfma_busy")
                                         if k in kernels[dominant]})
     hbm_name = "nce_fwd"
-    out = {
-        "metric": "pretrain samples/sec (DCNv2+MFP, Avazu, bs4096)", "value": world * B * args.steps / dt,
-        "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"DCNv2+MFP pretrain step, {args.workload}-shaped synthetic ids "
-                               f"({'uniform' if args.uniform else 'Zipf(1.1)'} per field), F={cfg.num_fields}, "
-                               f"V={cfg.input_size}, E=16, H=1000x3, cross x3, P=32, K=25, mask_ratio 0.3"
-                               + (", bf16 GEMM operands / activations over fp32 master weights, tables and optimizer"
-                                  if args.dtype == "bf16" else
-                                  (", fp32 GEMMs as three fp16 MFMAs per product (operands scaled by per-tensor magnitude records "
-                                   "and cut into two fp16 pieces, fp32 accumulation; weights cut once per optimizer step)"
-                                   if _ops.H2 else
-                                   ", fp32 GEMMs as six bf16 MFMAs per product (operands cut into three bf16 pieces, fp32 accumulation)")),
-                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
-                   "launch": ("eager" if not tr.use_graph else
-                              "hipGraph replay of mask + forward + backward; pack and merge + optimizer replayed per message size, RCCL calls eager"
-                              if dp_path else "hipGraph replay of the whole step"),
-                   "table_optimizer": "row-sparse AdamW with lazy replay of untouched rows, "
-                                      + f"{args.preroll} untimed pre-roll steps"},
+    return {
         "roofline": roofline,
         "roofline_hbm": dict(kernel=hbm_name, **{k: kernels[hbm_name][k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}),
         # all GEMM flops of a step over the whole step's time, against the dtype's dense MFMA peak:
@@ -558,15 +622,8 @@ def main():
         "step_mfma_frac": gemm_flops / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS[f32_kind if args.dtype == "f32" else args.dtype],
         "step_gemm_gflop": gemm_flops / 1e9,
         "traffic_stale": pmc_stale(args.dtype), "traffic_from": os.path.relpath(pmc_file(args.dtype), ROOT),
-        "kernels": kernels, "final_loss": final_loss,
+        "kernels": kernels,
     }
-    if dp_info:
-        out["dp"] = dp_info
-    if world == 1 and not args.no_cpu_baseline:
-        del tr
-        torch.cuda.empty_cache()
-        out["cpu_baseline"] = cpu_baseline(cfg, ids, labels, feat_count, B, args.cpu_steps)
-    print(json.dumps(out))
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@
 # Runs bench.py (no CPU baseline; extra arguments in $BENCH_ARGS) once per environment string, twice
 # round-robin, and prints ms/step (and the serial average us of the kernel classes named in $KERNELS).  The pool's boxes differ by +-4 %: only arms run on one box compare.
 TAG=$1; shift
+if [ -n "$KERNELS" ]; then BENCH_ARGS="--full $BENCH_ARGS"; fi     # the kernel table is a --full figure
 cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p gpurun_out/ab_$TAG
 for rep in 1 2; do

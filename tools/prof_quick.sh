@@ -7,7 +7,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 O=gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
-B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --no-cpu-baseline $@"
+B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --full --no-cpu-baseline $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/graph -o g -- $B > $O/graph.log 2>&1
 MAPX_GRAPH=0 MAPX_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o s -- $B > $O/serial.log 2>&1
 cp $(find $O/graph -name '*kernel_stats.csv' | head -1) $O/graph_kernel_stats.csv

@@ -12,10 +12,10 @@ O=gpurun_out/prof_$R
 rm -rf $O && mkdir -p $O/out
 for DT in f32 bf16; do
   S=""; [ $DT = bf16 ] && S="_bf16"
-  B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --no-cpu-baseline --dtype $DT"
+  B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --full --no-cpu-baseline --dtype $DT"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/graph$S -o g -- $B > $O/graph$S.log 2>&1
   MAPX_GRAPH=0 MAPX_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial$S -o s -- $B > $O/serial$S.log 2>&1
-  P="python3 bench.py --steps 10 --warmup 2 --preroll 60 --no-cpu-baseline --dtype $DT"
+  P="python3 bench.py --steps 10 --warmup 2 --preroll 60 --full --no-cpu-baseline --dtype $DT"
   MAPX_GRAPH=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch$S -o f -- $P > $O/fetch$S.log 2>&1
   MAPX_GRAPH=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write$S -o w -- $P > $O/write$S.log 2>&1
   MAPX_GRAPH=0 MAPX_SERIAL=1 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/mfma$S -o m -- $P > $O/mfma$S.log 2>&1
@@ -26,7 +26,7 @@ for DT in f32 bf16; do
           $(find $O/write$S -name '*counter_collection.csv' | head -1) $O/out/${R}_pmc_hbm_traffic$S.json > $O/out/pmc$S.txt
   echo "$DT done"
 done
-B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --no-cpu-baseline"
+B="python3 bench.py --steps 30 --warmup 5 --preroll 100 --full --no-cpu-baseline"
 MAPX_FORCE_DP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dp -o d -- $B > $O/dp.log 2>&1
 cp $(find $O/dp -name '*kernel_stats.csv' | head -1) $O/out/${R}_dp_rehearsal_kernel_stats.csv
 # the other BASELINE configurations' captured steps (configs[3] RFD, configs[4] finetune): kernel stats inside the graph
