@@ -31,7 +31,7 @@ typedef struct ihipStream_t* hipStream_t; /* opaque outside hipcc */
 #include <hip/hip_runtime_api.h>
 #endif
 
-#define MAPX_ABI_VERSION 46
+#define MAPX_ABI_VERSION 47
 
 #define MAPX_OK 0
 #define MAPX_EINVAL (-1)     /* bad argument (shape, null pointer, alignment) */
@@ -171,6 +171,31 @@ int mapx_attn_fwd(const float* q, const float* k, const float* v, int64_t G, int
                   float* o, float* p, hipStream_t stream);
 int mapx_attn_bwd(const float* q, const float* k, const float* v, const float* p, const float* d_o,
                   int64_t G, int F, int A, int scaled, float* dq, float* dk, float* dv, hipStream_t stream);
+
+/* ------------------------------------------------------------------ Transformer attention core
+ * models.py:491-568 (nn.TransformerEncoderLayer's nn.MultiheadAttention, batch_first, fp32) on B samples of F <= 64
+ * fields, E = H * dh with dh % 4 == 0, dh <= 64.  qkv [B*F, 3E] is the in-projection's output (row b*F + f; Q, K, V
+ * thirds; head h = columns [h*dh, (h+1)*dh) of each third), read in place.  Per (b, h):
+ *   P = softmax(Q K^T / sqrt(dh)) -> probs [B*H, F, F] (undropped, kept for backward);  O = (P * m / (1-p)) V
+ * written to o [B*F, E] at the head's columns (heads concatenated, as out_proj reads them).  The keep mask m of
+ * element (g = b*H + h, i, j) comes from Philox(seed, offset + *offset_dev_opt) and is regenerated, not stored;
+ * mapx_mha_dropout_mask writes it (1 = kept) into keep [B*H, F, F] with the very function the kernels use.
+ * Backward: d_qkv [B*F, 3E] = (dQ, dK, dV) in the layout of qkv (dS = P (dP - rowsum(P dP)) / sqrt(dh),
+ * dP = (dO V^T) m / (1-p)).  16-byte aligned qkv / o / d_o / d_qkv.  No atomics: bitwise deterministic. */
+int mapx_mha_fwd(const float* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed, uint64_t offset,
+                 const int32_t* offset_dev_opt, float* o, float* probs, hipStream_t stream);
+int mapx_mha_bwd(const float* qkv, const float* probs, const float* d_o, int64_t B, int F, int E, int H, float p,
+                 uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt, float* d_qkv, hipStream_t stream);
+int mapx_mha_dropout_mask(int64_t B, int F, int H, float p, uint64_t seed, uint64_t offset,
+                          const int32_t* offset_dev_opt, uint8_t* keep, hipStream_t stream);
+/* The Transformer finetune head's reduction over fields (models.py:551-563) of x [B,F,E] (E % 4 == 0) -> out [B,E]:
+ * mode 0 sum, 1 sum / F ("mean,fc"), 2 sum_f w_f x_f with w = softmax over F of scores_opt [B,F] ("attn,fc";
+ * weights_opt [B,F] receives w for backward).  Backward: dx [B,F,E] = w_f g; mode 2 also d_scores_opt [B,F] =
+ * w_f (g.x_f - sum_k w_k g.x_k), the gradient of the softmax's input. */
+int mapx_field_pool_fwd(const float* x, const float* scores_opt, int64_t B, int F, int E, int mode, float* out,
+                        float* weights_opt, hipStream_t stream);
+int mapx_field_pool_bwd(const float* g, const float* x, const float* weights_opt, int64_t B, int F, int E, int mode,
+                        float* dx, float* d_scores_opt, hipStream_t stream);
 
 /* ------------------------------------------------------------------ NCE sampler (a7, a8)
  * nce/alias_multinomial.py:39-72: Walker table from the renormalised noise probabilities,

@@ -354,10 +354,12 @@ static bool skinny_dispatch(int N, A... a) {
 }
 
 template <int NT>
+// (the forward and dX kernels do not stride over the grid: their grids cover every row, uncapped — grid_for's cap
+// of 2048 blocks left the rows past 32 768 (forward) / 2048 * 256 * 4 / (K / 4) (dX) unwritten)
 struct FwdLaunch {
   static void go(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, int M, int N, int K,
                  int relu, float* y, int64_t ldy, hipStream_t stream) {
-    hipLaunchKernelGGL(skinny_fwd_kernel<NT>, dim3(grid_for(M, 16)), dim3(256), 0, stream, x, ldx, w, ldw, bias, M, N,
+    hipLaunchKernelGGL(skinny_fwd_kernel<NT>, dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, stream, x, ldx, w, ldw, bias, M, N,
                        K, relu, y, ldy);
   }
 };
@@ -374,7 +376,7 @@ struct DxLaunch {
   static void go(const float* dy, int64_t ldy, const float* w, int64_t ldw, int M, int N, int K, float* dx,
                  int64_t lddx, hipStream_t stream) {
     const int64_t threads = (int64_t)((M + 3) / 4) * (K / 4);
-    hipLaunchKernelGGL(skinny_dx_kernel<NT>, dim3(grid_for(threads, 256)), dim3(256), 0, stream, dy, ldy, w, ldw, M, N,
+    hipLaunchKernelGGL(skinny_dx_kernel<NT>, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, stream, dy, ldy, w, ldw, M, N,
                        K, dx, lddx);
   }
 };
@@ -439,7 +441,7 @@ extern "C" int mapx_skinny_linear_fwd_bf16(const mapx_bf16* x, int64_t ldx, cons
   if (M == 0) return MAPX_OK;
   const __bf16* xx = reinterpret_cast<const __bf16*>(x);
   const __bf16* ww = reinterpret_cast<const __bf16*>(w);
-#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_fwd_kernel<NT, __bf16>), dim3(grid_for(M, 16)), dim3(256), 0, stream, xx, ldx, ww, ldw, bias_opt, M, N, K, relu, y, ldy)
+#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_fwd_kernel<NT, __bf16>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, stream, xx, ldx, ww, ldw, bias_opt, M, N, K, relu, y, ldy)
   if (N == 1) MAPX_SKH(1); else if (N <= 4) MAPX_SKH(4); else MAPX_SKH(8);
 #undef MAPX_SKH
   return check_launch("skinny_linear_fwd_bf16");
@@ -470,7 +472,7 @@ extern "C" int mapx_skinny_linear_dx_bf16(const mapx_bf16* dy, int64_t ldy, cons
   const __bf16* ww = reinterpret_cast<const __bf16*>(w);
   __bf16* out = reinterpret_cast<__bf16*>(dx);
   const int64_t threads = (int64_t)((M + 3) / 4) * (K / 4);
-#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_dx_kernel<NT, __bf16>), dim3(grid_for(threads, 256)), dim3(256), 0, stream, dd, ldy, ww, ldw, M, N, K, out, lddx)
+#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_dx_kernel<NT, __bf16>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, stream, dd, ldy, ww, ldw, M, N, K, out, lddx)
   if (N == 1) MAPX_SKH(1); else if (N <= 4) MAPX_SKH(4); else MAPX_SKH(8);
 #undef MAPX_SKH
   return check_launch("skinny_linear_dx_bf16");

@@ -2,6 +2,7 @@
 Embeddings :83-102, MLPBlock :173-188, CrossNetV2 :191-201).  autograd.Function = glue only:
 every forward/backward body is a C-ABI call (mapx.ops)."""
 import contextlib
+import copy
 import math
 import os
 
@@ -1087,3 +1088,159 @@ class _Bce(Function):
 def bce_with_logits(logits, labels):
     """-> (mean loss, stats = [loss, accuracy, mean(label)])  (BCEWithLogitsLoss, models.py:81,91)."""
     return _Bce.apply(logits, labels)
+
+
+# ----------------------------------------------------------------------------- Transformer encoder
+class MhaDropout(HipDropout):
+    """nn.MultiheadAttention's dropout of the attention probabilities (p = the layer's `dropout`).  A HipDropout site
+    like the others (Trainer gives it its seed, site and step counter), whose mask the attention kernels draw
+    themselves: ops.mha_fwd / mha_bwd take (p, seed, offset, offset_dev) from `philox()`."""
+
+    def philox(self):
+        """-> (p, seed, offset, offset_dev) of this forward call; p = 0 in eval mode (no mask)."""
+        if not self.training or self.p == 0.0:
+            return 0.0, 0, 0, None
+        base = (self.rank << 48) + ((16 + self.site) << 36)
+        if self.step_counter is not None:
+            return self.p, self.seed, base, self.step_counter
+        self._calls += 1
+        return self.p, self.seed, base + self._calls, None
+
+    def forward(self, x, out=None):
+        raise RuntimeError("MhaDropout is applied inside the attention kernels (_MhaCore)")
+
+
+class _MhaCore(Function):
+    """softmax(Q K^T / sqrt(dh)) -> dropout -> V per (sample, head), reading the packed in-projection output
+    qkv [B*F, 3E] and returning O [B*F, E] heads concatenated (csrc/mha.hip).  Backward writes dQ / dK / dV into
+    one packed [B*F, 3E] tensor: the in-projection's _Linear then forms its weight, bias and input gradients with
+    one launch each."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, F, E, H, drop):
+        p, seed, offset, dev = drop.philox() if drop is not None else (0.0, 0, 0, None)
+        o, probs = ops.mha_fwd(qkv, B, F, E, H, p, seed, offset, dev)
+        ctx.cfg = (B, F, E, H, p, seed, offset, dev)
+        ctx.save_for_backward(qkv, probs)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, probs = ctx.saved_tensors
+        B, F, E, H, p, seed, offset, dev = ctx.cfg
+        return ops.mha_bwd(qkv, probs, do, B, F, E, H, p, seed, offset, dev), None, None, None, None, None
+
+
+class HipMultiheadAttention(nn.Module):
+    """nn.MultiheadAttention(E, H, dropout, batch_first=True) as self-attention: parameters `in_proj_weight` [3E, E]
+    (Xavier-uniform), `in_proj_bias` [3E] (zeros), `out_proj.{weight,bias}` (nn.Linear's init, bias zeroed), torch's
+    names and initialisation.  forward() returns the heads' concatenated output BEFORE out_proj (the encoder layer
+    applies out_proj)."""
+
+    def __init__(self, embed_dim, num_heads, dropout=0.0):
+        super().__init__()
+        if embed_dim % num_heads:
+            raise ValueError(f"embed_dim {embed_dim} is not divisible by num_heads {num_heads}")
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = HipLinear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        with torch.no_grad():
+            self.out_proj.bias.zero_()
+        self.attn_drop = MhaDropout(dropout)
+
+    def forward(self, x2, B, F):
+        qkv = _Linear.apply(x2, self.in_proj_weight, self.in_proj_bias, False, None, False, None, None)
+        return _MhaCore.apply(qkv, B, F, self.embed_dim, self.num_heads, self.attn_drop)
+
+
+class TransformerEncoderLayer(nn.Module):
+    """nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation in {relu, gelu},
+    layer_norm_eps, batch_first=True, norm_first) with torch's parameter names:
+      post-norm: x = norm1(x + dropout1(SA(x)));  x = norm2(x + dropout2(linear2(dropout(act(linear1(x))))))
+      pre-norm:  x = x + dropout1(SA(norm1(x)));  x = x + dropout2(FF(norm2(x)))
+    relu is fused into linear1's GEMM epilogue, gelu (erf form) is one elementwise pass behind it."""
+
+    def __init__(self, d_model, nhead, dim_feedforward, dropout=0.0, activation="relu", layer_norm_eps=1e-5,
+                 norm_first=False):
+        super().__init__()
+        self.act = str(activation).lower()
+        if self.act not in ("relu", "gelu"):
+            raise ValueError(f"activation should be relu/gelu, not {activation}")
+        self.self_attn = HipMultiheadAttention(d_model, nhead, dropout)
+        self.linear1 = HipLinear(d_model, dim_feedforward, relu=self.act == "relu")
+        self.dropout = HipDropout(dropout)
+        self.linear2 = HipLinear(dim_feedforward, d_model)
+        self.norm_first = bool(norm_first)
+        self.norm1 = HipLayerNorm(d_model, layer_norm_eps)
+        self.norm2 = HipLayerNorm(d_model, layer_norm_eps)
+        self.dropout1 = HipDropout(dropout)
+        self.dropout2 = HipDropout(dropout)
+
+    def _sa(self, x2, B, F):
+        return self.dropout1(self.self_attn.out_proj(self.self_attn(x2, B, F)))
+
+    def _ff(self, x2):
+        h = self.linear1(x2)
+        if self.act == "gelu":
+            h = _Act.apply(h, "gelu", None)
+        return self.dropout2(self.linear2(self.dropout(h)))
+
+    def forward(self, x3):
+        B, F, E = x3.shape
+        x = x3.reshape(B * F, E)
+        # (the residual adds stay elementwise: the GEMM's EPI_ADD epilogue has no bias term, and every projection
+        # here has one)
+        if self.norm_first:
+            x = x + self._sa(self.norm1(x), B, F)
+            x = x + self._ff(self.norm2(x))
+        else:
+            x = self.norm1(x + self._sa(x, B, F))
+            x = self.norm2(x + self._ff(x))
+        return x.view(B, F, E)
+
+
+class TransformerEncoder(nn.Module):
+    """nn.TransformerEncoder(layer, num_layers) without a final norm: `layers.{i}` are copies of ONE layer, so every
+    layer starts with the same parameters (torch deep-copies too); each copy gets dropout sites of its own."""
+
+    def __init__(self, encoder_layer, num_layers):
+        super().__init__()
+        layers = [encoder_layer] + [copy.deepcopy(encoder_layer) for _ in range(num_layers - 1)]
+        for layer in layers[1:]:
+            for m in layer.modules():
+                if isinstance(m, HipDropout):
+                    HipDropout._sites += 1
+                    m.site = HipDropout._sites
+        self.layers = nn.ModuleList(layers[:num_layers])
+        self.num_layers = num_layers
+
+    def forward(self, x3):
+        for layer in self.layers:
+            x3 = layer(x3)
+        return x3
+
+
+class _FieldPool(Function):
+    """Reduction over the fields of the Transformer's finetune head: x3 [B,F,E] -> [B,E], "sum" / "mean", or "attn":
+    weighted by softmax_f(scores [B,F]) (the softmax is inside the kernel; backward returns the gradient of the
+    scores before it)."""
+
+    @staticmethod
+    def forward(ctx, x3, scores, mode):
+        x3 = x3.contiguous()
+        out, w = ops.field_pool_fwd(x3, mode, scores)
+        ctx.mode = mode
+        ctx.save_for_backward(x3, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x3, w = ctx.saved_tensors
+        dx, ds = ops.field_pool_bwd(g, x3, ctx.mode, w)
+        return dx, ds, None
+
+
+def field_pool(x3, mode, scores=None):
+    return _FieldPool.apply(x3, scores, mode)

@@ -10,7 +10,8 @@ from torch import nn
 from . import ops
 from .arguments import Config
 from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, HipLinear, MLPBlock, MultiHeadSelfAttention,
-                     RowTable, TableWeight, bce_with_logits, fm_product_sum)
+                     RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer, bce_with_logits, field_pool,
+                     fm_product_sum)
 from .nce import IndexLinear
 
 logger = logging.getLogger(__name__)
@@ -49,7 +50,7 @@ CATCHUP_AFTER_CROSS = os.environ.get("MAPX_CATCHUP_AFTER_CROSS", "0") == "1"    
 NCE_AFTER_CROSS = os.environ.get("MAPX_NCE_AFTER_CROSS", "0") == "1"
 EARLY_NCE_ALL = os.environ.get("MAPX_EARLY_NCE_ALL", "1") == "1"   # A/B switch: BaseModel._sample_early
 
-_OTHER_BACKBONES = ("trans", "fignn", "fgcnn")
+_OTHER_BACKBONES = ("fignn", "fgcnn")
 
 
 class _RfdPredictor(nn.ModuleDict):
@@ -87,10 +88,12 @@ class BaseModel(nn.Module):
             return AutoInt(config)
         if name == "xdeepfm":
             return xDeepFM(config)
+        if name == "trans":
+            return Transformer(config)
         if name in _OTHER_BACKBONES:
             raise NotImplementedError(
                 f"{config.model_name}: mapx builds the DCNv2 hot path and, of the other backbones "
-                "(SURVEY §8 f4), DNN, DeepFM, xDeepFM and AutoInt")
+                "(SURVEY §8 f4), DNN, DeepFM, xDeepFM, AutoInt and the Transformer")
         raise NotImplementedError(config.model_name)
 
     def validate_model_config(self):
@@ -569,4 +572,91 @@ class xDeepFM(BaseModel):
         logits = self.fc(final_vec)
         if lr is not None:
             logits = logits + lr.view(-1, 1) + self.lr_layer.bias
+        return self.get_outputs(logits, labels)
+
+
+class Transformer(BaseModel):
+    """nn.TransformerEncoder over the field embeddings (reference models.py:491-568): d_model = hidden_size (which
+    must equal embed_size), no final norm.  Pretraining feeds the flattened [B, F*E] encoder output to the MFP / RFD
+    heads; finetuning reduces it by `output_reduction` ("fc": trans_out over F*E; "mean,fc" / "sum,fc": over fields,
+    then trans_out over E; "attn,fc": softmax-weighted field sum with the weights from field_reduction_attn =
+    Linear(E,E), ReLU, Linear(E,1)) and adds the LR term (use_lr: its weight is the secondary parameter of the
+    embedding's RowTable, as in DeepFM) and an MLP tower over the flattened embeddings (num_dnn_layers > 0: `mlp` +
+    `mlp_out`).  The attention core is csrc/mha.hip: F <= 64 fields, head size hidden_size / num_attn_heads a
+    multiple of 4 and <= 64; LayerNorm over hidden_size <= 64."""
+    used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
+                   "num_attn_heads", "intermediate_size", "output_reduction",
+                   "norm_first", "layer_norm_eps", "use_lr",
+                   "dnn_size", "num_dnn_layers", "dnn_act", "dnn_drop"]
+    REDUCTIONS = ("fc", "mean,fc", "sum,fc", "attn,fc")
+
+    def __init__(self, config: Config):
+        super().__init__(model_name="trans", config=config)
+        E, H, F = int(config.hidden_size), int(config.num_attn_heads), int(config.num_fields)
+        if H < 1 or E % H or (E // H) % 4 or E // H > 64:
+            raise NotImplementedError(f"trans: the attention kernel takes a head size hidden_size / num_attn_heads that "
+                                      f"is a multiple of 4 and <= 64 (hidden_size={E}, num_attn_heads={H})")
+        if F > 64:
+            raise NotImplementedError(f"trans: the attention kernel takes at most 64 fields (num_fields={F})")
+        if E > 64:
+            raise NotImplementedError(f"trans: LayerNorm is built for hidden_size <= 64 (hidden_size={E})")
+        if not config.pretrain and config.output_reduction not in self.REDUCTIONS:
+            raise NotImplementedError(f"trans: output_reduction={config.output_reduction!r} (models.py:527-545 builds "
+                                      f"{', '.join(self.REDUCTIONS)})")
+        self.embed = Embeddings(config)
+        self.embed.defer_plan = True
+        layer = TransformerEncoderLayer(E, H, config.intermediate_size, dropout=config.hidden_dropout_rate,
+                                        activation=config.hidden_act, layer_norm_eps=config.layer_norm_eps,
+                                        norm_first=config.norm_first)
+        self.encoder = TransformerEncoder(layer, config.num_hidden_layers)
+        Ee = config.embed_size
+        if config.pretrain:
+            self.create_pretraining_predictor(config.num_fields * Ee)
+            return
+        red = config.output_reduction
+        if red == "attn,fc":
+            self.field_reduction_attn = nn.ModuleDict({"0": HipLinear(Ee, Ee, relu=True), "2": HipLinear(Ee, 1)})
+        self.trans_out = HipLinear(config.num_fields * Ee if red == "fc" else Ee, 1)
+        self.lr_layer = LR(config) if config.use_lr else None
+        if self.lr_layer is not None:          # one row table for both [V, *] parameters read with input_ids
+            self.embed.table = RowTable("embed.embedding", self.embed.embedding.weight, self.lr_layer.embed_w.weight)
+        if config.num_dnn_layers > 0:
+            self.mlp = MLPBlock(input_dim=config.num_fields * Ee, hidden_size=config.dnn_size,
+                                num_hidden_layers=config.num_dnn_layers, hidden_dropout_rate=config.dnn_drop,
+                                hidden_act=config.dnn_act)
+            self.mlp_out = HipLinear(config.dnn_size, 1)
+        else:
+            self.mlp = None
+
+    def validate_model_config(self):
+        assert self.config.embed_size == self.config.hidden_size, \
+            f"model {self.model_name} requires embed_size == hidden_size"
+        super().validate_model_config()
+
+    def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
+        lr = None
+        if not self.config.pretrain and self.lr_layer is not None:
+            x, lr = self.embed.forward_with_linear(input_ids, self.lr_layer.embed_w.weight)
+        else:
+            x = self.embed(input_ids)
+        nce_idx, early = self._sample_early(labels, masked_index, noise_samples)
+        enc = self.encoder(x)
+        self._plans_and_join(nce_idx, early)
+        if self.config.pretrain:
+            return self.get_outputs(enc.flatten(start_dim=1), labels, masked_index, noise_samples=noise_samples,
+                                    nce_idx=nce_idx)
+        red = self.config.output_reduction
+        if red == "fc":
+            logits = self.trans_out(enc.flatten(start_dim=1))
+        elif red == "attn,fc":
+            B, F, E = enc.shape
+            fra = self.field_reduction_attn
+            scores = fra["2"](fra["0"](enc.reshape(B * F, E))).view(B, F)
+            logits = self.trans_out(field_pool(enc, "attn", scores))
+        else:
+            logits = self.trans_out(field_pool(enc, red.split(",")[0]))
+        if lr is not None:
+            logits = logits + (lr.view(-1, 1) + self.lr_layer.bias)          # models.py:562-563
+        if self.mlp is not None:
+            logits = logits + self.mlp_out(self.mlp(ops.flat_rows(x)))      # models.py:564-565
         return self.get_outputs(logits, labels)

@@ -673,6 +673,63 @@ def attn_bwd(q, k, v, p, d_o, G, F, A, scaled):
     return dq, dk, dv
 
 
+# --------------------------------------------------------------------------- Transformer attention core
+def mha_fwd(qkv, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
+    """qkv [B*F, 3E] (the in-projection's output, read in place) -> (o [B*F, E] heads concatenated,
+    probs [B*H, F, F] undropped).  p > 0: O = (P * m / (1-p)) V with m = mha_dropout_mask(B, F, H, p, seed, offset)."""
+    require_gpu(qkv)
+    o = torch.empty(B * F, E, dtype=torch.float32, device=qkv.device)
+    probs = torch.empty(B * H, F, F, dtype=torch.float32, device=qkv.device)
+    check(lib.mapx_mha_fwd(ptr(qkv), B, F, E, H, float(p), int(seed), int(offset), ptr(offset_dev), ptr(o), ptr(probs),
+                           stream()))
+    return o, probs
+
+
+def mha_bwd(qkv, probs, d_o, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
+    """-> d_qkv [B*F, 3E] (dQ, dK, dV in qkv's layout); the dropout mask is regenerated from (seed, offset)."""
+    require_gpu(qkv, probs, d_o)
+    d_qkv = torch.empty_like(qkv)
+    check(lib.mapx_mha_bwd(ptr(qkv), ptr(probs), ptr(d_o.contiguous()), B, F, E, H, float(p), int(seed), int(offset),
+                           ptr(offset_dev), ptr(d_qkv), stream()))
+    return d_qkv
+
+
+def mha_dropout_mask(B, F, H, p, seed, offset, offset_dev=None, device="cuda"):
+    """The keep mask (uint8 [B*H, F, F], 1 = kept) that mha_fwd / mha_bwd draw for these arguments."""
+    keep = torch.empty(B * H, F, F, dtype=torch.uint8, device=device)
+    check(lib.mapx_mha_dropout_mask(B, F, H, float(p), int(seed), int(offset), ptr(offset_dev), ptr(keep), stream()))
+    return keep
+
+
+POOL_MODES = {"sum": 0, "mean": 1, "attn": 2}
+
+
+def field_pool_fwd(x3, mode, scores=None):
+    """x3 [B,F,E] -> (out [B,E], weights [B,F] | None): sum / mean over fields, or ("attn") weighted by
+    softmax_f(scores [B,F])."""
+    require_gpu(x3, scores)
+    x3 = x3.contiguous()
+    B, F, E = x3.shape
+    m = POOL_MODES[mode]
+    out = torch.empty(B, E, dtype=torch.float32, device=x3.device)
+    w = torch.empty(B, F, dtype=torch.float32, device=x3.device) if m == 2 else None
+    check(lib.mapx_field_pool_fwd(ptr(x3), ptr(scores.contiguous() if scores is not None else None), B, F, E, m,
+                                  ptr(out), ptr(w), stream()))
+    return out, w
+
+
+def field_pool_bwd(g, x3, mode, weights=None):
+    """-> (dx [B,F,E], d_scores [B,F] | None)."""
+    require_gpu(g, x3)
+    B, F, E = x3.shape
+    m = POOL_MODES[mode]
+    dx = torch.empty(B, F, E, dtype=torch.float32, device=g.device)
+    ds = torch.empty(B, F, dtype=torch.float32, device=g.device) if m == 2 else None
+    check(lib.mapx_field_pool_bwd(ptr(g.contiguous()), ptr(x3.contiguous()), ptr(weights), B, F, E, m, ptr(dx), ptr(ds),
+                                  stream()))
+    return dx, ds
+
+
 # --------------------------------------------------------------------------- NCE
 def alias_build(probs_cpu):
     """Host Walker table, bit-identical to the reference's (alias_multinomial.py:39-72)."""
