@@ -163,7 +163,7 @@ extern "C" int mapx_emb_gather_fwd(const int64_t* ids, int64_t n, const float* t
   MAPX_REQUIRE(ids && table && out, "emb_gather_fwd: null pointer");
   const bool vec = (E % 4 == 0) && ((uintptr_t)table % 16 == 0) && ((uintptr_t)out % 16 == 0);
   const int64_t total = n * (vec ? E / 4 : E);
-  static const int cap = [] { const char* e = getenv("MAPX_GATHER_GRID"); return e ? atoi(e) : 512; }();   // (2048 blocks: 6.2 us with the record's block reduction, 512: 5.0)
+  const int cap = 512;   // (2048 blocks: 6.2 us with the record's block reduction, 512: 5.0)
   const int grid = mapx::grid_for(total, 256, cap);
   if (lazy_opt) {
     MAPX_REQUIRE(vec, "emb_gather_fwd: rows are read through their pending updates for 16-byte rows only (E %% 4 == 0)");

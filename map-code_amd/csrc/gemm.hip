@@ -29,104 +29,23 @@ namespace mapx {
 // (kernels: gemm_x3.hip, gemm_grouped_x3_kernel).  P = 32 only (the reference default); other proj sizes and
 // widths that are not a multiple of 8 use the dense path.
 
-// Padded by-field slot layout of the T = B*L targets, straight from masked_index (one block,
-// one launch; the targets' field ids are a key space of F <= 64 values, so a counting sort in
+// Padded by-field slot layout of the T = B*L targets, straight from masked_index (one
+// launch; the targets' field ids are a key space of F <= 64 values, so a counting sort in
 // LDS replaces a general radix sort + run detection + layout = 9 launches).
 //   slots are ordered by field, inside a field by target index t (stable => the summation order
 //   of the grouped dW GEMM is fixed); every present field's group is padded to a multiple of 128.
 //   hpos[t] = slot of target t;  rowmap[slot] = batch row t / L, or -1 for padding;
 //   tile_group[slot / 128] = field of that 128-slot tile, or -1;  group_start[f], f = 0..F.
-constexpr int kLayoutThreads = 1024;
 constexpr int kLayoutMaxT = 96 * 1024;   // field ids of all targets cached in LDS as bytes
-__global__ void __launch_bounds__(kLayoutThreads) enc_group_layout_kernel(
-    const int64_t* __restrict__ masked_index, int T, int L, int F, int cap_slots, int32_t* __restrict__ rowmap,
-    int32_t* __restrict__ hpos, int32_t* __restrict__ tile_group, int32_t* __restrict__ group_start) {
-  constexpr int NW = kLayoutThreads / 64;
-  __shared__ int wave_cnt[NW][64];     // targets of field f in wave w's chunk, then the wave's running offset
-  __shared__ int gstart[64 + 1];       // padded start of field f's group
-  extern __shared__ uint8_t fld[];     // [T]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rounds = (T + kLayoutThreads - 1) / kLayoutThreads;      // same for every wave
-  const int wbase = wave * rounds * 64;                              // wave w owns targets [wbase, wbase + rounds*64)
-  for (int i = threadIdx.x; i < NW * 64; i += kLayoutThreads) (&wave_cnt[0][0])[i] = 0;
-  for (int t = threadIdx.x; t < T; t += kLayoutThreads) {            // coalesced, all loads independent
-    int f = (int)masked_index[t];
-    fld[t] = (uint8_t)(f < 0 ? 0 : (f >= F ? F - 1 : f));
-  }
-  for (int s = threadIdx.x; s < cap_slots; s += kLayoutThreads) rowmap[s] = -1;
-  __syncthreads();
-  for (int r = 0; r < rounds; ++r) {
-    const int t = wbase + r * 64 + lane;
-    if (t < T) atomicAdd(&wave_cnt[wave][fld[t]], 1);
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {              // thread f: exclusive prefix over the waves, field total
-    const int f = threadIdx.x;
-    int run = 0;
-    for (int w = 0; w < NW; ++w) {
-      const int c = wave_cnt[w][f];
-      wave_cnt[w][f] = run;
-      run += c;
-    }
-    gstart[f] = f < F ? (run + 127) / 128 * 128 : 0;                // padded length for now
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int f = 0; f < F; ++f) {
-      const int len = gstart[f];
-      gstart[f] = run;
-      group_start[f] = run;
-      run += len;
-    }
-    gstart[F] = run;
-    group_start[F] = run;
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < cap_slots / 128; k += kLayoutThreads) {
-    int g = -1;
-    for (int f = 0; f < F; ++f)
-      if (gstart[f] <= k * 128 && k * 128 < gstart[f + 1]) g = f;
-    tile_group[k] = g;
-  }
-  // placement: a wave walks its chunk in target order; lanes of one round that share a field
-  // rank themselves by lane id, then the field's running offset advances by their number
-  for (int r = 0; r < rounds; ++r) {
-    const int t = wbase + r * 64 + lane;
-    const bool live = t < T;
-    const int f = live ? fld[t] : 0;
-    unsigned long long peers = __ballot(live);
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-      const unsigned long long m = __ballot(live && ((f >> b) & 1));
-      peers &= ((f >> b) & 1) ? m : ~m;
-    }
-    const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-    // LDS operations of one wave execute in order: the next round's read sees this round's
-    // update without a hardware wait; only the compiler has to keep the order
-    int base = 0;
-    if (live) base = wave_cnt[wave][f];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (live) {
-      const int s = gstart[f] + base + rank;
-      hpos[t] = s;
-      rowmap[s] = t / L;
-      if (rank == 0) wave_cnt[wave][f] = base + __popcll(peers);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
 
-// The same layout with one workgroup PER FIELD (grid = F).  The single-workgroup kernel above takes
+// One workgroup PER FIELD (grid = F).  (A single-workgroup kernel took
 // 30-50 us at the head of the cross tower's stream, and since the NCE sampling joined it there that
-// chain is the longer one of the forward pass.  Every workgroup histograms all T field ids (LDS
+// chain is the longer one of the forward pass.)  Every workgroup histograms all T field ids (LDS
 // atomics; the ids are cached as bytes in LDS), so each knows the padded start of its own field's
 // group without talking to the others; then its 4 waves place the targets of field f in target
 // order: wave w owns a contiguous quarter of the targets, counts its matches first (ballots), and
-// after one barrier walks the quarter again handing out consecutive slots.  Stable, like the
-// kernel above, so the dW summation order is unchanged.
+// after one barrier walks the quarter again handing out consecutive slots.  Stable, so the dW
+// summation order is fixed.
 constexpr int kLayoutMwThreads = 1024;
 constexpr int kLayoutBatch = 8;          // field ids a thread fetches before it processes any of them
 __global__ void __launch_bounds__(kLayoutMwThreads) enc_group_layout_mw_kernel(
@@ -505,24 +424,12 @@ extern "C" int mapx_enc_group_layout(const int64_t* masked_index, int T, int L, 
   const size_t dyn = ((size_t)T + 15) & ~(size_t)15;
   static bool raised = false;
   if (!raised) {       // above the 64 KB default of dynamic LDS
-    MAPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_group_layout_kernel),
+    MAPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_group_layout_mw_kernel),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLayoutMaxT));
     raised = true;
   }
-  static const bool one_block = [] { const char* e = getenv("MAPX_LAYOUT_ONE_BLOCK"); return e && atoi(e) != 0; }();
-  if (one_block) {
-    hipLaunchKernelGGL(enc_group_layout_kernel, dim3(1), dim3(kLayoutThreads), dyn, stream, masked_index, T, L, F,
-                       cap_slots, rowmap, hpos, tile_group, group_start);
-  } else {
-    static bool raised_mw = false;
-    if (!raised_mw) {
-      MAPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_group_layout_mw_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLayoutMaxT));
-      raised_mw = true;
-    }
-    hipLaunchKernelGGL(enc_group_layout_mw_kernel, dim3(F), dim3(kLayoutMwThreads), dyn, stream, masked_index, T, L, F,
-                       cap_slots, rowmap, hpos, tile_group, group_start);
-  }
+  hipLaunchKernelGGL(enc_group_layout_mw_kernel, dim3(F), dim3(kLayoutMwThreads), dyn, stream, masked_index, T, L, F,
+                     cap_slots, rowmap, hpos, tile_group, group_start);
   return check_launch("enc_group_layout");
 }
 

@@ -671,8 +671,7 @@ static hipError_t launch_one_h(const GemmHArgs& a, int nsplit, int c_f32, int au
 template <int WMT, int WNT, bool A_KC, bool B_KC>
 static hipError_t launch_tile_h(const GemmHArgs& a, bool vec, int nsplit, int c_f32, int aux1_f32, hipStream_t stream) {
   // the woven K loop: vector loads and at least two K-steps in every split-K slab
-  static const bool weave_on = [] { const char* e = getenv("MAPX_BF16_WEAVE"); return !e || atoi(e) != 0; }();
-  const bool weave = weave_on && vec && (int64_t)a.K - (int64_t)a.k_chunk * (nsplit - 1) > kHBK;
+  const bool weave = vec && (int64_t)a.K - (int64_t)a.k_chunk * (nsplit - 1) > kHBK;
   if (weave) return launch_one_h<WMT, WNT, A_KC, B_KC, true, true>(a, nsplit, c_f32, aux1_f32, stream);
   return vec ? launch_one_h<WMT, WNT, A_KC, B_KC, true, false>(a, nsplit, c_f32, aux1_f32, stream)
              : launch_one_h<WMT, WNT, A_KC, B_KC, false, false>(a, nsplit, c_f32, aux1_f32, stream);

@@ -315,7 +315,7 @@ static hipError_t launch_layout_h2(GemmX3Args& a, int tile, int nsplit, hipStrea
 // slabs, k_chunk) when both operands come with a magnitude record.  Returns false when this family does not
 // build the case (scalar-load operands, a slab of one K-step, the 8-wave layout asked for): the caller goes on
 // with its own kernels.
-bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, bool xcd_on, int nsplit,
+bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, int nsplit,
                     int batch, hipStream_t stream, hipError_t* err) {
   static const bool on = [] { const char* e = getenv("MAPX_GEMM_H2"); return !e || atoi(e) != 0; }();
   if (!on || !vec) return false;
@@ -328,13 +328,11 @@ bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool 
     // of them took 83 us, 256 tiles of 64 x 64 take 71).  (The two epilogues that leave one partial row per 128-row tile keep
     // what the caller chose.)
     auto blocks = [&](int bm, int bn) { return ceil_div(g.M, bm) * ceil_div(g.N, bn) * nsplit * batch; };
-    static const int forced = [] { const char* e = getenv("MAPX_H2_TILE"); return e ? atoi(e) : -1; }();   // A/B switch
-    int mine = blocks(128, 128) >= 128 ? 3 : (blocks(128, 64) >= 160 ? 1 : 0);
-    if (forced >= 0 && mine == 3) mine = forced;
+    const int mine = blocks(128, 128) >= 128 ? 3 : (blocks(128, 64) >= 160 ? 1 : 0);
     if (mine != tile && nsplit > 1 && batch == 1) {       // the k-slice dealing depends on the tile grid (gemm_x3.hip)
       const int bm = mine == 0 ? 64 : 128, bn = mine == 3 ? 128 : 64;
       const int64_t nb1 = ceil_div(g.M, bm) * ceil_div(g.N, bn);
-      g.xcd_slices = (xcd_on && 8 % nsplit == 0 && nb1 % (8 / nsplit) == 0 && (nb1 * nsplit) % 8 == 0) ? 1 : 0;
+      g.xcd_slices = (8 % nsplit == 0 && nb1 % (8 / nsplit) == 0 && (nb1 * nsplit) % 8 == 0) ? 1 : 0;
     }
     tile = mine;
   }

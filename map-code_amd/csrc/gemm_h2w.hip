@@ -695,7 +695,6 @@ static hipError_t launch_h2w(const GemmX3Args& g, const void* planes, hipStream_
 bool gemm_f32h2w_try(GemmX3Args& g, int a_kc, bool vec, const void* planes, int nsplit, int batch, hipStream_t stream,
                      hipError_t* err) {
   static const bool on = [] { const char* e = getenv("MAPX_GEMM_H2W"); return !e || atoi(e) != 0; }();
-  static const bool narrow = [] { const char* e = getenv("MAPX_GEMM_H2W_NARROW"); return !e || atoi(e) != 0; }();
   if (!on || !planes || !a_kc || !vec || nsplit != 1 || batch != 1 || !g.amax_a) return false;
   if (g.K < 2 * kXBK || g.K % 8 != 0 || (uintptr_t)planes % 16 != 0) return false;
   // Opt-in (MAPX_GEMM_H2W8=1, read at every call so that a test can switch it): alone and repeated, the 8-wave
@@ -718,7 +717,7 @@ bool gemm_f32h2w_try(GemmX3Args& g, int a_kc, bool vec, const void* planes, int 
     *err = launch_h2w<4>(g, planes, stream);
     return true;
   }
-  if (narrow && ceil_div(g.M, 128) * ceil_div(g.N, 64) >= 128) {      // narrow products (N = 368): 128 x 64 tiles
+  if (ceil_div(g.M, 128) * ceil_div(g.N, 64) >= 128) {      // narrow products (N = 368): 128 x 64 tiles
     g.tiles_n = (int)ceil_div(g.N, 64);
     *err = launch_h2w<2>(g, planes, stream);
     return true;

@@ -551,16 +551,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_x3_v4_kernel(const float* _
   }
 }
 
-bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, bool xcd_on, int nsplit,
+bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, int nsplit,
                     int batch, hipStream_t stream, hipError_t* err);      // gemm_h2.hip
 
 bool gemm_f32h2w_try(GemmX3Args& g, int a_kc, bool vec, const void* planes, int nsplit, int batch, hipStream_t stream,
                      hipError_t* err);     // gemm_h2w.hip
-
-static bool xcd_slices_enabled() {
-  static const bool on = [] { const char* e = getenv("MAPX_XCD_SLICES"); return !e || atoi(e) != 0; }();
-  return on;
-}
 
 // Called by mapx_gemm_f32 (gemm.hip) when the split-bf16 path is selected.  Same contract.
 int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, int64_t lda, const float* B,
@@ -609,9 +604,7 @@ int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, i
   // the whole step (0.958 vs 1.069 ms): its one wave per SIMD and ~360 of 512 registers leave room for the
   // small kernels the other queue runs beside a GEMM, where the 8-wave layout (2 x 250 registers per SIMD)
   // owns the CU and every such kernel waits for a CU to drain.
-  static const int big_tile = [] { const char* e = getenv("MAPX_X3_TILE"); return e ? atoi(e) : 333; }();
-  const int cls = (a_kc && b_kc) ? 0 : a_kc ? 1 : 2;
-  int tile = (big >= 160) ? (cls == 0 ? big_tile / 100 : cls == 1 ? big_tile / 10 % 10 : big_tile % 10) : 0;
+  int tile = (big >= 160) ? 3 : 0;
   if (tile_hint >= 0 && (tile_hint & 255) <= 3) tile = tile_hint & 255;
   if (epi == MAPX_EPI_BWD_FUSED && tile == 0) tile = 1;       // one partial row per 128-row tile
   if (epi == MAPX_EPI_RELU_MASK_COLSUM) {
@@ -624,7 +617,7 @@ int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, i
   }
   // the woven K loop (4-wave layouts with vector loads) wants >= 2 K-steps in every slab
   if (tile != 2 && vec && K - (int64_t)g.k_chunk * (nsplit - 1) <= kXBK) tile = 2;
-  if (nsplit > 1 && batch == 1 && xcd_slices_enabled()) {
+  if (nsplit > 1 && batch == 1) {
     const int bm = tile == 0 ? 64 : 128, bn = (tile == 0 || tile == 1) ? 64 : 128;
     const int64_t nb1 = ceil_div(M, bm) * ceil_div(N, bn);
     g.xcd_slices = (8 % nsplit == 0 && nb1 % (8 / nsplit) == 0 && (nb1 * nsplit) % 8 == 0) ? 1 : 0;
@@ -637,7 +630,7 @@ int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, i
   // operand B's pieces already in HBM (a weight matrix: gemm_h2w.hip), else both operands cut in the kernel
   if (!hinted && ex && ex->b_planes && gemm_f32h2w_try(g, a_kc, vec, ex->b_planes, nsplit, batch, stream, &e)) {
   } else
-  if (!(scaled && gemm_f32h2_try(g, a_kc, b_kc, vec, tile, hinted, xcd_slices_enabled(), nsplit, batch, stream, &e))) {
+  if (!(scaled && gemm_f32h2_try(g, a_kc, b_kc, vec, tile, hinted, nsplit, batch, stream, &e))) {
     if (a_kc && b_kc) e = launch_layout_x3<true, true>(g, vec, tile, nsplit, stream, batch);
     else if (a_kc) e = launch_layout_x3<true, false>(g, vec, tile, nsplit, stream, batch);
     else e = launch_layout_x3<false, false>(g, vec, tile, nsplit, stream, batch);

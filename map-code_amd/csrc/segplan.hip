@@ -4,12 +4,9 @@
 // deterministic gradient reduce-by-key after the backward pass (segreduce.h).
 //
 // The sort is the hand-written LSD radix sort of radixsort.h (8-bit digits: two launches per pass, two more for the
-// runs; 9- and 12-bit digits and a scan launch per pass were measured and lost).  rocPRIM (header-only, compiled
-// into this library) serves the comparison path MAPX_SORT=1 only.
+// runs; 9- and 12-bit digits and a scan launch per pass were measured and lost).
 #include <cstdlib>
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/mapx_hip.h"
 #include "common.h"
@@ -17,33 +14,6 @@
 #include "segreduce.h"
 
 namespace mapx {
-
-struct HeadFlag {
-  const int32_t* sk;
-  __host__ __device__ inline int32_t operator()(int32_t j) const {
-    return (j == 0 || sk[j] != sk[j - 1]) ? 1 : 0;
-  }
-};
-
-__global__ void __launch_bounds__(256) seg_mark_kernel(const int32_t* __restrict__ sk,
-                                                       const int32_t* __restrict__ rank, int64_t n,
-                                                       int32_t* __restrict__ uniq,
-                                                       int32_t* __restrict__ seg_start,
-                                                       int32_t* __restrict__ n_uniq) {
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n;
-       j += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t r = rank[j];
-    if (j == 0 || sk[j] != sk[j - 1]) {
-      uniq[r - 1] = sk[j];
-      seg_start[r - 1] = (int32_t)j;
-    }
-    if (j == n - 1) {
-      n_uniq[0] = r;
-      n_uniq[1] = 0;      // owner counter of the one segment reduction that will use this plan
-      seg_start[r] = (int32_t)n;
-    }
-  }
-}
 
 static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -53,47 +23,9 @@ static int key_bits_for(int64_t V) {
   return b;
 }
 
-static size_t offsets_scan_temp_bytes(int64_t m) {
-  size_t sz = 0;
-  (void)rocprim::exclusive_scan(nullptr, sz, (const int32_t*)nullptr, (int32_t*)nullptr, 0, (size_t)m,
-                                rocprim::plus<int32_t>(), hipStream_t(0));
-  return sz;
-}
-
-static size_t scan_temp_bytes(int64_t n) {
-  size_t sz = 0;
-  auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<int32_t>(0),
-                                             HeadFlag{nullptr});
-  (void)rocprim::inclusive_scan(nullptr, sz, in, (int32_t*)nullptr, (size_t)n,
-                                rocprim::plus<int32_t>(), hipStream_t(0));
-  return sz;
-}
-
-}  // namespace mapx
-
-namespace mapx {
-// rocPRIM's radix sort with the merge-sort shortcut disabled (MergeSortLimit = 0): Onesweep
-// (one histogram launch + one scan + one decoupled-look-back pass per digit) at every size.
-using OnesweepCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                               rocprim::default_config, 0>;
-static size_t onesweep_temp_bytes(int64_t n, int bits) {
-  size_t sz = 0;
-  rocprim::counting_iterator<int32_t> iota(0);
-  (void)rocprim::radix_sort_pairs<OnesweepCfg>(nullptr, sz, (const int32_t*)nullptr, (int32_t*)nullptr, iota,
-                                               (int32_t*)nullptr, (size_t)n, 0u, (unsigned)bits,
-                                               hipStream_t(0));
-  return sz;
-}
-// measured inside the full step (MI355X): hand-written passes 1.70 ms/step, Onesweep 1.76 ms/step
-static int sort_mode() {   // 0 = hand-written LSD passes (radixsort.h, default), 1 = rocPRIM Onesweep
-  static int m = [] { const char* e = getenv("MAPX_SORT"); return e ? atoi(e) : 0; }();
-  return m;
-}
-
 struct PlanWs {   // carve-up of the caller's workspace
   int32_t *tk, *tv, *bh, *off;
-  void* scan;
-  size_t scan_bytes, total;
+  size_t total;
 };
 static PlanWs plan_ws(void* ws, int64_t n) {
   PlanWs w;
@@ -105,11 +37,6 @@ static PlanWs plan_ws(void* ws, int64_t n) {
   w.tv = reinterpret_cast<int32_t*>(base + take((size_t)n * 4));
   w.bh = reinterpret_cast<int32_t*>(base + take(hist * 4));
   w.off = reinterpret_cast<int32_t*>(base + take(hist * 4));
-  const size_t a = offsets_scan_temp_bytes((int64_t)hist), b = scan_temp_bytes(n);
-  const size_t c = onesweep_temp_bytes(n, 31);
-  w.scan_bytes = a > b ? a : b;
-  if (c > w.scan_bytes) w.scan_bytes = c;
-  w.scan = base + take(w.scan_bytes);
   w.total = o;
   return w;
 }
@@ -140,16 +67,10 @@ extern "C" int mapx_seg_plan(const int32_t* keys, int64_t n, int64_t V, void* ws
     return MAPX_EWORKSPACE;
   }
   const int bits = key_bits_for(V), passes = radix_passes(bits), nblocks = radix_blocks(n);
-  if (sort_mode() == 1) {
-    rocprim::counting_iterator<int32_t> iota(0);
-    size_t sb = w.scan_bytes;
-    MAPX_HIP(rocprim::radix_sort_pairs<OnesweepCfg>(w.scan, sb, keys, sorted_keys, iota, perm, (size_t)n, 0u,
-                                                    (unsigned)bits, stream));
-  }
   // ping-pong so that the last pass lands in (sorted_keys, perm)
   const int32_t* src_k = keys;
   const int32_t* src_v = nullptr;
-  for (int p = 0; p < passes && sort_mode() == 0; ++p) {
+  for (int p = 0; p < passes; ++p) {
     const int shift = p * kSortBits;
     const int db = (bits - shift) < kSortBits ? (bits - shift) : kSortBits;
     const int bins = 1 << db;
@@ -167,19 +88,10 @@ extern "C" int mapx_seg_plan(const int32_t* keys, int64_t n, int64_t V, void* ws
     src_k = dst_k;
     src_v = dst_v;
   }
-  if (sort_mode() == 1) {   // comparison path: device scan + mark
-    auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<int32_t>(0),
-                                                  HeadFlag{sorted_keys});
-    size_t sb = w.scan_bytes;
-    MAPX_HIP(rocprim::inclusive_scan(w.scan, sb, flags, rank, (size_t)n, rocprim::plus<int32_t>(), stream));
-    hipLaunchKernelGGL(seg_mark_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, sorted_keys, rank, n,
-                       uniq, seg_start, n_uniq);
-  } else {
-    hipLaunchKernelGGL(seg_count_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys, n,
-                       w.off);
-    hipLaunchKernelGGL(seg_mark_tiles_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys,
-                       n, (const int32_t*)w.off, rank, uniq, seg_start, n_uniq);
-  }
+  hipLaunchKernelGGL(seg_count_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys, n,
+                     w.off);
+  hipLaunchKernelGGL(seg_mark_tiles_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys,
+                     n, (const int32_t*)w.off, rank, uniq, seg_start, n_uniq);
   return check_launch("seg_plan");
 }
 

@@ -30,8 +30,7 @@ constexpr int kSegChunk = 32;  // sorted positions per lane group in pass A ...
 constexpr int kSegChunkSmall = 16;
 constexpr int64_t kSegSmallN = 1 << 18;
 inline int seg_chunk_for(int64_t n) {
-  static const int64_t small_n = [] { const char* e = getenv("MAPX_SEG_SMALL_N"); return e ? atoll(e) : kSegSmallN; }();
-  return n <= small_n ? kSegChunkSmall : kSegChunk;
+  return n <= kSegSmallN ? kSegChunkSmall : kSegChunk;
 }
 
 struct SegPlanView {

@@ -50,7 +50,7 @@ class RowTable:
     def num_rows(self):
         return self.p0.shape[0]
 
-    def prepare(self, keys_i32, need_plan, defer_plan=False, through_replay=False, catch_up=True):
+    def prepare(self, keys_i32, need_plan, defer_plan=False, through_replay=False):
         """Called by the forward pass with this step's row ids (repeats allowed).
         * stale rows among them are brought up to date on the current stream, straight from the
           raw id list (ownership by atomicCAS in the kernel): nothing on the critical path
@@ -72,20 +72,10 @@ class RowTable:
         if self.lazy is not None and through_replay:
             self.lazy.refresh_coef()
         elif self.lazy is not None and (self.lazy.stale or torch.cuda.is_current_stream_capturing()):
-            if catch_up:
-                self.lazy.catch_up_raw(keys_i32)
-            else:
-                self.pending_catch_up = keys_i32        # the caller runs it later on this stream (catch_up_pending)
+            self.lazy.catch_up_raw(keys_i32)
         if need_plan and not defer_plan:
             self.plan.start()
         return self.plan
-
-    def catch_up_pending(self):
-        """The catch-up pass prepare(catch_up=False) left out (before the first kernel that reads the rows)."""
-        keys = getattr(self, "pending_catch_up", None)
-        if keys is not None:
-            self.pending_catch_up = None
-            self.lazy.catch_up_raw(keys)
 
     def start_plan(self, after=None):
         """`after`: a stream whose work enqueued so far the sort must not delay (PlanSlot.start_many)."""
@@ -120,11 +110,6 @@ class RowTable:
 # and worth nothing on the step (one box, tools/ab_env.sh): gather 5.0 -> 9.0 us, the 7.9-us catch-up launch gone,
 # the update +1.4 us: 0.6884 / 0.6907 ms per step against 0.6880 / 0.6899 with the catch-up pass.  Opt-in.
 EMB_LAZY_FOLD = os.environ.get("MAPX_EMB_LAZY_FOLD", "0") == "1"
-JOIN_DEEP_FIRST = int(os.environ.get("MAPX_JOIN_DEEP_FIRST", "1"))
-DX_FIRST = os.environ.get("MAPX_DX_FIRST", "0") == "1"                   # A/B switch: an MLP layer's dX product before its dW
-IMPLIED = os.environ.get("MAPX_PLAN_IMPLIED", "1") == "1"
-HEAD_DW_LATE = os.environ.get("MAPX_HEAD_DW_LATE", "1") == "1"     # A/B switch (tools/ab_env.sh)
-PAD_K = os.environ.get("MAPX_PAD_K", "1") == "1"                   # A/B switch: _Linear with an input width % 8 != 0
 
 # callables (table, plan) run on the plan stream right after a table's plan has been enqueued
 # (trainer.GraphedBackward publishes the plan's unique-row count to the host from there)
@@ -146,14 +131,10 @@ class PlanSlot:
         self.table, self.keys, self.value = table, keys_i32, None
         self.origin = torch.cuda.current_stream()
         self.ready = ops.record_event()
-        self.partners = []          # other tables' slots to build in the same chain of launches (start_many)
 
     def start(self, after=None):
         if self.value is not None:
             return
-        if self.partners:
-            partners, self.partners = self.partners, []
-            return PlanSlot.start_many([self] + partners, implied=partners if IMPLIED else ())
         keys, self.keys = self.keys, None
         side = _side_stream(keys.device, self.table.name)
         forked = ops.stream_wait_event(side, self.ready, self.origin)
@@ -234,8 +215,7 @@ class _Gather(Function):
     def backward(ctx, g):
         if ctx.plan is None:
             raise RuntimeError("embedding backward without a segment plan")
-        if (getattr(ctx.table, "mark_dense_ready", False) and ops.tail_overlap(g.dtype == torch.bfloat16)
-                and not parallel.exchanging()):
+        if getattr(ctx.table, "mark_dense_ready", False) and not parallel.exchanging():
             # this node is the model's last: every dense gradient of THIS stream is enqueued (the tower stream's
             # are behind it in that stream's own order, which is where the optimizer's dense half runs) — the
             # optimizer's dense half need not wait for the table's
@@ -254,9 +234,6 @@ class _Gather(Function):
             if g2.dtype != g.dtype or g2.shape != g.shape:
                 g, g2 = g + g2, None
         ctx.table.sparse_grad = (plan, ops.seg_reduce_rows(plan, g, ctx.width, src2=g2), None)
-        lazy = ctx.table.lazy
-        if lazy is not None and getattr(lazy, "early_now", False) and getattr(ctx.table, "mark_dense_ready", False):
-            lazy.update()                 # nothing else of the step feeds this table: its rows move at once
         if not ops.step_window[0]:
             ops.join_pending()            # no optimizer.step() follows at once: leave nothing open behind backward()
         return None, None, None, None, None
@@ -422,7 +399,7 @@ class Embeddings(nn.Module):
         # a training step reads the rows through their pending updates inside the gather (no catch-up launch at the head
         # of the step; the gradient update writes each row once); eval / no optimizer: the catch-up pass or nothing
         lazy = self.table.lazy
-        fold = (EMB_LAZY_FOLD and need_grad and lazy is not None and lazy.replay_in_readers() and lazy.m1 is None
+        fold = (EMB_LAZY_FOLD and need_grad and lazy is not None and lazy.m1 is None
                 and w.shape[1] % (8 if self.compute_dtype == torch.bfloat16 else 4) == 0 and w.is_cuda)
         if keys is not None:
             self.table.prepare(keys, need_grad, defer_plan=self.defer_plan, through_replay=fold)
@@ -513,7 +490,7 @@ class _JoinLink:
         self.t = self.dx0 = self.g = self.dz = None
 
     def usable(self, dz, final):
-        return (ops.JOIN_FUSE and ops.DEFER_COLSUM and dz.dtype == torch.float32 and final.dtype == torch.float32
+        return (ops.JOIN_FUSE and dz.dtype == torch.float32 and final.dtype == torch.float32
                 and self.relu.sb is not None and self.sb_cross is not None and self.x0 is not None
                 and self.D % 4 == 0 and final.shape[1] % 4 == 0 and final.shape[1] > self.D
                 and ops.row_sliceable(final) and self.x0.is_contiguous() and self.u.is_contiguous())
@@ -534,21 +511,12 @@ def join_bwd_input(dz, w, final, link):
         return torch.empty(1, 1, dtype=final.dtype, device=final.device).expand(final.shape[0], Nn)    # never read
     main = torch.cuda.current_stream() if dz.is_cuda else None
     side = ops.aux_stream("tower", dz.device) if dz.is_cuda else None
-    dzr = None
-    fork_ev = None
-    if JOIN_DEEP_FIRST and dz.is_cuda:
-        # (the graph runtime keeps a node's FIRST-captured successor on the node's hardware queue and sends later ones
-        # to the other queue, behind whatever that one holds — at this point of the step the segment plans' sort
-        # chain: the deep tower's product, the longer backward chain's first link, is enqueued first)
-        if JOIN_DEEP_FIRST == 2:
-            fork_ev = ops.record_event()         # the cross product forks from HERE: it does not wait for the deep one,
-                                                 # and the deep tower's chain is the deep product's first successor
-        ops.dbg_sleep("join_deep")
-        dzr = ops.linear_bwd_input(dz, ops.cols(w, D, None), relu_of=final[:, D:], colsum_to=link.relu.sb)
-    if fork_ev is not None:
-        forked = ops.stream_wait_event(side, fork_ev, main)
-    else:
-        forked = ops.stream_wait(side, main) if dz.is_cuda else False
+    # (the graph runtime keeps a node's FIRST-captured successor on the node's hardware queue and sends later ones
+    # to the other queue, behind whatever that one holds — at this point of the step the segment plans' sort
+    # chain: the deep tower's product, the longer backward chain's first link, is enqueued first)
+    ops.dbg_sleep("join_deep")
+    dzr = ops.linear_bwd_input(dz, ops.cols(w, D, None), relu_of=final[:, D:], colsum_to=link.relu.sb)
+    forked = ops.stream_wait(side, main) if dz.is_cuda else False
     with (torch.cuda.stream(side) if forked else contextlib.nullcontext()):
         ops.dbg_sleep("join_cross")
         g, t, dx0, part = ops.gemm_bwd_fused(dz, ops.cols(w, 0, D), D, x0=link.x0, u=link.u, plus_v=link.plus_v)
@@ -556,9 +524,6 @@ def join_bwd_input(dz, w, final, link):
     if forked:
         dz.record_stream(side)
         ops.pending_joins.append((main, side))
-    if dzr is None:
-        ops.dbg_sleep("join_deep")
-        dzr = ops.linear_bwd_input(dz, ops.cols(w, D, None), relu_of=final[:, D:], colsum_to=link.relu.sb)
     link.relu.premasked = True
     link.t, link.dx0, link.g, link.dz = t, dx0, g, dzr
     return torch.empty(1, 1, dtype=final.dtype, device=final.device).expand(final.shape[0], Nn)    # never read
@@ -570,7 +535,7 @@ class _Linear(Function):
         x = x.contiguous()
         half = ops.is_bf16(x)
         ctx.kpad, ctx.sw_real = 0, None
-        if (PAD_K and not half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
+        if (not half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
                 and link_in is None):
             # An input width that is not a multiple of 8 floats (DeepFM's heads read cat([dnn, lr + fm]): 1001 columns)
             # leaves the GEMMs their scalar operand path — 172 / 161 / 123 us for the forward / dW / dX of a
@@ -602,18 +567,11 @@ class _Linear(Function):
         if ctx.relu and ctx.link_out is not None and ctx.link_out.premasked:
             # the consumer's dX GEMM has applied this layer's mask and queued its bias gradient (_ReluLink)
             dz, db = (gy if ops.row_sliceable(gy) else gy.contiguous()), None
-            dw_after = None
-            if DX_FIRST and sw is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[0] and not ctx.kpad:
-                # the layer below waits for this node's dX, only the optimizer for its dW: the dX product is enqueued
-                # first, the dW product behind it on the same stream
-                dw_after = (dz, x, sw)
-                dw = None
-            else:
-                dw = ops.linear_bwd_weight(dz, x, out=sw, defer=True) if ctx.needs_input_grad[1] else None
-                dw = None if sw is not None else dw
+            dw = ops.linear_bwd_weight(dz, x, out=sw, defer=True) if ctx.needs_input_grad[1] else None
+            dw = None if sw is not None else dw
         elif ctx.relu and (ctx.half or gy.shape[1] % 4 == 0):      # ReLU mask and bias gradient in one pass over dY
             dz, db = ops.relu_mask_colsum(gy, y, db=sb, defer=True)      # gy may be a slice of d(concat)
-            if (HEAD_DW_LATE and isinstance(ctx.link_in, _JoinLink) and ops.step_window[0] and sw is not None
+            if (isinstance(ctx.link_in, _JoinLink) and ops.step_window[0] and sw is not None
                     and ctx.needs_input_grad[1]):
                 # The heads' first layer (RFD's 1368 -> 736 predictor): both towers' backward passes wait for this
                 # node's dX, only the optimizer for its dW (83 us alone on the stream while the other queue idled) —
@@ -623,7 +581,7 @@ class _Linear(Function):
                     dz.record_stream(cur)
                     x.record_stream(cur)
                     ops.linear_bwd_weight(dz, x, out=sw, defer=True)
-                ops.add_late_task(head_dw, dense=True)
+                ops.add_late_task(head_dw)
                 dw = None
             else:
                 dw = ops.linear_bwd_weight(dz, x, out=sw, defer=True) if ctx.needs_input_grad[1] else None
@@ -641,8 +599,6 @@ class _Linear(Function):
                 link.premasked = True
             else:
                 dx = ops.linear_bwd_input(dz, w)
-        if locals().get("dw_after") is not None:
-            ops.linear_bwd_weight(dw_after[0], dw_after[1], out=dw_after[2], defer=True)
         if ctx.kpad:                              # operands padded to a multiple of 8 columns in forward: cut them off
             K = w.shape[1] - ctx.kpad
             if dx is not None:
@@ -782,7 +738,6 @@ class _CrossTower(Function):
         ws = saved[2 * n:3 * n]
         if not ops.row_sliceable(g):
             g = g.contiguous()                   # else read in place: a slice of d(concat) costs no copy
-        ops.run_side_tasks()                     # this chain has slack against the deep tower's
         ops.dbg_sleep("cross_bwd")
         grads = [None] * (2 * n)
         D = x0.shape[1]
@@ -799,7 +754,7 @@ class _CrossTower(Function):
         f32 = g.dtype == torch.float32 and x0.dtype == torch.float32
         have_slots = all(sw is not None and sb is not None for sw, sb in ctx.slots)
         # fused epilogues / one launch for all weight gradients: fp32, optimizer-owned gradient slots, 16-byte rows
-        ok = ops.DEFER_COLSUM and f32 and have_slots and D % 4 == 0 and n <= 4
+        ok = f32 and have_slots and D % 4 == 0 and n <= 4
         fuse, batch_dw = ops.CROSS_FUSE and ok, ops.DW_BATCH and ok
         pend = []
         for i in range(n - 1, -1, -1):
@@ -962,7 +917,7 @@ class _CinStack(Function):
         units = [w.shape[0] for w in ws]
         out = torch.empty(B, sum(units), dtype=torch.float32, device=x3.device)
         xi, saved, col = x0t, [], 0
-        pad = PAD_K and B * E >= 256
+        pad = B * E >= 256
         wps = []
         for w, b in zip(ws, bs):
             # The Hadamard matrix has F * H_i columns (529, 1150 at Avazu's sizes) and the layer `units` = 50 outputs:
@@ -1003,7 +958,7 @@ class _CinStack(Function):
             Kc, Kp = w[0].numel(), wp.shape[1]
             db = ops.colsum(dy, out=sb)
             grads[2 * i + 1] = None if sb is not None else db
-            if Kp != Kc or (PAD_K and u % 8 != 0 and dy.shape[0] >= 256):
+            if Kp != Kc or (u % 8 != 0 and dy.shape[0] >= 256):
                 # dy's `units` columns padded to a multiple of 8 as well (a 15-MB copy): dW and dX both read it
                 up = (u + 7) // 8 * 8
                 dyp = torch.nn.functional.pad(dy, (0, up - u))

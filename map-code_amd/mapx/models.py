@@ -2,7 +2,6 @@
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
 is a gfx950 kernel."""
 import logging
-import os
 
 import torch
 from torch import nn
@@ -15,40 +14,29 @@ from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, HipLinear, MLPBl
 from .nce import IndexLinear
 
 logger = logging.getLogger(__name__)
-GROUPED_ENCODER = os.environ.get("MAPX_GROUPED_ENC", "1") == "1"
-NCE_EARLY = os.environ.get("MAPX_NCE_EARLY", "1") == "1"
-# both tables' segment plans from one chain of launches (8 launches instead of 16, 0.112 instead of
-# 0.19 ms of sorting per step): "fwd" = started in forward behind the towers, "bwd" = started by the
-# head's backward node (where the sampled ids' sort alone starts otherwise), "off" = one chain per
-# table; "auto" = fwd.  What decided it was WHERE the graph runtime runs the chain: captured as a branch
-# of its own it was run ahead of the deep tower's GEMMs on the queue the two share, and the joint chain
-# lost in fp32 (1.306 fwd / 1.305 bwd vs 1.200 off) and won only a little in bf16 (0.752 vs 0.793).  Made
-# to wait for the deep tower's GEMMs (PLAN_AFTER_DNN below) it wins in both: fp32 0.908 / 0.912 vs 0.935 /
-# 0.937 ms (off), bf16 0.690 vs 0.744 (fwd without the wait) vs 0.783 (off).  (Also measured in fp32: the
-# embedding's sort started by the head's backward node right behind the sampled ids' sort — so that the
-# head's backward no longer waits 34 us for the latter — 1.13 vs 0.96 ms.)
-JOINT_PLAN = os.environ.get("MAPX_JOINT_PLAN", "auto")
-# the joint plan in forward waits for the deep tower's GEMMs to be on their way (see above)
-# the grouped encoder's slot layout ahead of the deep tower (main stream) or on the cross tower's stream.  Round 2: main
-# won (0.869 / 0.873 vs 0.876 / 0.882 ms); round 3, after the backward pass changed (tools/flag_sweep.py): the tower
-# stream wins, 0.8058 vs 0.8223 ms; round 4: with the two-piece fp16 GEMMs cutting both operands main won (0.7175 vs
-# 0.7307), with the weights' planes (gemm_h2w.hip) the tower stream again (0.7120 vs 0.7175) — kept there
-# "auto": on the main stream when the cross tower is at least 512 columns wide (Criteo-shaped: its stream is the longer
-# one of the forward pass, 1.0026 -> 0.9924 ms with the layout off it), on the cross tower's stream otherwise (Avazu-
-# shaped: equal either way, 0.7064 vs 0.7070)
-LAYOUT_ON_MAIN = os.environ.get("MAPX_LAYOUT_ON_MAIN", "auto")
-PLAN_AFTER_DNN = os.environ.get("MAPX_PLAN_AFTER_DNN", "1")       # 1 | tower | 0: what the joint plan goes behind
-# RFD / finetune steps: what the one table's sort goes behind: auto | main | tower | 0 (A/B switch)
-PLAN_AFTER_TRUNK = os.environ.get("MAPX_PLAN_AFTER_TRUNK", "auto")
+WIDE_CROSS_TOWER = 512        # columns: from here on the cross tower's stream is the longer one (Criteo-shaped inputs)
 
-X0_LINK = os.environ.get("MAPX_X0_LINK", "1") == "1"       # A/B switch of layers._X0Link
-# Round 4 (the two-piece fp16 GEMMs made the towers a third shorter): the NCE head's sampling + catch-up (HBM-bound,
-# 80 us in the graph) BEHIND the cross tower's GEMMs on the tower stream instead of in front of them — in front, the
-# cross tower ended 50 us after the deep one and the encoder waited for it; the main stream joins the tower stream at
-# the cross tower's end (an event), the loss kernel alone waits for the sampled ids (`nce_idx._ready`)
-CATCHUP_AFTER_CROSS = os.environ.get("MAPX_CATCHUP_AFTER_CROSS", "0") == "1"     # A/B switch (DCNV2.forward)
-NCE_AFTER_CROSS = os.environ.get("MAPX_NCE_AFTER_CROSS", "0") == "1"
-EARLY_NCE_ALL = os.environ.get("MAPX_EARLY_NCE_ALL", "1") == "1"   # A/B switch: BaseModel._sample_early
+
+def layout_on_main(D):
+    """The grouped encoder's slot layout ahead of the deep tower (main stream, True) or on the cross tower's stream:
+    on the main stream when the cross tower is at least 512 columns wide (Criteo-shaped: its stream is the longer
+    one of the forward pass, 1.0026 -> 0.9924 ms with the layout off it), on the cross tower's stream otherwise
+    (Avazu-shaped: equal either way, 0.7064 vs 0.7070)."""
+    return D >= WIDE_CROSS_TOWER
+
+
+def plan_after_main(pretrain, f32_trunk, D):
+    """RFD / finetune steps (one table, one sort chain): the sort goes behind what the main stream (the deep tower's
+    forward GEMMs, True) or the tower stream (the cross tower's, False) holds.  Forked from the ids alone the graph
+    runtime ran it LAST, 127 us of sort + reduction + row update exposed behind the backward pass; behind the deep
+    tower's forward GEMMs it runs beside the head: RFD 0.946 -> 0.845 ms, finetune 0.765 -> 0.664.  Behind the CROSS
+    tower's (the head is short then and the deep tower's backward would wait for the sort on its queue): finetune
+    0.636 -> 0.619 ms, RFD 0.768 -> 0.786 — so by the head.  After the join's capture order changed the finetune step
+    with the fp32 trunk at Avazu's width also prefers the main stream (0.515 / 0.513 -> 0.493 / 0.492 ms); its
+    Criteo-shaped (0.623 vs 0.641) and bf16 (0.345 vs 0.376) forms keep the tower stream.  (The single-stream
+    backbones measured neutral (RFD / CTR) or worse (DNN + MFP): left as they were.)"""
+    return pretrain or (f32_trunk and D < WIDE_CROSS_TOWER)
+
 
 _OTHER_BACKBONES = ("fignn", "fgcnn")
 
@@ -106,7 +94,7 @@ class BaseModel(nn.Module):
         """MFP over a single-stream trunk (DNN, DeepFM, xDeepFM, AutoInt): the NCE head's sampling and the lazy
         catch-up of the sampled rows need only the targets — they run on the tower stream beside the trunk instead of
         between the trunk and the loss (as DCNV2.forward does by hand).  -> (ids | None, join state)."""
-        if not (EARLY_NCE_ALL and self.config.pretrain and self.config.pt_type == "MFP" and masked_index is not None
+        if not (self.config.pretrain and self.config.pt_type == "MFP" and masked_index is not None
                 and labels is not None and labels.is_cuda):
             return None, None
         main = torch.cuda.current_stream()
@@ -145,7 +133,7 @@ class BaseModel(nn.Module):
         if (is_pretrain is None and cfg.pretrain) or is_pretrain:
             if cfg.pt_type == "MFP":
                 crit = self.mfp_criterion
-                if (GROUPED_ENCODER and crit.supports_grouped_encoder() and inputs.shape[1] % 8 == 0
+                if (crit.supports_grouped_encoder() and inputs.shape[1] % 8 == 0
                         and inputs.dtype == torch.float32):
                     # only the L masked fields' blocks of feat_encoder are computed (26 %)
                     loss, _logits, _idx = crit.forward_with_encoder(labels, inputs, self.feat_encoder,
@@ -238,20 +226,11 @@ class DCNV2(BaseModel):
 
     def _grouped_head(self, masked_index):
         return (self._mfp_head(masked_index) and self.embed.compute_dtype == torch.float32
-                and GROUPED_ENCODER and self.mfp_criterion.supports_grouped_encoder()
+                and self.mfp_criterion.supports_grouped_encoder()
                 and self.feat_encoder.in_features % 8 == 0)
 
     def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
         groups, nce_idx, join = None, None, None
-        planes_ev = None
-        if ops._dirty_planes and input_ids.is_cuda and self.config.num_hidden_layers > 0:
-            # the weights' planes of this step (ops.PLANES_AT_START): on the tower stream, beside the step's head (catch-up,
-            # gather: small grids); the deep tower's first product waits for them
-            tower0 = ops.aux_stream("tower", input_ids.device)
-            if ops.stream_wait(tower0, torch.cuda.current_stream()):
-                with torch.cuda.stream(tower0):
-                    ops.refresh_dirty_planes()
-                    planes_ev = ops.record_event()
         feat_embed = ops.flat_rows(self.embed(input_ids))
         if self.config.num_hidden_layers > 0:
             # Three independent chains leave the gather: the cross tower (small D x D GEMMs on a
@@ -274,7 +253,7 @@ class DCNV2(BaseModel):
                 from .layers import _JoinLink
                 join = _JoinLink(D)            # towers -> the head's first layer (fused backward epilogue)
             x0_link = None
-            if (X0_LINK and direct and torch.is_grad_enabled() and self.embed.table.plan is not None
+            if (direct and torch.is_grad_enabled() and self.embed.table.plan is not None
                     and not self.embed.embed_norm and not (self.embed.dropout.p > 0 and self.training)):
                 from .layers import _X0Link
                 x0_link = _X0Link(main)        # cross tower -> the gather's backward (no elementwise add, no wait)
@@ -283,7 +262,7 @@ class DCNV2(BaseModel):
             if feat_embed.dtype == torch.float32:
                 # ONE magnitude record for the concatenated output: both towers' last kernels raise it (ops.out_record)
                 ops.tag(final_buf, ops.amax_record(final_buf.device))
-            if (LAYOUT_ON_MAIN == "1" or (LAYOUT_ON_MAIN == "auto" and D >= 512)) and self._grouped_head(masked_index):
+            if layout_on_main(D) and self._grouped_head(masked_index):
                 # the grouped encoder's slot layout (one 15-us launch) ahead of the deep tower, which by now
                 # has ~45 us of slack against the cross tower's stream (round 1 had it the other way round)
                 groups = ops.EncGroups(masked_index, self.config.num_fields)
@@ -292,69 +271,31 @@ class DCNV2(BaseModel):
                     # the cross tower has ~70 us of slack against the deep one: the slot layout of
                     # the grouped encoder (one single-workgroup launch) rides on its stream
                     groups = ops.EncGroups(masked_index, self.config.num_fields)
-                early_nce = self._mfp_head(masked_index) and NCE_EARLY and labels is not None \
-                    and (groups is not None or self.embed.compute_dtype != torch.float32)
-                after_cross = early_nce and NCE_AFTER_CROSS and groups is not None and direct
-                if early_nce and not after_cross:
+                if self._mfp_head(masked_index) and labels is not None \
+                        and (groups is not None or self.embed.compute_dtype != torch.float32):
                     # the NCE head's sampling and the lazy catch-up of the sampled rows need only
                     # the targets: HBM-bound kernels that run beside the deep tower's first GEMMs
-                    # instead of alone between the towers and the loss (same branch, no new one).  (Round 2: BEHIND
-                    # the cross tower's GEMMs instead, the trunk joining at the cross tower's end and only the
-                    # loss kernel waiting for the sampling: 1.02 vs 0.91 ms fp32, 0.72 vs 0.66 bf16.)
-                    # (CATCHUP_AFTER_CROSS: the draw stays here — the segment plans' sort waits for it — and the
-                    # catch-up of the sampled rows goes BEHIND the cross tower's products on this stream, in front of
-                    # the join: since the fp32 products became 1.3-1.9 x faster the cross tower's stream, not the deep
-                    # tower's, is the longer one in forward)
-                    nce_idx = self.mfp_criterion.sample_ids(labels, noise_samples, catch_up=not CATCHUP_AFTER_CROSS)
+                    # instead of alone between the towers and the loss (same branch, no new one)
+                    nce_idx = self.mfp_criterion.sample_ids(labels, noise_samples)
                 cross_output = self.cross_net(feat_embed, out=ops.alias_cols(final_buf, 0, D) if direct else None,
                                               link=join, x0_link=x0_link)
-                if early_nce and not after_cross and CATCHUP_AFTER_CROSS:
-                    self.mfp_criterion.table.catch_up_pending()
-                cross_done = None
-                if after_cross:
-                    cross_done = ops.record_event()
-                    nce_idx = self.mfp_criterion.sample_ids(labels, noise_samples)
-                    nce_idx._ready = (ops.record_event(), tower)
-            if planes_ev is not None:
-                ops.stream_wait_event(main, planes_ev, tower)
             dnn_output = self.parallel_dnn(feat_embed, out=ops.alias_cols(final_buf, D, H) if direct else None,
                                            link_last=join.relu if join is not None else None)
-            # Both tables' segment plans from ONE chain of launches (8 instead of 8 + 8), when the
-            # sampled ids exist already (drawn early on the tower stream).  (Round 1 note: the sampled
-            # ids' sort as a chain of its own ahead of the embedding's cost 1.375 vs 1.21 ms.)
-            mode = JOINT_PLAN
-            if mode == "auto":
-                mode = "fwd"
-            if nce_idx is not None and mode == "fwd":
+            # Both tables' segment plans from ONE chain of launches (8 instead of 8 + 8, 0.112 instead of 0.19 ms of
+            # sorting per step), when the sampled ids exist already (drawn early on the tower stream).  The chain
+            # waits for the deep tower's GEMMs to be on their way: captured as a branch of its own the graph runtime
+            # ran it ahead of them on the queue the two share.
+            if nce_idx is not None:
                 from .layers import PlanSlot
-                from .layers import IMPLIED
                 # (the tower stream forked from the main one behind the gather: the sampled ids' event
                 # implies that the embedding's keys are final)
                 PlanSlot.start_many([self.embed.table.plan, self.mfp_criterion.table.plan],
-                                    implied=[self.embed.table.plan] if IMPLIED else (),
-                                    after={"1": main, "tower": tower}.get(PLAN_AFTER_DNN))
-            elif nce_idx is not None and mode == "bwd" and self.mfp_criterion.table.plan is not None:
-                # the head's backward node starts both (PlanSlot.start_many from IndexLinear's partner list)
-                self.mfp_criterion.table.plan.partners = [self.embed.table.plan]
+                                    implied=[self.embed.table.plan], after=main)
             else:
-                # (RFD / finetune steps: one table, one chain.  Forked from the ids alone the graph runtime ran it
-                # LAST, 127 us of sort + reduction + row update exposed behind the backward pass; behind the deep
-                # tower's forward GEMMs ("main") it runs beside the head: RFD 0.946 -> 0.845 ms, finetune 0.765 -> 0.664.  The
-                # single-stream backbones below measured neutral (RFD / CTR) or worse (DNN + MFP): left as they were)
-                # Behind the CROSS tower's (the head is short then and the deep tower's backward would wait for the
-                # sort on its queue): finetune 0.636 -> 0.619 ms, RFD 0.768 -> 0.786 — so by the head.
-                # Round 4 (tools/mini_sweep_steps.sh, after the join's capture order changed): the finetune step with
-                # the fp32 trunk at Avazu's width now also prefers "main" (0.515 / 0.513 -> 0.493 / 0.492 ms); its
-                # Criteo-shaped (0.623 vs 0.641) and bf16 (0.345 vs 0.376) forms keep "tower".
-                narrow_f32 = self.embed.compute_dtype == torch.float32 and D < 512
-                where = PLAN_AFTER_TRUNK if PLAN_AFTER_TRUNK != "auto" else \
-                    ("main" if (self.config.pretrain or narrow_f32) else "tower")
-                self.embed.table.start_plan(after={"main": main, "tower": tower}.get(where))
-            if cross_done is not None:
-                ops.stream_wait_event(main, cross_done, tower)       # (the sampled ids: waited for by the loss kernel)
-                ops.pending_joins.append((main, tower))
-            else:
-                ops.stream_wait(main, tower)
+                # (RFD / finetune steps: one table, one chain)
+                f32_trunk = self.embed.compute_dtype == torch.float32
+                self.embed.table.start_plan(after=main if plan_after_main(self.config.pretrain, f32_trunk, D) else tower)
+            ops.stream_wait(main, tower)
             if forked:
                 feat_embed.record_stream(tower)
                 final_buf.record_stream(tower)

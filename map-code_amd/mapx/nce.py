@@ -59,16 +59,12 @@ class AliasMultinomial(nn.Module):
         return ops.alias_draw(self.packed(), targets, K, seed, offset, offset_dev)
 
 
-def _head_side():
-    return HEAD_SIDE
-
-
 class _NceLoss(Function):
     @staticmethod
     def forward(ctx, enc, emb_w, bias_w, logq, masked_index, idx, crit, F, P, want_logits):
         # inside a training step (the Trainer's window) the head's backward follows at once: its first launch also
         # forms the loss totals, one launch less between the loss and the backward pass
-        later = TOTALS_LATER and ops.step_window[0] and ctx.needs_input_grad[0]
+        later = ops.step_window[0] and ctx.needs_input_grad[0]
         o = ops.nce_fwd(enc.contiguous(), masked_index, idx, emb_w, bias_w.view(-1), logq, F, P,
                         want_logits=want_logits, totals_later=later, lazy=getattr(idx, "_lazy", None))
         ctx.totals = o["totals"]
@@ -89,15 +85,12 @@ class _NceLoss(Function):
         ctx.totals = None
         if ctx.plan is None:
             raise RuntimeError("NCE backward without a segment plan")
-        lazy = ctx.crit.table.lazy
-        early = lazy is not None and getattr(lazy, "early_now", False)
-        if (DEFER_PLAN_JOIN and getattr(ctx.crit, "towers_follow", False) and ops.step_window[0] and _head_side()
-                and dh.is_cuda and (early or ops.HEAD_SIDE_REDUCE_ONLY)):
+        if getattr(ctx.crit, "towers_follow", False) and ops.step_window[0] and dh.is_cuda:
             # The dense-encoder head (bf16 mode).  Joined HERE the sort of the sampled ids held the main stream: with
             # bf16 GEMMs the sort chain outlasts the forward pass (by 40 us at Avazu's sizes, 70 at Criteo's) and the
             # whole backward pass waited for it.  The join moves behind the encoder's backward (the towers' join node
-            # runs it: ~130 us of main-stream work later, when the sort is long done), and the table's gradient + row
-            # update go to the END of the cross tower's chain, as in the grouped head (a tower <- plan edge of its own
+            # runs it: ~130 us of main-stream work later, when the sort is long done), and the table's gradient
+            # goes to the END of the cross tower's chain, as in the grouped head (a tower <- plan edge of its own
             # is what segfaults in hipStreamEndCapture; the tower stream syncs with the main one at the join node).
             slot, crit, K, P = ctx.plan, ctx.crit, ctx.K, ctx.P
             holder = {}
@@ -107,47 +100,28 @@ class _NceLoss(Function):
                 plan = holder.get("plan") or slot.get()
                 ge, gb = ops.nce_table_grad(plan, dlogit, h, K, P, gscale=gl)
                 crit.table.sparse_grad = (plan, ge, gb)
-                if early:            # (with a gradient exchange or a clipping norm ahead the row update has to wait)
-                    lazy.update()
                 cur = torch.cuda.current_stream()
                 for t in (dlogit, h, gl) + tuple(plan.tensors()):
                     t.record_stream(cur)
             ops.add_late_task(table_work)
             return denc, None, None, None, None, None, None, None, None, None
         plan = ctx.plan.get()
-        if lazy is not None and getattr(lazy, "early_now", False) and _head_side() and dh.is_cuda:
-            # as in _EncNceLoss.backward: the table's gradient and row update leave the main chain
-            main, side = torch.cuda.current_stream(), ops.aux_stream("tower", dh.device)
-            if ops.stream_wait(side, main):
-                with torch.cuda.stream(side):
-                    ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
-                    ctx.crit.table.sparse_grad = (plan, ge, gb)
-                    lazy.update()
-                for t in (ge, gb, dlogit, h, gl) + tuple(plan.tensors()):
-                    t.record_stream(side)
-                ops.pending_joins.append((main, side))
-                return denc, None, None, None, None, None, None, None, None, None
         ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
         ctx.crit.table.sparse_grad = (plan, ge, gb)
         return denc, None, None, None, None, None, None, None, None, None
 
 
-HEAD_SIDE = os.environ.get("MAPX_HEAD_SIDE", "1") == "1"     # 0.871 vs 0.900 ms per step
-DEFER_PLAN_JOIN = os.environ.get("MAPX_DEFER_PLAN_JOIN", "1") == "1"    # the dense-encoder head: see _NceLoss.backward
-TOTALS_LATER = os.environ.get("MAPX_TOTALS_LATER", "1") == "1"     # loss totals formed by the head's first backward launch
-LATE_TABLE = os.environ.get("MAPX_LATE_TABLE", "1") == "1"
-# _EncNceLoss.backward: the table's gradient on the plan stream behind its sort ("1"), at the end of the cross tower's
-# chain ("0"), or ("auto") by the cross tower's width: its chain is the longer one at Criteo's 624 columns, where taking
-# the gradient off it wins (1.0155 / 1.0085 -> 0.9868 / 0.9865 ms), and has slack at Avazu's 368, where the plan
-# stream's queue is the deep tower's (0.668 -> 0.690 / 0.694 with "1").
-TABLE_ON_PLAN = os.environ.get("MAPX_TABLE_ON_PLAN", "auto")
 TABLE_ON_PLAN_MIN_D = 512
 
 
 def _table_on_plan(join):
-    if TABLE_ON_PLAN == "auto":
-        return join is not None and join.D >= TABLE_ON_PLAN_MIN_D
-    return TABLE_ON_PLAN == "1"
+    """_EncNceLoss.backward: the table's gradient on the plan stream behind its sort (True) or at the end of the cross
+    tower's chain (False), by the cross tower's width: its chain is the longer one at Criteo's 624 columns, where taking
+    the gradient off it wins (1.0155 / 1.0085 -> 0.9868 / 0.9865 ms), and has slack at Avazu's 368, where the plan
+    stream's queue is the deep tower's (0.668 -> 0.690 / 0.694 on the plan stream)."""
+    return join is not None and join.D >= TABLE_ON_PLAN_MIN_D
+
+
 # "1": a training step reads the sampled table rows through their pending zero-gradient updates (no catch-up pass; the
 # gradient update is a row's one read-modify-write of the step; VERDICT r3 item 4a).  Built, bit-identical, and
 # measured slower on the step it was asked for (one box, tools/ab_env.sh): the loss kernel 19.5 -> 64 us (639 k row
@@ -168,10 +142,7 @@ class _EncNceLoss(Function):
         final = final.contiguous()
         dh_slots = torch.empty(groups.cap, P, dtype=torch.float32, device=final.device)
         h_slots = ops.enc_grouped_fwd(final, w_enc, b_enc, groups, zero_slots=dh_slots)
-        ready = getattr(idx, "_ready", None)
-        if ready is not None:           # sampled behind the cross tower (models.NCE_AFTER_CROSS): only this kernel waits
-            ops.stream_wait_event(torch.cuda.current_stream(), ready[0], ready[1])
-        later = TOTALS_LATER and ops.step_window[0] and ctx.needs_input_grad[0]      # (see _NceLoss.forward)
+        later = ops.step_window[0] and ctx.needs_input_grad[0]      # (see _NceLoss.forward)
         o = ops.nce_fwd(h_slots, masked_index, idx, emb_w, bias_w.view(-1), logq, F, P,
                         want_logits=want_logits, hpos=groups.hpos, dh_slots=dh_slots, totals_later=later,
                         lazy=getattr(idx, "_lazy", None))
@@ -208,10 +179,7 @@ class _EncNceLoss(Function):
             ctx.plan.start()         # sort of the sampled ids: forks from the draw, enqueued behind the dX GEMM
         if ctx.plan is None:
             raise RuntimeError("NCE backward without a segment plan")
-        lazy = ctx.crit.table.lazy
-        early = lazy is not None and getattr(lazy, "early_now", False)
-        # (with a gradient exchange or a clipping norm ahead the row update has to wait; the reduction need not)
-        aside = HEAD_SIDE and final.is_cuda and (early or ops.HEAD_SIDE_REDUCE_ONLY)
+        aside, table_done = final.is_cuda, False
         if aside and joined and _table_on_plan(ctx.join) and ctx.plan.value is not None and ops.step_window[0]:
             # The table's gradient on the PLAN stream, right behind the sort that it alone needs: no stream waits for the
             # plan at this point of the step (rounds 1-4 joined the plan into the main stream here — a tower <- plan join
@@ -225,35 +193,31 @@ class _EncNceLoss(Function):
                 with torch.cuda.stream(pst):
                     ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
                     ctx.crit.table.sparse_grad = (plan, ge, gb)
-                    if early:
-                        lazy.update()
                 for t in (ge, gb, dlogit, h, gl):
                     t.record_stream(pst)
                 ops.pending_joins.append((main, pst))
-                early = None
-        elif aside and joined and LATE_TABLE:
+                table_done = True
+        elif aside and joined:
             # with one product per tower the cross tower's chain starts at once on the tower stream; the table's
-            # gradient reduction and row update (HBM-bound, ~70 us) go BEHIND it (ops.run_late_tasks) instead of in
+            # gradient reduction (HBM-bound) goes BEHIND it (ops.run_late_tasks) instead of in
             # front of it, beside the deep tower's remaining MFMA-bound GEMMs
-            crit, K, P, do_update = ctx.crit, ctx.K, ctx.P, early
+            crit, K, P = ctx.crit, ctx.K, ctx.P
             plan = ctx.plan.get()        # (joined here, on the main stream: a tower <- plan join inside a capture
                                          # is the one that crashed hipStreamEndCapture in round 1)
 
             def table_work():
                 ge, gb = ops.nce_table_grad(plan, dlogit, h, K, P, gscale=gl)
                 crit.table.sparse_grad = (plan, ge, gb)
-                if do_update:
-                    lazy.update()
                 cur = torch.cuda.current_stream()
                 for t in (dlogit, h, gl) + tuple(plan.tensors()):
                     t.record_stream(cur)
             ops.add_late_task(table_work)
-            early = None
+            table_done = True
         elif aside:
-            # The table's gradient reduction and row update need nothing of this backward pass but the loss
-            # scale; the trunk's backward needs only dfinal.  They go to the tower stream (idle between the
+            # The table's gradient reduction needs nothing of this backward pass but the loss
+            # scale; the trunk's backward needs only dfinal.  It goes to the tower stream (idle between the
             # towers' forward and backward), forked behind the dX GEMM; the trunk's backward no longer waits
-            # for them on the main stream.  (The encoder's dW / db there as well, or on the plan stream: 0.888 /
+            # for it on the main stream.  (The encoder's dW / db there as well, or on the plan stream: 0.888 /
             # 0.883 vs 0.873 ms — the cross tower's backward queues behind whatever this stream holds.)
             plan = ctx.plan.get()
             main, side = torch.cuda.current_stream(), ops.aux_stream("tower", final.device)
@@ -261,12 +225,10 @@ class _EncNceLoss(Function):
                 with torch.cuda.stream(side):
                     ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
                     ctx.crit.table.sparse_grad = (plan, ge, gb)
-                    if early:
-                        lazy.update()
                 for t in (ge, gb, dlogit, h, gl) + tuple(plan.tensors()):
                     t.record_stream(side)
                 ops.pending_joins.append((main, side))
-                early = None
+                table_done = True
         if joined and sw is not None and sb is not None:
             # nothing but the optimizer waits for the encoder's own gradients, and both towers' backward passes
             # wait for this node to return: they go to the end of the cross tower's chain (ops.run_late_tasks)
@@ -278,26 +240,15 @@ class _EncNceLoss(Function):
                     t.record_stream(cur)
                 ops.enc_grouped_dw(dh_slots, final, groups, out=sw, gscale=gl)
                 ops.colsum(denc, out=sb, defer=True)
-            ops.add_late_task(encoder_grads, dense=True)
+            ops.add_late_task(encoder_grads)
             dw = db = None
         else:
             dw = ops.enc_grouped_dw(dh_slots, final, ctx.groups, out=sw, gscale=gl)
             db = ops.colsum(denc, out=sb, defer=True)      # second stage with the other deferred partial sums
-        if early is not None:
+        if not table_done:
             plan = ctx.plan.get()
             ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
             ctx.crit.table.sparse_grad = (plan, ge, gb)
-        if early:
-            # the table's row update (HBM-bound, 26 us at the end of the step) needs nothing else of
-            # this backward pass: queued as a side task, it runs at the start of the cross tower's
-            # backward chain, which has slack against the deep tower's (1.212 -> 1.201 ms).  The
-            # encoder's bias-gradient column sum queued the same way cost what this gains.
-            def update_rows():
-                cur = torch.cuda.current_stream()
-                for t in (ge, gb) + tuple(plan.tensors()):
-                    t.record_stream(cur)
-                lazy.update()
-            ops.add_side_task(update_rows)
         return (dfinal, None if sw is not None else dw, None if sb is not None else db,
                 None, None, None, None, None, None, None, None, None, None, None)
 
@@ -370,7 +321,7 @@ class IndexLinear(nn.Module):
     def supports_grouped_encoder(self):
         return self.proj_size == 32 and self.noise_ratio + 1 <= 32
 
-    def sample_ids(self, target, noise_samples=None, catch_up=True):
+    def sample_ids(self, target, noise_samples=None):
         """The step's sampled row ids [B*L, K+1] (target in column 0) and the lazy catch-up of the
         rows they name.  Depends on the targets only, not on the trunk: a model may call it early,
         on a stream that has slack (DCNV2 does, ahead of the cross tower), and hand the result to
@@ -385,9 +336,9 @@ class IndexLinear(nn.Module):
         # a training step's rows are read through their pending updates by the loss kernel and written once, by the
         # gradient update; without a gradient (eval) the catch-up pass brings them up to date
         lazy = self.table.lazy
-        fold = (LAZY_FOLD and need_grad and lazy is not None and lazy.replay_in_readers()
+        fold = (LAZY_FOLD and need_grad and lazy is not None
                 and ops.lazy_rows_supported(self.proj_size, idx.shape[1]))
-        self.table.prepare(idx.view(-1), need_grad, defer_plan=True, through_replay=fold, catch_up=catch_up)
+        self.table.prepare(idx.view(-1), need_grad, defer_plan=True, through_replay=fold)
         idx._lazy = lazy.lazy_rows() if fold else None
         return idx
 

@@ -100,13 +100,7 @@ def aux_stream(name, device, high=False):
     return st
 
 
-# Side tasks: HBM-bound work that is independent of the trunk's backward (e.g. the row update of a
-# table whose gradient is final) queued by one backward node and run by another at the START of a
-# side-stream chain that has slack (the cross tower's backward) — the same placement that works in
-# forward for the NCE sampling; whatever is still queued when the optimizer starts runs there.
-_side_tasks = []
 pending_joins = []                # (waiting stream, side stream) left open by a backward node; the optimizer joins
-HEAD_SIDE_REDUCE_ONLY = os.environ.get("MAPX_HEAD_SIDE_DP", "1") == "1"
 
 
 def join_pending():
@@ -124,25 +118,11 @@ unit_gradient = [None]
 # True between MapxOptimizer.backward_window(True) and (False): optimizer.step() follows this backward pass at
 # once and joins what it left open; outside the window backward() joins its side streams itself
 step_window = [False]
-# "1" (default): the optimizer's dense half forks from there onto the tower stream, beside the tables' half; "0":
-# everything on the main stream.  (With early row updates in the bf16 mode — its default until the end of round 4 — the
-# dense half queued up behind the NCE table's gradient and update on the tower stream while the main queue idled for
-# 72 us, and "0" was better there: 0.5454 / 0.5425 -> 0.5397 / 0.5397 ms; without early updates "1" wins in both modes:
-# optim.py.)  "auto" = "1".
-TAIL_OVERLAP = os.environ.get("MAPX_TAIL_OVERLAP", "1")
-
-
-def tail_overlap(bf16_trunk):
-    return TAIL_OVERLAP in ("1", "auto")
-
-
-def add_side_task(fn):
-    _side_tasks.append(fn)
 
 
 def run_side_tasks():
-    while _side_tasks:
-        _side_tasks.pop(0)()
+    """Nothing queues side tasks any more (they carried the tables' early row updates); the benchmark's
+    data-parallel rehearsal still calls this between backward and the exchange."""
 
 
 # Late tasks: work of a backward node that nothing but the optimizer waits for (the grouped encoder's weight and
@@ -151,34 +131,15 @@ def run_side_tasks():
 _late_tasks = []
 
 
-def add_late_task(fn, dense=False):
-    """dense: the task forms gradients of DENSE parameters (a head's or the encoder's dW / db) — those run first, and an
-    event behind them (late_dense_done) lets the optimizer's dense half start without waiting for the tables' work that
-    the other late tasks put on the same stream."""
-    _late_tasks.append((fn, bool(dense)))
-
-
-LATE_DENSE_FIRST = os.environ.get("MAPX_LATE_DENSE_FIRST", "0") == "1"      # A/B switch (with MAPX_DENSE_BEFORE_JOIN)
-late_dense_done = [None, None]        # [event, stream] behind the last dense-gradient late task of this backward pass
+def add_late_task(fn):
+    _late_tasks.append(fn)
 
 
 def run_late_tasks():
-    if not _late_tasks:
-        return
     tasks = list(_late_tasks)
     _late_tasks.clear()
-    if not LATE_DENSE_FIRST:
-        for fn, _ in tasks:
-            fn()
-        return
-    for fn, dense in tasks:
-        if dense:
-            fn()
-    if any(not dense for _, dense in tasks) and torch.cuda.is_available():
-        late_dense_done[0], late_dense_done[1] = record_event(), torch.cuda.current_stream()
-    for fn, dense in tasks:
-        if not dense:
-            fn()
+    for fn in tasks:
+        fn()
 
 
 # Main tasks: stream joins a backward node wants on the MAIN stream but not yet (the wait for a segment plan that the
@@ -198,7 +159,6 @@ def run_main_tasks():
 
 def clear_side_tasks():
     """Drop tasks that an aborted backward pass left behind."""
-    _side_tasks.clear()
     _late_tasks.clear()
     _main_tasks.clear()
 
@@ -225,7 +185,6 @@ def reset_aux_streams():
     pending_joins.clear()
     step_window[0] = False
     _deferred.clear()
-    _side_tasks.clear()
     _late_tasks.clear()
     _main_tasks.clear()
     dense_ready[0] = dense_ready[1] = None
@@ -292,21 +251,9 @@ _deferred = []
 COLSUM_CHUNKS = lib.mapx_colsum_chunks()
 
 
-# measured on MI355X inside the full step: deferring is 2-3 % SLOWER (1.56 vs 1.52 ms) — by then the
-# slabs have left L2 and one launch has few blocks — so it is off by default.  Sending each layer's
-# sums to a side stream instead was far worse (1.78 vs 1.45 ms): inside the captured graph every
-# extra parallel branch of tiny kernels disturbs the queue assignment of the GEMM chains.
-# Letting the dense optimizer kernel sum the slabs while it reads the gradient (no extra launch
-# at all) was also slower (1.49 vs 1.42 ms): the slabs are cold by then, whereas a reduce right
-# behind the GEMM finds them in L2 / Infinity Cache.
-DEFER = os.environ.get("MAPX_DEFER", "0") == "1"
-# the bias gradients' row-chunk partials alone (7 tiny second-stage launches per step on the GEMM chains,
-# 128 x N floats each: nothing to go cold)
-# measured: 0.943 / 0.950 vs 0.952 / 0.954 ms per step, same box: on by default
-DEFER_COLSUM = DEFER or os.environ.get("MAPX_DEFER_COLSUM", "1") == "1"
-# the same for the bf16 mode's column-sum kernels (round 3: each bias gradient had a second-stage launch of its own,
-# 7-10 us apiece on the backward chains of a 0.5-ms step)
-DEFER_COLSUM_H = os.environ.get("MAPX_DEFER_COLSUM_H", "1") == "1"
+# What is deferred: the bias gradients' row-chunk partials and the streaming kernels' dW partials (tiny second-stage
+# launches on the GEMM chains otherwise, 128 x N floats each: nothing to go cold).  The MFMA GEMMs' split-K slabs are
+# NOT: they are summed right behind the GEMM, where they are still in L2 / Infinity Cache (DESIGN: "Retired switches").
 
 
 def defer_sum(dst, src, stride, nsplit, n):
@@ -1147,8 +1094,6 @@ def weight_planes(w, b_kc, M):
     rec = amax_of(base)
     if reg is None or rec is None:
         return None
-    if _dirty_planes:
-        refresh_dirty_planes()            # (nobody re-cut them at the start of this step: do it before the first reader)
     Nn, K = (w.shape[0], w.shape[1]) if b_kc else (w.shape[1], w.shape[0])
     if not planes_wanted(M, Nn, K):
         return None
@@ -1159,32 +1104,6 @@ def weight_planes(w, b_kc, M):
             return None               # (registered by the eager steps that precede a capture)
         pl = reg[key] = h2_weight_planes(base.detach()[:, c0:c1] if (c0, c1) != (0, None) else base.detach(), b_kc, rec)
     return pl
-
-
-# Where the planes are re-cut: right behind the AdamW kernel (end of the step, "0"), or at the START of the next step
-# ("1"): the optimizer only notes which parameters it wrote; the model's forward re-cuts them on a stream that is idle
-# while the step's head (mask, catch-up, gather) runs, and any product that asks for planes before that re-cuts on the
-# spot — a stale plane is never read.
-PLANES_AT_START = os.environ.get("MAPX_PLANES_AT_START", "0") == "1"
-_dirty_planes = []
-
-
-def planes_written(params):
-    """The optimizer wrote these parameters (their records are current): re-cut their planes now or note them."""
-    if PLANES_AT_START:
-        _dirty_planes.append(list(params))
-    else:
-        refresh_weight_planes(params)
-
-
-def refresh_dirty_planes():
-    """Re-cut the planes of every parameter noted by planes_written, on the current stream.  -> True if any."""
-    if not _dirty_planes:
-        return False
-    todo = [p for ps in _dirty_planes for p in ps]
-    del _dirty_planes[:]
-    refresh_weight_planes(todo)
-    return True
 
 
 def refresh_weight_planes(params):
@@ -1225,7 +1144,7 @@ def _scale_arg(amax_a, amax_b, amax_c=None, amax_c2=None, b_planes=None):
 
 
 def gemm(a, b, a_kc, b_kc, M, N, K, out=None, ldc=None, epi=N.EPI_NONE, bias=None, aux1=None,
-         aux2=None, out2=None, nsplit=1, lda=None, ldb=None, tile=-1, defer=False, out_dtype=None,
+         aux2=None, out2=None, nsplit=1, lda=None, ldb=None, tile=-1, out_dtype=None,
          amax_a=None, amax_b=None, amax_c=None, record=True, b_planes=None):
     """C[M,N] = epi(sum_k A(m,k) B(k,n)); see include/mapx_hip.h: mapx_gemm_f32 (fp32 operands) /
     mapx_gemm_bf16 (bf16 operands; `out_dtype` picks a bf16 or fp32 result).  amax_a / amax_b: the operands'
@@ -1242,11 +1161,8 @@ def gemm(a, b, a_kc, b_kc, M, N, K, out=None, ldc=None, epi=N.EPI_NONE, bias=Non
     ldb = ldb if ldb is not None else b.stride(0)
     ws, wsn = None, 0
     if nsplit > 1:
-        wsn = lib.mapx_gemm_splitk_workspace_bytes(M, N, nsplit)
-        # deferred slabs must outlive this call: their own buffer, not the shared scratch
-        ws = torch.empty(wsn, dtype=torch.uint8, device=dev) if defer else scratch(wsn, dev)
+        ws = scratch(lib.mapx_gemm_splitk_workspace_bytes(M, N, nsplit), dev)
         wsn = ws.numel()
-    got = native_int() if (defer and nsplit > 1) else None
     ld1 = aux1.stride(0) if aux1 is not None else 0
     ld2 = aux2.stride(0) if aux2 is not None else 0
     ldo2 = out2.stride(0) if out2 is not None else 0
@@ -1273,11 +1189,8 @@ def gemm(a, b, a_kc, b_kc, M, N, K, out=None, ldc=None, epi=N.EPI_NONE, bias=Non
                                 aux1.data_ptr() if aux1 is not None else None, ld1,
                                 aux2.data_ptr() if aux2 is not None else None, ld2,
                                 out2.data_ptr() if out2 is not None else None, ldo2, nsplit, tile,
-                                ws.data_ptr() if ws is not None else None, wsn,
-                                None if got is None else native_byref(got),
+                                ws.data_ptr() if ws is not None else None, wsn, None,
                                 None if sc is None else native_byref(sc), stream()))
-    if got is not None and got.value > 1:
-        defer_sum(out, ws.view(torch.float32), M * N, got.value, M * N)
     return tag(out, amax_c)
 
 
@@ -1305,7 +1218,7 @@ def _skinny_h(Nn, K, *mats):
     return SKINNY and SKINNY_BF16 and 1 <= Nn <= 8 and K >= 4 and K % 4 == 0 and all(_rows8h(m) for m in mats)
 
 
-_TALL_ROWS = int(os.environ.get("MAPX_TALL_ROWS", "128"))
+_TALL_ROWS = 128
 SKINNY_MAX = int(os.environ.get("MAPX_SKINNY_MAX", "8"))            # forward: wider layers measured faster on the GEMM
 # dW / dX (RFD's 23-wide layer: 14.6 / 8.6 vs 28 / 12 us).  The kernels take up to 64 outputs (Criteo's 39-wide layer:
 # dW 45 -> 26 us, its RFD step -2.3 %): opt-in.  (With 33..64 on, the captured step of the 64-wide test models stopped
@@ -1353,9 +1266,8 @@ RELU_LINK = os.environ.get("MAPX_RELU_LINK", "1") == "1"
 
 
 def fused_mask_colsum_ok(dy, relu_of):
-    """Can linear_bwd_input also apply the upstream ReLU's mask and form its bias gradient?  (16-byte rows,
-    deferred partial sums on.)"""
-    if not (RELU_LINK and DEFER_COLSUM and relu_of.dim() == 2 and dy.dtype == relu_of.dtype):
+    """Can linear_bwd_input also apply the upstream ReLU's mask and form its bias gradient?  (16-byte rows.)"""
+    if not (RELU_LINK and relu_of.dim() == 2 and dy.dtype == relu_of.dtype):
         return False
     if is_bf16(dy):
         return relu_of.shape[1] % 8 == 0 and relu_of.stride(1) == 1 and relu_of.stride(0) % 8 == 0 \
@@ -1418,7 +1330,8 @@ def _splits_wide_tiles(M, Nn, Kred):
 
 
 def linear_bwd_weight(dy, x, out=None, defer=False):
-    """dW = dY^T X.  dy [B,N], x [B,K] -> [N,K].  defer: leave split-K slabs for flush_deferred()."""
+    """dW = dY^T X.  dy [B,N], x [B,K] -> [N,K].  defer (needs out): the streaming kernels leave their row-chunk
+    partials for flush_deferred(); the MFMA GEMMs sum their split-K slabs at once."""
     Bn, Nn = dy.shape
     K = x.shape[1]
     # (also: both dimensions small over many rows — AutoInt's attention projections, dW [40, 16 | 40] over B*F rows.
@@ -1442,7 +1355,7 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
         with _timed("skinny_linear", 4.0 * (Bn * K + Bn * Nn + chunks * Nn * K)):
             check(lib.mapx_skinny_linear_dw(ptr(dy), dy.stride(0), ptr(x), x.stride(0), Bn, Nn, K, ptr(part), chunks,
                                             stream()))
-        if DEFER_COLSUM and defer and out is not None:
+        if defer and out is not None:
             defer_sum(dw, part, Nn * K, chunks, Nn * K)          # with the step's other partial sums
         else:
             _sum_now(dw, part, Nn * K, chunks, Nn * K)
@@ -1458,7 +1371,7 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
         with _timed("skinny_linear", 2.0 * (Bn * K + Bn * Nn) + 4.0 * chunks * Nn * K):
             check(lib.mapx_skinny_linear_dw_bf16(ptr(dy), dy.stride(0), ptr(x), x.stride(0), Bn, Nn, K, ptr(part), chunks,
                                                  stream()))
-        if DEFER_COLSUM and defer and out is not None:
+        if defer and out is not None:
             defer_sum(dw, part, Nn * K, chunks, Nn * K)
         else:
             _sum_now(dw, part, Nn * K, chunks, Nn * K)
@@ -1469,8 +1382,7 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
         ns = 1
     if is_bf16(dy):                          # fp32 gradient from bf16 operands
         return gemm_bf16(dy, x, False, False, Nn, K, Bn, out=out, out_dtype=torch.float32, nsplit=ns)
-    return gemm(dy, x, False, False, Nn, K, Bn, out=out, nsplit=ns, defer=DEFER and defer and out is not None,
-                record=False)
+    return gemm(dy, x, False, False, Nn, K, Bn, out=out, nsplit=ns, record=False)
 
 
 def _partials_h(Nn, device, defer):
@@ -1491,7 +1403,7 @@ def colsum(x, out=None, defer=False):
     require_gpu(x)
     M, Nn = x.shape
     if is_bf16(x):
-        later = DEFER_COLSUM and DEFER_COLSUM_H and defer and out is not None
+        later = defer and out is not None
         if out is None:
             out = torch.empty(Nn, dtype=torch.float32, device=x.device)
         if x.stride(1) != 1:
@@ -1502,7 +1414,7 @@ def colsum(x, out=None, defer=False):
         if later:
             defer_sum(out, ws.view(torch.float32), Nn, chunks, Nn)
         return out
-    defer = DEFER_COLSUM and defer and out is not None
+    defer = defer and out is not None
     if out is None:
         out = torch.empty(Nn, dtype=torch.float32, device=x.device)
     ws = _partials(Nn, x.device, defer)
@@ -1557,7 +1469,7 @@ def relu_mask_colsum(dy, y, db=None, defer=False):
             y = y.contiguous()
         M, Nn = dy.shape
         dz = torch.empty(M, Nn, dtype=BF16, device=dy.device)
-        later = DEFER_COLSUM and DEFER_COLSUM_H and defer and db is not None
+        later = defer and db is not None
         if db is None:
             db = torch.empty(Nn, dtype=torch.float32, device=dy.device)
         ws, chunks = _partials_h(Nn, dy.device, later)
@@ -1572,7 +1484,7 @@ def relu_mask_colsum(dy, y, db=None, defer=False):
         y = y.contiguous()
     M, Nn = dy.shape
     dz = torch.empty(M, Nn, dtype=torch.float32, device=dy.device)
-    defer = DEFER_COLSUM and defer and db is not None
+    defer = defer and db is not None
     if db is None:
         db = torch.empty(Nn, dtype=torch.float32, device=dy.device)
     ws = _partials(Nn, dy.device, defer)
@@ -1595,7 +1507,7 @@ def cross_bwd_pre_colsum(g, x0, u, dx0=None, db=None, defer=False, plus_g=False)
         acc = dx0 is not None
         if dx0 is None:
             dx0 = torch.empty(M, Nn, dtype=torch.float32, device=g.device)
-        later = DEFER_COLSUM and DEFER_COLSUM_H and defer and db is not None
+        later = defer and db is not None
         if db is None:
             db = torch.empty(Nn, dtype=torch.float32, device=g.device)
         ws, chunks = _partials_h(Nn, g.device, later)
@@ -1612,7 +1524,7 @@ def cross_bwd_pre_colsum(g, x0, u, dx0=None, db=None, defer=False, plus_g=False)
     acc = dx0 is not None
     if dx0 is None:
         dx0 = torch.empty(M, Nn, dtype=torch.float32, device=g.device)
-    defer = DEFER_COLSUM and defer and db is not None
+    defer = defer and db is not None
     if db is None:
         db = torch.empty(Nn, dtype=torch.float32, device=g.device)
     ws = _partials(Nn, g.device, defer)
@@ -1904,7 +1816,6 @@ def make_sched(lr0, lambdas, beta1, beta2):
 
 
 REPLAY_TERMS = 7          # kJ + 1 in csrc/optim.hip
-CLOSED_REPLAY = os.environ.get("MAPX_CLOSED_REPLAY", "1") == "1"     # 0: step-by-step replay + closed-form tail
 
 
 def make_replay_aux(lr0, lambdas, beta1, beta2, wd):
@@ -1912,7 +1823,7 @@ def make_replay_aux(lr0, lambdas, beta1, beta2, wd):
     (csrc/optim.hip: replay_coef): prefix products prod_{i<s}(1 - lr_i*wd), beta1^n, beta2^n, and
     R_i[s] = a_s + q_i / (1 - d_s) * R_i[s+1] for q_i = beta1 * beta2^(-(i+1)/2), i = 0..6, once with
     d_s = lr_s*wd and once with d_s = 0.  a_s and lr_s are the fp32-rounded values the kernels read
-    from the schedule table.  MAPX_CLOSED_REPLAY=0: the first three rows only."""
+    from the schedule table."""
     T = len(lambdas)
     sched = make_sched(lr0, lambdas, beta1, beta2).to(torch.float64)        # fp32 values, as doubles
     a, lr = sched[:, 0].tolist(), sched[:, 1].tolist()
@@ -1922,17 +1833,16 @@ def make_replay_aux(lr0, lambdas, beta1, beta2, wd):
     n = torch.arange(T + 1, dtype=torch.float64)
     rows = [cum, torch.pow(torch.tensor(beta1, dtype=torch.float64), n),
             torch.pow(torch.tensor(beta2, dtype=torch.float64), n)]
-    if CLOSED_REPLAY:
-        beta = math.sqrt(beta2)
-        cum_l = cum.tolist()
-        for decay in (True, False):
-            for i in range(REPLAY_TERMS):
-                q = (beta1 / beta) * beta ** (-i)
-                R = [0.0] * (T + 1)
-                for s in range(T - 1, -1, -1):
-                    keep = (cum_l[s + 1] / cum_l[s]) if decay else 1.0     # 1 - d_s, consistent with row 0
-                    R[s] = a[s] + q / keep * R[s + 1]
-                rows.append(torch.tensor(R, dtype=torch.float64))
+    beta = math.sqrt(beta2)
+    cum_l = cum.tolist()
+    for decay in (True, False):
+        for i in range(REPLAY_TERMS):
+            q = (beta1 / beta) * beta ** (-i)
+            R = [0.0] * (T + 1)
+            for s in range(T - 1, -1, -1):
+                keep = (cum_l[s + 1] / cum_l[s]) if decay else 1.0     # 1 - d_s, consistent with row 0
+                R[s] = a[s] + q / keep * R[s + 1]
+            rows.append(torch.tensor(R, dtype=torch.float64))
     return torch.stack(rows).contiguous()
 
 

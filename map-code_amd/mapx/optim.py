@@ -9,15 +9,12 @@ reference's Trainer.get_optimizer builds it (code/trainer.py:60-85), on device.
   int, so nothing is synchronised with the host during training.
 """
 import math
-import os
 
 import torch
 
 from . import ops
 
 NO_DECAY = ("bias", "LayerNorm.weight")          # trainer.py:61
-DENSE_BEFORE_JOIN = os.environ.get("MAPX_DENSE_BEFORE_JOIN", "0") == "1"     # A/B switch: MapxOptimizer.step
-PACK_MOMENTS = os.environ.get("MAPX_PACK_MOMENTS", "1") == "1"      # A/B switch: m | v of a table row in one record
 
 
 def decays(name):
@@ -49,17 +46,12 @@ class TableAdam:
         # places per row (the parameter row and this record) instead of three — random rows cost per access, not
         # per byte (csrc/optim.hip TableGroup).  m0 / v0 (m1 / v1) are views of the halves.
         W = p0.shape[1]
-        self.mv0 = torch.zeros(p0.shape[0], 2 * W, dtype=p0.dtype, device=p0.device) if PACK_MOMENTS else None
-        if PACK_MOMENTS:
-            self.m0, self.v0 = self.mv0[:, :W], self.mv0[:, W:]
-        else:
-            self.m0, self.v0 = torch.zeros_like(p0), torch.zeros_like(p0)
+        self.mv0 = torch.zeros(p0.shape[0], 2 * W, dtype=p0.dtype, device=p0.device)
+        self.m0, self.v0 = self.mv0[:, :W], self.mv0[:, W:]
         self.m1 = self.v1 = self.mv1 = None
-        if p1 is not None and PACK_MOMENTS:
+        if p1 is not None:
             self.mv1 = torch.zeros(p1.shape[0], 2, device=p1.device)
             self.m1, self.v1 = self.mv1[:, 0], self.mv1[:, 1]
-        elif p1 is not None:
-            self.m1, self.v1 = torch.zeros(p1.shape[0], device=p1.device), torch.zeros(p1.shape[0], device=p1.device)
         self.last = torch.zeros(p0.shape[0], dtype=torch.int32, device=p0.device)
         self.stale = False
         self.cursor = 0
@@ -77,10 +69,6 @@ class TableAdam:
 
     def catch_up(self, plan):
         self._call(rows=plan.uniq, n_rows=plan.n, n_rows_dev=plan.n_uniq)
-
-    def replay_in_readers(self):
-        """The closed form is tabulated (17-row aux): a forward kernel may read rows through their pending updates."""
-        return self.aux.shape[0] > 3
 
     def refresh_coef(self):
         """This step's replay coefficients (ops.replay_coef_table) for the kernels that take lazy_rows()."""
@@ -168,35 +156,18 @@ class MapxOptimizer:
             wd0 = self.wd if decays(names[id(t.p0)]) else 0.0
             wd1 = (self.wd if decays(names[id(t.p1)]) else 0.0) if t.p1 is not None else 0.0
             self.tables.append(TableAdam(t, wd0, wd1, self.hyper, self.sched, self.done, self.aux, max_gap))
-        # a table may apply its update as soon as its gradient is final (ops.add_side_task) unless the
-        # step needs all gradients first: a global clipping norm, or the gradient exchange of N ranks
-        from . import parallel
-        # Round 3 (tools/flag_sweep.py, one box each): in fp32, with the table gradients on the tower stream's late
-        # tasks, the early row updates LOSE (0.8058 vs 0.7975 ms per step: the updates run in step(), beside the
-        # optimizer's dense half); in the bf16 mode, whose GEMM chains are half as long, they WIN (0.5931 vs 0.6318).
-        # Round 4, two sweeps: with gemm_h2.hip alone early won in fp32 too (0.7075 vs 0.7175), with the weights' planes
-        # (gemm_h2w.hip, the shipped default) it loses again (0.7315 vs 0.7120).  End of round 4 (the deep tower's join
-        # product captured first, layers.JOIN_DEEP_FIRST): they lose in the bf16 mode as well — MFP 0.5372 / 0.5417 with
-        # them (and the dense half on the main stream) vs 0.5305 / 0.5327 without (dense half beside the tables' on the
-        # tower stream, as in fp32), RFD 0.448 / 0.441 vs 0.428 / 0.426, Criteo-shaped equal (profiles/r04_ab_tail.txt).
-        early_default = "0"
-        early = (os.environ.get("MAPX_EARLY_TABLE_UPDATE", early_default) == "1" and self.max_grad_norm <= 0
-                 and not parallel.exchanging())
-        for t in self.tables:
-            t.early_ok, t.early_now = early, False
         # (int64 device cursor, stride) of a captured step that walks the epoch's permutation: moved to the next
         # batch by the launch that advances the update counter (trainer.GraphedStep sets it around its capture)
         self.walk_cursor = None
 
     def backward_window(self, open_):
         """Between backward_window(True) and (False) — the Trainer brackets loss.backward() of a step
-        whose optimizer.step() follows at once — a table may apply its row update as soon as its
-        gradient is final.  Outside the window backward() never touches a parameter."""
+        whose optimizer.step() follows at once — backward nodes may leave side streams open and queue work for
+        optimizer.step() to pick up (ops.pending_joins, late and main tasks).  Outside the window backward() joins
+        what it forked itself."""
         if open_:
             ops.clear_side_tasks()      # leftovers of a backward pass that raised
         ops.step_window[0] = bool(open_)
-        for t in self.tables:
-            t.early_now = bool(open_) and t.early_ok
 
     FLAT_PAD = 8          # elements every parameter's slot of a flat buffer is rounded up to (saved with the state)
 
@@ -285,25 +256,8 @@ class MapxOptimizer:
         ops.run_main_tasks()            # stream joins nobody picked up
         main = torch.cuda.current_stream() if torch.cuda.is_available() else None
         ev, ev_stream = ops.dense_ready
-        late_ev, late_stream = ops.late_dense_done
-        ops.late_dense_done[0] = ops.late_dense_done[1] = None
         from . import parallel
-        # The dense half first, when it runs on this stream (no fork: the bf16 trunk, ops.tail_overlap) and the side
-        # stream's dense gradients are marked by an event: it then waits for THAT event, not for the tables' gradient
-        # and row update that follow on the side stream (28 us of idle main queue in front of sum_tasks on
-        # profiles/r04_step_timeline_bf16.txt); everything else is joined behind it.
-        dense_first = (DENSE_BEFORE_JOIN and ev is None and late_ev is not None and main is not None
-                       and self.max_grad_norm <= 0 and not parallel.exchanging() and not ops._side_tasks
-                       and not ops._late_tasks)
-        if dense_first:
-            ops.stream_wait_event(main, late_ev, late_stream)
-            if self.collect_torch_grads() == 0:
-                ops.flush_deferred()
-                self._dense_update()
-            else:
-                dense_first = False        # (a torch-op gradient arrived in .grad: the plain order below)
         ops.join_pending()              # side work a backward node forked and left open
-        ops.run_side_tasks()            # early table updates nobody picked up
         ops.run_late_tasks()            # optimizer-only gradients nobody picked up
         moved = self.collect_torch_grads()
         ops.dense_ready[0] = ops.dense_ready[1] = None
@@ -323,9 +277,6 @@ class MapxOptimizer:
                 t.update()
             if forked:
                 ops.stream_wait(main, side)
-        elif dense_first:
-            for t in self.tables:
-                t.update()
         else:
             ops.flush_deferred()            # split-K slabs / colsum partials of this backward pass
             if self.max_grad_norm > 0:
@@ -346,7 +297,7 @@ class MapxOptimizer:
                             shadow=g["h"], seg_off=g.get("seg_off"), seg_amax=g.get("amax"))
         for g in self.groups:
             if g.get("amax") is not None:
-                ops.planes_written(g["params"])              # the weights' fp16 pieces for the next step's products
+                ops.refresh_weight_planes(g["params"])       # the weights' fp16 pieces for the next step's products
 
     def zero_grad(self):
         """Dense gradients are overwritten by the next backward (see layers._grad_slot); only

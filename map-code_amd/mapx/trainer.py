@@ -154,8 +154,7 @@ class GraphedStep:
         # Batches that are rows of the resident split in an epoch's permutation (RowsRef with `order`): the
         # graph owns a copy of the permutation and a device-side cursor that it advances itself, so a replay
         # is preceded by no copy at all (before: two 5-us copies + launch gaps in front of every step).
-        self.walk = (isinstance(X, RowsRef) and X.order is not None and X.stride > 0 and Y is X
-                     and os.environ.get("MAPX_WALK", "1") == "1")
+        self.walk = isinstance(X, RowsRef) and X.order is not None and X.stride > 0 and Y is X
         if self.walk:
             self.order = X.order.clone()
             self.cursor = torch.full((1,), X.start, dtype=torch.int64, device=X.device)
@@ -262,7 +261,6 @@ class GraphedBackward:
                 # NCE table's gradient): run HERE, inside the graph — left to optimizer.step() they would run once,
                 # eagerly, and every replay would miss that gradient
                 ops.run_main_tasks()
-                ops.run_side_tasks()
                 ops.run_late_tasks()
                 # deferred partial sums (bias gradients) belong to this graph: the list that names them
                 # exists only while the capture runs, a replay would leave them unsummed for the tail
@@ -368,10 +366,6 @@ class GraphedBackward:
         return self.out
 
 
-PACK_FIRST = os.environ.get("MAPX_DP_PACK_FIRST", "1") == "1"      # A/B switch (GraphedExchangeTail)
-MERGE_SIDE = os.environ.get("MAPX_DP_MERGE_SIDE", "1") == "1"      # A/B switch: one branch per table's merge
-
-
 class GraphedExchangeTail:
     """Everything between the last backward kernel and the next step, for ONE tuple of exchange
     message sizes: graph 1 packs every table's (id, row) message; the all-gathers run eagerly as
@@ -398,7 +392,7 @@ class GraphedExchangeTail:
                 # dense AdamW as a third branch was measured slower)
                 main = torch.cuda.current_stream()
                 order = sorted(range(len(tables)), key=lambda i: -sizes[i])
-                side = [ops.aux_stream(f"merge{j}", main.device) for j in range(len(order) - 1)] if MERGE_SIDE else []
+                side = [ops.aux_stream(f"merge{j}", main.device) for j in range(len(order) - 1)]
                 for st in side:
                     ops.stream_wait(st, main)
                 for j, i in enumerate(order):
@@ -414,15 +408,12 @@ class GraphedExchangeTail:
 
     def __call__(self, host_s):
         opt = self.trainer.optimizer
-        if PACK_FIRST:
-            # the messages are packed BEFORE the dense all-reduce is issued: the two collectives then follow each other
-            # on the communicator's stream without a hop to the main stream and back between them
-            self.pack.replay()
+        # the messages are packed BEFORE the dense all-reduce is issued: the two collectives then follow each other
+        # on the communicator's stream without a hop to the main stream and back between them
+        self.pack.replay()
         t0 = time.perf_counter()
         parallel.sync_dense(opt)
         host_s[3] += time.perf_counter() - t0
-        if not PACK_FIRST:
-            self.pack.replay()
         parallel.all_gather_tables(self.msgs, self.gathered)
         self.merge.replay()
         opt.steps_done += 1

@@ -1,6 +1,6 @@
 """GPU time of tall weight gradients with both dimensions small (AutoInt's attention projections: dW [40, 16 | 40] over
 B*F = 94 208 rows): the streaming kernel (csrc/skinny.hip, skinny_dw_tall_kernel) against the one-tile split-K GEMM.
-    python tools/micro/tall_bench.py        (MAPX_TALL_ROWS=<rows per chunk> sweeps the chunking)"""
+    python tools/micro/tall_bench.py"""
 import os
 import sys
 
