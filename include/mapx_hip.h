@@ -31,7 +31,7 @@ typedef struct ihipStream_t* hipStream_t; /* opaque outside hipcc */
 #include <hip/hip_runtime_api.h>
 #endif
 
-#define MAPX_ABI_VERSION 47
+#define MAPX_ABI_VERSION 48
 
 #define MAPX_OK 0
 #define MAPX_EINVAL (-1)     /* bad argument (shape, null pointer, alignment) */
@@ -660,6 +660,20 @@ int mapx_vocab_assign(const int32_t* by_first, const int32_t* by_count, const in
 int mapx_vocab_map(const int32_t* slot_of_row, const int32_t* slot_entry, const int32_t* rank_of_entry,
                    const int32_t* n_kept, int64_t n, int64_t base, int64_t* ids_out, int64_t ld_out,
                    hipStream_t stream);
+
+/* ------------------------------------------------------------------ state fingerprint (replica-consistency check)
+ * No reference site: the reference trains unsynchronised replicas and never compares them.  An
+ * order-independent 64-bit integer fingerprint of n_words raw 32-bit words (bit patterns: -0.0 != +0.0, NaN payloads
+ * count); unsigned 64-bit arithmetic that wraps, G = 0x9E3779B97F4A7C15:
+ *   mix(x):  x += G;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;  x ^ x >> 31
+ *   chunks[k] = sum_j mix(j << 32 | w[k * 65536 + j])   (j inside the chunk; the last chunk may be short)
+ *   *total    = sum_k mix(chunks[k] + (k + 1) * G)      (0 for n_words == 0)
+ * Exact for any grid (both sums commute; no atomics, no floating point).  data needs 4-byte alignment only. */
+int mapx_fingerprint_words(const void* data, int64_t n_words,
+                           uint64_t* chunks /* [ceil(n/65536)], device scratch, may be NULL only when n_words == 0 */,
+                           uint64_t* total  /* [1], device */,
+                           int blocks       /* 0 = auto; otherwise the first launch's grid size */,
+                           hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmapx_hip.so")
 
-MAPX_ABI_VERSION = 47
+MAPX_ABI_VERSION = 48
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_CROSS, EPI_ADD, EPI_RELU_MASK, EPI_RELU_MASK_COLSUM = range(7)
 
 _p, _i, _i64, _u64, _f, _d, _sz = (C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double,
@@ -130,6 +130,7 @@ SIGNATURES = {
     "mapx_replay_coef_table": (_i, [_p, _i, _i, _d, _d, _p, _p, _p]),
     "mapx_table_adam": (_i, [_p, _p, _p, _i64, _i, _f, _p, _p, _p, _i64, _f, _p, _p, _i64, _i64, _p, _p, _p, _p,
                              _i, _p, _p, _i, _i, _d, _d, _d, _i, _p]),
+    "mapx_fingerprint_words": (_i, [_p, _i64, _p, _p, _i, _p]),
 }
 
 

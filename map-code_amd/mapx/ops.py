@@ -1935,3 +1935,40 @@ def table_adam(p0, m0, v0, wd0, last, sched, done, aux, beta1, beta2, eps, p1=No
                                   ptr(last), ptr(rows), row_begin, n_rows, ptr(n_rows_dev), ptr(grad0),
                                   ptr(grad1), ptr(sched), sched.shape[0], ptr(done), ptr(aux),
                                   aux.shape[1], aux.shape[0], beta1, beta2, eps, int(rows_may_repeat), stream()))
+
+
+# ----------------------------------------------------------------------------- state fingerprint
+FP_CHUNK = 65536            # words per chunk value (include/mapx_hip.h: mapx_fingerprint_words)
+
+
+def fingerprint_into(t, total, chunks=None, blocks=0):
+    """Enqueue the fingerprint of `t` (a contiguous device tensor of a 4-byte dtype) into `total` (one element of an
+    int64 device tensor); `chunks`: int64 scratch of at least ceil(numel / FP_CHUNK) elements, allocated when None.
+    Nothing is synchronised: the caller reads `total` / `chunks` when it wants them.  -> the chunk values."""
+    if not isinstance(t, torch.Tensor) or t.element_size() != 4 or t.is_complex():
+        raise TypeError(f"fingerprint: a tensor of a 4-byte dtype, not {getattr(t, 'dtype', type(t))} "
+                        "(view or cast it explicitly)")
+    require_gpu(t, total)
+    if not t.is_contiguous():
+        raise ValueError("fingerprint: the tensor must be contiguous (nothing is copied silently)")
+    n = t.numel()
+    nchunks = (n + FP_CHUNK - 1) // FP_CHUNK
+    if chunks is None:
+        chunks = torch.empty(nchunks, dtype=torch.int64, device=t.device)
+    if total.dtype != torch.int64 or total.numel() != 1 or chunks.dtype != torch.int64 or chunks.numel() < nchunks \
+            or not chunks.is_contiguous():
+        raise ValueError("fingerprint: `total` is one int64 element, `chunks` contiguous int64 of ceil(n / 65536)")
+    with _timed("fingerprint", 4.0 * n):
+        check(lib.mapx_fingerprint_words(t.data_ptr() if n else None, n, chunks.data_ptr() if nchunks else None,
+                                         total.data_ptr(), int(blocks), stream()))
+    return chunks[:nchunks]
+
+
+def fingerprint(t, chunks=False, blocks=0):
+    """Order-independent 64-bit fingerprint of the raw bit patterns of a contiguous device tensor of a 4-byte dtype
+    -> Python int in [0, 2^64) (one host sync); chunks=True: also the int64 tensor of the per-chunk values (chunk k
+    covers elements [k * FP_CHUNK, (k + 1) * FP_CHUNK)).  blocks: grid size of the chunk launch (0 = auto)."""
+    total = torch.empty(1, dtype=torch.int64, device=t.device if isinstance(t, torch.Tensor) else None)
+    c = fingerprint_into(t, total, None, blocks)
+    f = int(total.item()) & 0xFFFFFFFFFFFFFFFF
+    return (f, c) if chunks else f

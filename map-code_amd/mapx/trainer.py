@@ -21,7 +21,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import ops, parallel
+from . import ops, parallel, replica
 from .optim import MapxOptimizer
 
 logger = logging.getLogger(__name__)
@@ -491,6 +491,13 @@ class Trainer:
         self.optimizer.step()                                # + scheduler.step() + zero_grad()
         self.global_step += 1
 
+    def _check_replicas(self, where):
+        """Every rank holds the same training state, or every rank raises replica.ReplicaDivergence (world > 1 and
+        MAPX_REPLICA_CHECK != 0).  Called where the state is flushed on every rank anyway and before
+        anything only rank 0 does; it reads the state as it is and never flushes."""
+        if self.optimizer is not None and self.world > 1 and replica.enabled():
+            replica.check_replicas(self.model, self.optimizer, f"{where}, step {self.global_step}")
+
     @contextlib.contextmanager
     def _step_window(self):
         """Brackets forward + loss.backward() of a step whose gradient exchange / optimizer.step() follows at once
@@ -679,9 +686,11 @@ class Trainer:
                     win_loss.zero_(); win_acc.zero_()
                     start_time = time.time()
             self.optimizer.flush()      # on EVERY rank: replicas must replay their lazy rows at the same steps
+            self._check_replicas(f"MFP_pretrain epoch {epoch}")
             if self.args.local_rank in [-1, 0]:
                 self.MFP_pretrain_eval()
         self.optimizer.flush()
+        self._check_replicas("MFP_pretrain end")
         if self.args.local_rank in [-1, 0]:
             self.save_model(self.args.output_dir)
         logger.info(str(self.eval_metrics))
@@ -733,9 +742,11 @@ class Trainer:
                     win.zero_()
                     start_time = time.time()
             self.optimizer.flush()      # on EVERY rank: replicas must replay their lazy rows at the same steps
+            self._check_replicas(f"RFD_pretrain epoch {epoch}")
             if self.args.local_rank in [-1, 0]:
                 self.RFD_pretrain_eval()
         self.optimizer.flush()
+        self._check_replicas("RFD_pretrain end")
         if self.args.local_rank in [-1, 0]:
             self.save_model(self.args.output_dir)
         logger.info(str(self.eval_metrics))
@@ -799,6 +810,8 @@ class Trainer:
         logger.info(f"  num examples = {ev.n}")
         if self.optimizer is not None:
             self.optimizer.flush()
+        if not test_eval:       # the epoch-end evaluation of train(): every rank is here, rank 0 alone may save below
+            self._check_replicas("train eval")
         self.model.eval()
         all_logits = []
         with torch.no_grad():
@@ -844,7 +857,8 @@ class Trainer:
         """Full resume state, beyond the reference's weights-only checkpoint: raw (un-flushed)
         weights, optimizer state, step counters."""
         torch.save(dict(model={k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                        optimizer=self.optimizer.state_dict(), global_step=self.global_step), path)
+                        optimizer=self.optimizer.state_dict(), global_step=self.global_step,
+                        fingerprint=dict(replica.state_fingerprint(self.model, self.optimizer))), path)
 
     def load_training_state(self, path):
         st = torch.load(path, map_location="cpu")
@@ -855,6 +869,15 @@ class Trainer:
         self.optimizer.load_state_dict(st["optimizer"])      # (re-derives the bf16 weight shadows)
         self.global_step = int(st["global_step"])
         self._graphs = {}
+        saved = st.get("fingerprint")           # (files written before the key existed load unchecked)
+        if saved is not None:
+            if st["optimizer"].get("flat_pad") != self.optimizer.FLAT_PAD:      # re-packed flat buffers: other words
+                saved = {k: v for k, v in saved.items() if not k.startswith("dense")}
+            got = replica.state_fingerprint(self.model, self.optimizer)
+            bad = [k for k, v in saved.items() if got.get(k) != v]
+            if bad:
+                raise ValueError(f"{path}: the loaded training state does not match the fingerprint saved with it "
+                                 f"in {bad} (a damaged file, or a model / optimizer of another layout)")
 
     def load_model(self, load_step, model_dir):
         sd = torch.load(os.path.join(model_dir, f"{load_step}.model"), map_location="cpu")
