@@ -363,9 +363,9 @@ __global__ void __launch_bounds__(64) publish_i32_kernel(const int32_t* __restri
 extern "C" int mapx_pack_sparse(const int32_t* uniq, const float* rows0, int W0, const float* rows1_opt,
                                 const int32_t* n_uniq, int64_t cap, int64_t maxc, float scale,
                                 int32_t pad_id, int32_t* keys_out, float* rows_out, hipStream_t stream) {
-  MAPX_REQUIRE(uniq && rows0 && n_uniq && keys_out && rows_out, "pack_sparse: null pointer");
   MAPX_REQUIRE(W0 > 0 && W0 % 4 == 0 && cap >= 0 && maxc >= 0, "pack_sparse: bad sizes");
-  if (maxc == 0) return MAPX_OK;
+  if (maxc == 0) return MAPX_OK;          // an empty message: its outputs have no storage to point at
+  MAPX_REQUIRE(uniq && rows0 && n_uniq && keys_out && rows_out, "pack_sparse: null pointer");
   const int Wp = rows1_opt ? W0 + 4 : W0;
   hipLaunchKernelGGL(mapx::pack_sparse_kernel, dim3(mapx::grid_for(maxc * (Wp / 4), 256)), dim3(256), 0, stream,
                      uniq, rows0, W0, rows1_opt, n_uniq, cap, maxc, scale, pad_id, keys_out, rows_out);
