@@ -171,6 +171,23 @@ int mapx_attn_fwd(const float* q, const float* k, const float* v, int64_t G, int
                   float* o, float* p, hipStream_t stream);
 int mapx_attn_bwd(const float* q, const float* k, const float* v, const float* p, const float* d_o,
                   int64_t G, int F, int A, int scaled, float* dq, float* dk, float* dv, hipStream_t stream);
+/* The same with the reference's two dropouts of an attention layer (layers.py:740-742 on the probabilities,
+ * :901-904 on the heads' output; one rate p, 0 <= p < 1):  P~ = P * m_p / (1-p),  O = (P~ V) * m_o / (1-p); probs
+ * receives P undropped.  Backward: dO' = dO m_o / (1-p), dV = P~^T dO', dP = (dO' V^T) m_p / (1-p), then as above.
+ * Neither keep mask is stored: m_p of (g, i, j) is bit j%4 of the Philox draw (seed, counter (g*F + i) * ceil(F/4) + j/4,
+ * offset_p + *offset_dev_opt), kept where the word is >= p * 2^32; m_o of (g, i, a) likewise with counter
+ * (g*F + i) * ceil(A/4) + a/4 and offset_o + *offset_dev_opt (offset_dev_opt may be NULL; offset_p != offset_o makes
+ * the masks independent).  mapx_attn_dropout_masks writes both (1 = kept) into keep_p [G,F,F] and keep_o [G,F,A] with
+ * the very functions the kernels call (tests, debugging).  p = 0 runs mapx_attn_fwd / mapx_attn_bwd.  No atomics.
+ * (Added inside ABI 48: purely additive, no existing entry changed; a binding that needs them finds them by name.) */
+int mapx_attn_drop_fwd(const float* q, const float* k, const float* v, int64_t G, int F, int A, int scaled, float p,
+                       uint64_t seed, uint64_t offset_p, uint64_t offset_o, const int32_t* offset_dev_opt, float* o,
+                       float* probs, hipStream_t stream);
+int mapx_attn_drop_bwd(const float* q, const float* k, const float* v, const float* probs, const float* d_o, int64_t G,
+                       int F, int A, int scaled, float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
+                       const int32_t* offset_dev_opt, float* dq, float* dk, float* dv, hipStream_t stream);
+int mapx_attn_dropout_masks(int64_t G, int F, int A, float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
+                            const int32_t* offset_dev_opt, uint8_t* keep_p, uint8_t* keep_o, hipStream_t stream);
 
 /* ------------------------------------------------------------------ Transformer attention core
  * models.py:491-568 (nn.TransformerEncoderLayer's nn.MultiheadAttention, batch_first, fp32) on B samples of F <= 64

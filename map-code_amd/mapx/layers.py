@@ -820,10 +820,12 @@ class _SelfAttention(Function):
     """One AutoInt-style MultiHeadSelfAttention (reference layers.py:848-914, align_to="output"):
     out = relu(softmax(Q K^T [/ sqrt(A)]) V [+ residual]), Q/K/V/residual = bias-free projections
     of x [B,F,Din]; heads are the reference's .view(B*H, -1, A) chunks.  Projections and all
-    weight / input gradients are MFMA GEMMs, the F x F core is csrc/attn.hip."""
+    weight / input gradients are MFMA GEMMs, the F x F core is csrc/attn.hip.  `drops`: None, or the layer's two
+    dropout sites (on the probabilities, on the heads' output: layers.py:740-742, 901-904), whose masks the core's
+    dropout forms draw themselves; the output they return is already dropped, so the residual branches do not change."""
 
     @staticmethod
-    def forward(ctx, x, wq, wk, wv, wres, heads, attn_size, res_conn, scaled):
+    def forward(ctx, x, wq, wk, wv, wres, heads, attn_size, res_conn, scaled, drops=None):
         B, F, Din = x.shape
         HA = heads * attn_size
         x2 = x.contiguous().view(B * F, Din)
@@ -831,7 +833,16 @@ class _SelfAttention(Function):
         q = ops.gemm(x2, wq, True, True, M, HA, Din)
         k = ops.gemm(x2, wk, True, True, M, HA, Din)
         v = ops.gemm(x2, wv, True, True, M, HA, Din)
-        o, p = ops.attn_fwd(q, k, v, B * heads, F, attn_size, scaled)
+        drop = None
+        if drops is not None:
+            (rate, seed, off_p, dev), (_, seed_o, off_o, dev_o) = drops[0].philox(), drops[1].philox()
+            if rate > 0:
+                assert seed == seed_o and dev is dev_o, "the two dropout sites of a layer belong to one Trainer"
+                drop = (rate, seed, off_p, off_o, dev)
+        if drop is None:
+            o, p = ops.attn_fwd(q, k, v, B * heads, F, attn_size, scaled)
+        else:
+            o, p = ops.attn_drop_fwd(q, k, v, B * heads, F, attn_size, scaled, *drop)
         if res_conn:
             pre = ops.gemm(x2, wres, True, True, M, HA, Din, epi=ops.N.EPI_ADD, aux1=o) if wres is not None \
                 else o + x2
@@ -839,6 +850,7 @@ class _SelfAttention(Function):
             pre = o
         out = torch.relu(pre)
         ctx.cfg = (B, F, Din, heads, attn_size, res_conn, scaled)
+        ctx.drop = drop
         ctx.slots = [_grad_slot(w) if w is not None else None for w in (wq, wk, wv, wres)]
         ctx.save_for_backward(x2, wq, wk, wv, wres, q, k, v, p, out)
         return out.view(B, F, HA)
@@ -849,7 +861,10 @@ class _SelfAttention(Function):
         B, F, Din, heads, A, res_conn, scaled = ctx.cfg
         HA = heads * A
         dpre = ops.relu_mask(g.contiguous().view(B * F, HA), out)
-        dq, dk, dv = ops.attn_bwd(q, k, v, p, dpre, B * heads, F, A, scaled)
+        if ctx.drop is None:
+            dq, dk, dv = ops.attn_bwd(q, k, v, p, dpre, B * heads, F, A, scaled)
+        else:
+            dq, dk, dv = ops.attn_drop_bwd(q, k, v, p, dpre, B * heads, F, A, scaled, *ctx.drop)
         sq, sk, sv, sr = ctx.slots
         grads = []
         for d, slot in ((dq, sq), (dk, sk), (dv, sv)):
@@ -866,7 +881,7 @@ class _SelfAttention(Function):
                 dx = ops.linear_bwd_input(dpre, wres, add=dx)
             else:
                 dx = dx + dpre
-        return dx.view(B, F, Din), grads[0], grads[1], grads[2], gres, None, None, None, None
+        return dx.view(B, F, Din), grads[0], grads[1], grads[2], gres, None, None, None, None, None
 
 
 class _ProjWeight(nn.Module):
@@ -880,12 +895,12 @@ class _ProjWeight(nn.Module):
 
 class MultiHeadSelfAttention(nn.Module):
     """Reference layers.py:848-914 restricted to what AutoInt builds (models.py:451-460):
-    layer_norm off, align_to="output", attention dropout 0."""
+    layer_norm off, align_to="output".  dropout_rate > 0 creates, as the reference does only then, its two dropouts
+    (`dot_product_attention.dropout` on the probabilities, `dropout` on the heads' output before the residual add):
+    MhaDropout sites without parameters, applied inside the attention kernels."""
 
     def __init__(self, input_dim, attention_dim, num_heads, dropout_rate=0.0, use_residual=True, use_scale=False):
         super().__init__()
-        if dropout_rate > 0:
-            raise NotImplementedError("attn_probs_dropout_rate > 0 is not built (deterministic parity path)")
         self.attention_dim, self.num_heads = attention_dim, num_heads
         self.output_dim = num_heads * attention_dim
         self.use_residual, self.use_scale = use_residual, use_scale
@@ -893,11 +908,18 @@ class MultiHeadSelfAttention(nn.Module):
         self.W_k = _ProjWeight(input_dim, self.output_dim)
         self.W_v = _ProjWeight(input_dim, self.output_dim)
         self.W_res = _ProjWeight(input_dim, self.output_dim) if input_dim != self.output_dim else None
+        if dropout_rate > 0:            # (a rate-0 model creates no site: the other dropouts keep their site numbers)
+            self.dot_product_attention = nn.Module()
+            self.dot_product_attention.dropout = MhaDropout(dropout_rate)
+            self.dropout = MhaDropout(dropout_rate)
+        else:
+            self.dropout = None
 
     def forward(self, x):
+        drops = (self.dot_product_attention.dropout, self.dropout) if self.dropout is not None else None
         return _SelfAttention.apply(x, self.W_q.weight, self.W_k.weight, self.W_v.weight,
                                     self.W_res.weight if self.W_res is not None else None, self.num_heads,
-                                    self.attention_dim, self.use_residual, self.use_scale)
+                                    self.attention_dim, self.use_residual, self.use_scale, drops)
 
 
 class _CinStack(Function):
@@ -1047,9 +1069,10 @@ def bce_with_logits(logits, labels):
 
 # ----------------------------------------------------------------------------- Transformer encoder
 class MhaDropout(HipDropout):
-    """nn.MultiheadAttention's dropout of the attention probabilities (p = the layer's `dropout`).  A HipDropout site
-    like the others (Trainer gives it its seed, site and step counter), whose mask the attention kernels draw
-    themselves: ops.mha_fwd / mha_bwd take (p, seed, offset, offset_dev) from `philox()`."""
+    """A dropout applied inside an attention kernel: nn.MultiheadAttention's dropout of the attention probabilities
+    (p = the layer's `dropout`), and AutoInt's two per attention layer.  A HipDropout site like the others (Trainer
+    gives it its seed, site and step counter), whose mask the attention kernels draw themselves: ops.mha_fwd / mha_bwd
+    and ops.attn_drop_fwd / attn_drop_bwd take (p, seed, offset, offset_dev) from `philox()`."""
 
     def philox(self):
         """-> (p, seed, offset, offset_dev) of this forward call; p = 0 in eval mode (no mask)."""
@@ -1062,7 +1085,7 @@ class MhaDropout(HipDropout):
         return self.p, self.seed, base + self._calls, None
 
     def forward(self, x, out=None):
-        raise RuntimeError("MhaDropout is applied inside the attention kernels (_MhaCore)")
+        raise RuntimeError("MhaDropout is applied inside the attention kernels (_MhaCore, _SelfAttention)")
 
 
 class _MhaCore(Function):

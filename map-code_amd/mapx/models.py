@@ -413,7 +413,7 @@ class AutoInt(BaseModel):
     the flattened [B, F*heads*attn_size] output feeds the MFP / RFD heads or `attn_out`; the finetune model adds
     the LR term (use_lr: its weight is the secondary parameter of the embedding's RowTable, as in DeepFM) and an MLP
     tower over the flattened embeddings (num_dnn_layers > 0: `dnn` + `dnn_out`), models.py:464-471, 482-486.
-    Not built: attention dropout > 0."""
+    attn_probs_dropout_rate > 0: two dropouts per attention layer, drawn inside csrc/attn.hip."""
     used_params = ["embed_size", "num_attn_layers", "attn_size", "num_attn_heads", "attn_probs_dropout_rate",
                    "use_lr", "res_conn", "attn_scale", "dnn_size", "num_dnn_layers", "dnn_act", "dnn_drop"]
 

@@ -45,6 +45,9 @@ SIGNATURES = {
     "mapx_fm_bwd": (_i, [_p, _p, _p, _i64, _i, _i, _p, _p]),
     "mapx_attn_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p]),
     "mapx_attn_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p]),
+    "mapx_attn_drop_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _u64, _p, _p, _p, _p]),
+    "mapx_attn_drop_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
+    "mapx_attn_dropout_masks": (_i, [_i64, _i, _i, _f, _u64, _u64, _u64, _p, _p, _p, _p]),
     "mapx_mha_fwd": (_i, [_p, _i64, _i, _i, _i, _f, _u64, _u64, _p, _p, _p, _p]),
     "mapx_mha_bwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _p, _p, _p]),
     "mapx_mha_dropout_mask": (_i, [_i64, _i, _i, _f, _u64, _u64, _p, _p, _p]),

@@ -620,6 +620,37 @@ def attn_bwd(q, k, v, p, d_o, G, F, A, scaled):
     return dq, dk, dv
 
 
+def attn_drop_fwd(q, k, v, G, F, A, scaled, p, seed, offset_p, offset_o, offset_dev=None):
+    """attn_fwd with the layer's two dropouts inside the kernel: O = ((P * m_p / (1-p)) V) * m_o / (1-p) with
+    (m_p, m_o) = attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev) -> (o, p undropped)."""
+    require_gpu(q, k, v)
+    o = torch.empty_like(q)
+    probs = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
+    check(lib.mapx_attn_drop_fwd(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), float(p), int(seed), int(offset_p),
+                                 int(offset_o), ptr(offset_dev), ptr(o), ptr(probs), stream()))
+    return o, probs
+
+
+def attn_drop_bwd(q, k, v, probs, d_o, G, F, A, scaled, p, seed, offset_p, offset_o, offset_dev=None):
+    """-> (dq, dk, dv); both masks are regenerated from (seed, offsets)."""
+    require_gpu(q, k, v, probs, d_o)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(lib.mapx_attn_drop_bwd(ptr(q), ptr(k), ptr(v), ptr(probs), ptr(d_o.contiguous()), G, F, A, int(bool(scaled)),
+                                 float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev), ptr(dq), ptr(dk),
+                                 ptr(dv), stream()))
+    return dq, dk, dv
+
+
+def attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev=None, device="cuda"):
+    """The keep masks (uint8, 1 = kept) that attn_drop_fwd / attn_drop_bwd draw for these arguments:
+    (keep_p [G,F,F] on the probabilities, keep_o [G,F,A] on the output)."""
+    keep_p = torch.empty(G, F, F, dtype=torch.uint8, device=device)
+    keep_o = torch.empty(G, F, A, dtype=torch.uint8, device=device)
+    check(lib.mapx_attn_dropout_masks(G, F, A, float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev),
+                                      ptr(keep_p), ptr(keep_o), stream()))
+    return keep_p, keep_o
+
+
 # --------------------------------------------------------------------------- Transformer attention core
 def mha_fwd(qkv, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
     """qkv [B*F, 3E] (the in-projection's output, read in place) -> (o [B*F, E] heads concatenated,
