@@ -678,6 +678,50 @@ int mapx_vocab_map(const int32_t* slot_of_row, const int32_t* slot_entry, const 
                    const int32_t* n_kept, int64_t n, int64_t base, int64_t* ids_out, int64_t ld_out,
                    hipStream_t stream);
 
+/* ------------------------------------------------------------------ FGCNN backbone
+ * models.py:325-407, layers.py:204-251 (FGCNNBlock) and :105-137 (InnerProductLayer, output="inner_product").
+ * All tensors fp32 and dense, [B, C, H, E] with E % 4 == 0 and 16-byte aligned; at most 32 channels, odd kernel
+ * height kh <= 15; the weights and one sample's slabs must fit 128 KB of LDS.  No atomics: bitwise deterministic.
+ *
+ * conv_fwd   z[b,co,h,e] = bias[co] + sum_ci sum_k w[co,ci,k] x[b,ci,h+k-(kh-1)/2,e]   (rows outside [0,H) are zero);
+ *            part_opt [B,Cout,2] (fp64) receives per (sample, channel) sum(z) and sum(z^2)   (NULL: eval, no statistics).
+ * bn_stats   n = B*H*E values per channel: mean = S/n, var = SS/n - mean^2 (fp64), stats[c] = {mean, 1/sqrt(var+eps)};
+ *            running_mean = (1-m) running_mean + m mean, running_var = (1-m) running_var + m var n/(n-1) (unbiased),
+ *            *num_batches_tracked += 1 on the device (BatchNorm2d in train mode).  n == 1 is refused as torch does.
+ * pool_fwd   u = gamma (z - mean) rstd + beta with {mean, rstd} = stats_opt[c], or (stats_opt NULL, eval)
+ *            {running_mean[c], 1/sqrt(running_var[c] + eps)};  a = act(u), act 0 = tanh, 1 = relu;
+ *            y[b,c,o,e] = max_k a[b,c,o*ps-pad+k,e], k in [0,ps), pad = H % ps rows of -inf on both ends, floor mode:
+ *            y is [B,C,Hp,E], Hp = (H + 2 pad - ps) / ps + 1.  2 pad > ps is refused (torch's MaxPool2d raises too).
+ *            idx_opt [B,C,Hp,E] (uint8) = k of the maximum, the first of equal ones.
+ * pool_bwd   g[b,c,h,e] = dy[b,c,o,e] act'(u) where h is the maximum of its window o = (h+pad)/ps, else 0 (u recomputed
+ *            from z);  part [B,C,2] (fp64) = per (sample, channel) sum(g), sum(g xhat), xhat = (z - mean) rstd.
+ * bn_bwd_sums dbeta[c] = sum(g), dgamma[c] = sum(g xhat) over the batch, bsum[c] = {dbeta/n, dgamma/n}.
+ * conv_bwd   dz = gamma rstd (g - dbeta/n - xhat dgamma/n);  dx_opt[b,ci,h,e] = sum_co sum_k w[co,ci,k] dz[b,co,h-k+pad,e];
+ *            dw[co,ci,k] = sum_{b,h,e} dz[b,co,h,e] x[b,ci,h+k-pad,e], db[co] = sum dz: partial rows per group of samples
+ *            in part_w [groups, Cout*Cin*kh] / part_b [groups, Cout] (groups = mapx_fgcnn_conv_bwd_groups(B)), added in order. */
+int mapx_fgcnn_conv_fwd(const float* x, const float* w, const float* bias, int64_t B, int Cin, int Cout, int H, int E,
+                        int kh, float* z, double* part_opt, hipStream_t stream);
+int mapx_fgcnn_bn_stats(const double* part, int64_t B, int C, int H, int E, float eps, float momentum, float* stats,
+                        float* running_mean_opt, float* running_var_opt, int64_t* num_batches_tracked_opt,
+                        hipStream_t stream);
+int mapx_fgcnn_pool_fwd(const float* z, const float* stats_opt, const float* running_mean_opt,
+                        const float* running_var_opt, float eps, const float* gamma, const float* beta, int64_t B, int C,
+                        int H, int E, int ps, int act, float* y, uint8_t* idx_opt, hipStream_t stream);
+int mapx_fgcnn_pool_bwd(const float* dy, const uint8_t* idx, const float* z, const float* stats, const float* gamma,
+                        const float* beta, int64_t B, int C, int H, int E, int ps, int act, float* g, double* part,
+                        hipStream_t stream);
+int mapx_fgcnn_bn_bwd_sums(const double* part, int64_t B, int C, int H, int E, float* bsum, float* dgamma, float* dbeta,
+                           hipStream_t stream);
+int mapx_fgcnn_conv_bwd_groups(int64_t B);
+int mapx_fgcnn_conv_bwd(const float* g, const float* z, const float* x, const float* w, const float* stats,
+                        const float* gamma, const float* bsum, int64_t B, int Cin, int Cout, int H, int E, int kh,
+                        float* dx_opt, float* part_w, float* part_b, float* dw, float* db, hipStream_t stream);
+/* Pairwise inner products of x [B,T,E] (2 <= T <= 192, E % 4 == 0, E <= 64): out[b, p] = x[b,i,:] . x[b,j,:] over the
+ * pairs i < j in row-major order (torch.masked_select(x x^T, strict upper triangle)), out [B, T(T-1)/2].
+ * Backward: dx[b,i,:] = sum_{j>i} g[b,(i,j)] x[b,j,:] + sum_{j<i} g[b,(j,i)] x[b,j,:]. */
+int mapx_inner_product_fwd(const float* x, int64_t B, int T, int E, float* out, hipStream_t stream);
+int mapx_inner_product_bwd(const float* g, const float* x, int64_t B, int T, int E, float* dx, hipStream_t stream);
+
 /* ------------------------------------------------------------------ state fingerprint (replica-consistency check)
  * No reference site: the reference trains unsynchronised replicas and never compares them.  An
  * order-independent 64-bit integer fingerprint of n_words raw 32-bit words (bit patterns: -0.0 != +0.0, NaN payloads

@@ -151,6 +151,8 @@ class PlanSlot:
             for t in self.value.tensors():
                 t.record_stream(self.origin)
 
+    MAX_PER_CHAIN = 2       # key lists one chain of launches sorts (csrc/radixsort.h kMaxSortProbs)
+
     @staticmethod
     def start_many(slots, implied=(), after=None):
         """Build the plans of several tables' slots with ONE chain of launches (ops.SegPlan.build_many:
@@ -159,7 +161,11 @@ class PlanSlot:
         slots = [s for s in slots if s is not None and s.value is None]
         if len(slots) <= 1:
             for s in slots:
-                s.start()
+                s.start(after=after)
+            return
+        if len(slots) > PlanSlot.MAX_PER_CHAIN:        # (FGCNN + MFP: two embedding tables and the NCE table)
+            for i in range(0, len(slots), PlanSlot.MAX_PER_CHAIN):
+                PlanSlot.start_many(slots[i:i + PlanSlot.MAX_PER_CHAIN], implied=implied, after=after)
             return
         keys = [s.keys for s in slots]
         side = _side_stream(keys[0].device)
@@ -1222,3 +1228,129 @@ class _FieldPool(Function):
 
 def field_pool(x3, mode, scores=None):
     return _FieldPool.apply(x3, scores, mode)
+
+
+# ----------------------------------------------------------------------------- FGCNN
+class _InnerProduct(Function):
+    """InnerProductLayer(output='inner_product') (reference layers.py:132-135): x [B,T,E] -> x_i . x_j over the pairs
+    i < j in masked_select's order, [B, T(T-1)/2]  (csrc/fgcnn.hip)."""
+
+    @staticmethod
+    def forward(ctx, x3):
+        x3 = x3.contiguous()
+        ctx.save_for_backward(x3)
+        return ops.inner_product_fwd(x3)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x3,) = ctx.saved_tensors
+        return ops.inner_product_bwd(g, x3)
+
+
+def inner_product(x3):
+    return _InnerProduct.apply(x3)
+
+
+class _ConvBnActPool(Function):
+    """One FGCNN stage: Conv2d((kh,1)) -> BatchNorm2d -> act -> MaxPool2d((ps,1)) (reference layers.py:226-232) as
+    three launches forward (conv + partial statistics, their finalise, normalise + act + pool) and four backward
+    (csrc/fgcnn.hip).  Train mode normalises with the batch statistics and moves the running ones (and the batch
+    counter) on the device; saved for backward: the input, z (the conv output) and one uint8 argmax per pooled
+    element.  Eval mode normalises with the running statistics, saves nothing and has no backward."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, tracked, ps, act, training):
+        x = x.contiguous()
+        ctx.training = training
+        if not training:
+            z, _ = ops.fgcnn_conv_fwd(x, w, b, stats=False)
+            y, _ = ops.fgcnn_pool_fwd(z, gamma, beta, ps, act, running_mean=running_mean, running_var=running_var,
+                                      save=False)
+            return y
+        z, part = ops.fgcnn_conv_fwd(x, w, b)
+        stats = ops.fgcnn_bn_stats(part, z.shape[2], z.shape[3], running_mean, running_var, tracked)
+        y, idx = ops.fgcnn_pool_fwd(z, gamma, beta, ps, act, stats=stats)
+        ctx.cfg = (ps, act)
+        ctx.slots = tuple(_grad_slot(p) for p in (w, b, gamma, beta))
+        ctx.save_for_backward(x, w, z, idx, stats, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.training:
+            raise NotImplementedError("FGCNN in eval mode (BatchNorm on its running statistics) is forward only")
+        x, w, z, idx, stats, gamma, beta = ctx.saved_tensors
+        ps, act = ctx.cfg
+        sw, sb, sg, sbe = ctx.slots
+        dx, dw, db, dgamma, dbeta = ops.fgcnn_bwd(dy, idx, z, x, w, stats, gamma, beta, ps, act, dw=sw, db=sb,
+                                                  dgamma=sg, dbeta=sbe, need_dx=ctx.needs_input_grad[0])
+        return (dx, None if sw is not None else dw, None if sb is not None else db,
+                None if sg is not None else dgamma, None if sbe is not None else dbeta, None, None, None, None, None,
+                None)
+
+
+class _ConvWeights(nn.Module):
+    """`weight` [Cout, Cin, kh, 1] and `bias` [Cout] of an nn.Conv2d with a (kh, 1) kernel (its default
+    initialisation)."""
+
+    def __init__(self, in_channels, out_channels, kernel_height):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_height, 1))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(in_channels * kernel_height)
+        with torch.no_grad():
+            self.bias.uniform_(-bound, bound)
+
+
+class _BatchNormState(nn.Module):
+    """The parameters and buffers of an nn.BatchNorm2d (eps 1e-5, momentum 0.1, affine, tracked statistics)."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(channels))
+        self.bias = nn.Parameter(torch.zeros(channels))
+        self.register_buffer("running_mean", torch.zeros(channels))
+        self.register_buffer("running_var", torch.ones(channels))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+
+class FGCNNBlock(nn.Module):
+    """Reference layers.py:204-251: stage i is Conv2d(C_{i-1}, C_i, (kh_i, 1), padding ((kh_i-1)//2, 0)) ->
+    BatchNorm2d -> act -> MaxPool2d((ps_i, 1), padding (H_{i-1} % ps_i, 0)) on [B, C_{i-1}, H_{i-1}, E], then
+    Linear -> act from the flattened stage output to R_i * H_i new feature rows; the new rows of all stages are
+    concatenated.  state_dict keys `conv_layers.{i}.0.*` (conv), `.1.*` (batch norm), `recombine_layers.{i}.0.*`."""
+    ACTS = ("tanh", "relu")
+
+    def __init__(self, num_fields, embedding_dim, channels, kernel_heights, pooling_sizes, recombined_channels,
+                 activation="tanh"):
+        super().__init__()
+        self.act = str(activation).lower()
+        if self.act not in self.ACTS:
+            raise NotImplementedError(f"conv_act={activation!r}: the FGCNN kernels build {' | '.join(self.ACTS)}")
+        self.embedding_dim = embedding_dim
+        self.pooling_sizes = list(pooling_sizes)
+        self.conv_layers, self.recombine_layers = nn.ModuleList(), nn.ModuleList()
+        c_in, height = 1, num_fields
+        for c_out, kh, ps, rc in zip(channels, kernel_heights, pooling_sizes, recombined_channels):
+            if 2 * (height % ps) > ps:
+                raise ValueError(f"pooling_sizes: a stage of height {height} pooled by {ps} pads {height % ps} rows, "
+                                 "more than half of the pooling size (torch's MaxPool2d raises too)")
+            self.conv_layers.append(nn.ModuleDict({"0": _ConvWeights(c_in, c_out, kh), "1": _BatchNormState(c_out)}))
+            height = int(math.ceil(height / ps))
+            self.recombine_layers.append(nn.ModuleDict({
+                "0": HipLinear(height * embedding_dim * c_out, height * embedding_dim * rc, relu=self.act == "relu")}))
+            c_in = c_out
+
+    def forward(self, x):
+        """x [B, 1, F, E] -> the new feature rows [B, sum_i R_i H_i, E]."""
+        B, new = x.shape[0], []
+        for stage, rec, ps in zip(self.conv_layers, self.recombine_layers, self.pooling_sizes):
+            conv, bn = stage["0"], stage["1"]
+            x = _ConvBnActPool.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                     bn.num_batches_tracked, ps, self.act, self.training)
+            r = rec["0"](x.flatten(start_dim=1))
+            if self.act != "relu":
+                r = _Act.apply(r, self.act, None)
+            new.append(r.reshape(B, -1, self.embedding_dim))
+        return torch.cat(new, dim=1)

@@ -1,6 +1,7 @@
 """BaseModel + DCNV2 (host mirror of reference code/models.py:21-127, 282-322): same factory,
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
-is a gfx950 kernel."""
+is a gfx950 kernel.  The other backbones the factory builds: DNN, DeepFM, xDeepFM, AutoInt, trans, fgcnn
+(fignn raises)."""
 import logging
 
 import torch
@@ -8,9 +9,9 @@ from torch import nn
 
 from . import ops
 from .arguments import Config
-from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, HipLinear, MLPBlock, MultiHeadSelfAttention,
-                     RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer, bce_with_logits, field_pool,
-                     fm_product_sum)
+from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, FGCNNBlock, HipLinear, MLPBlock,
+                     MultiHeadSelfAttention, RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer,
+                     bce_with_logits, field_pool, fm_product_sum, inner_product)
 from .nce import IndexLinear
 
 logger = logging.getLogger(__name__)
@@ -38,7 +39,7 @@ def plan_after_main(pretrain, f32_trunk, D):
     return pretrain or (f32_trunk and D < WIDE_CROSS_TOWER)
 
 
-_OTHER_BACKBONES = ("fignn", "fgcnn")
+_OTHER_BACKBONES = ("fignn",)
 
 
 class _RfdPredictor(nn.ModuleDict):
@@ -78,10 +79,12 @@ class BaseModel(nn.Module):
             return xDeepFM(config)
         if name == "trans":
             return Transformer(config)
+        if name == "fgcnn":
+            return FGCNN(config)
         if name in _OTHER_BACKBONES:
             raise NotImplementedError(
                 f"{config.model_name}: mapx builds the DCNv2 hot path and, of the other backbones "
-                "(SURVEY §8 f4), DNN, DeepFM, xDeepFM, AutoInt and the Transformer")
+                "(SURVEY §8 f4), DNN, DeepFM, xDeepFM, AutoInt, the Transformer and FGCNN")
         raise NotImplementedError(config.model_name)
 
     def validate_model_config(self):
@@ -91,7 +94,7 @@ class BaseModel(nn.Module):
 
     # ------------------------------------------------------------------ heads
     def _sample_early(self, labels, masked_index, noise_samples):
-        """MFP over a single-stream trunk (DNN, DeepFM, xDeepFM, AutoInt): the NCE head's sampling and the lazy
+        """MFP over a single-stream trunk (DNN, DeepFM, xDeepFM, AutoInt, trans, FGCNN): the NCE head's sampling and the lazy
         catch-up of the sampled rows need only the targets — they run on the tower stream beside the trunk instead of
         between the trunk and the loss (as DCNV2.forward does by hand).  -> (ids | None, join state)."""
         if not (self.config.pretrain and self.config.pt_type == "MFP" and masked_index is not None
@@ -105,17 +108,23 @@ class BaseModel(nn.Module):
         return idx, (main, tower, forked, labels)
 
     def _plans_and_join(self, idx, state):
-        """Behind the trunk: both tables' segment plans from ONE chain of launches (behind what the main stream holds),
-        then the main stream takes the sampled ids over."""
+        """Behind the trunk: the tables' segment plans from ONE chain of launches per two tables (behind what the main
+        stream holds), then the main stream takes the sampled ids over.  The trunk's tables: `embed`, and FGCNN's second
+        embedding `fg_embed`."""
+        trunk = [self.embed.table]
+        if getattr(self, "fg_embed", None) is not None:
+            trunk.append(self.fg_embed.table)
         if state is None:
-            self.embed.table.start_plan()
+            for tb in trunk:
+                tb.start_plan()
             return
         main, tower, forked, labels = state
         from .layers import PlanSlot
-        if self.mfp_criterion.table.plan is not None and self.embed.table.plan is not None:
-            PlanSlot.start_many([self.embed.table.plan, self.mfp_criterion.table.plan], after=main)
+        if self.mfp_criterion.table.plan is not None and all(tb.plan is not None for tb in trunk):
+            PlanSlot.start_many([tb.plan for tb in trunk] + [self.mfp_criterion.table.plan], after=main)
         else:
-            self.embed.table.start_plan()
+            for tb in trunk:
+                tb.start_plan()
         ops.stream_wait(main, tower)
         if forked:
             labels.record_stream(tower)
@@ -601,3 +610,116 @@ class Transformer(BaseModel):
         if self.mlp is not None:
             logits = logits + self.mlp_out(self.mlp(ops.flat_rows(x)))      # models.py:564-565
         return self.get_outputs(logits, labels)
+
+
+def _int_list(config, key):
+    try:
+        return [int(c) for c in str(getattr(config, key)).split(",")]
+    except ValueError:
+        raise ValueError(f"{key}={getattr(config, key)!r}: a comma list of integers") from None
+
+
+class FGCNN(BaseModel):
+    """Feature generation by convolution (reference models.py:325-407): a second embedding `fg_embed` of the same ids
+    (or `embed` itself with share_embedding) goes through FGCNNBlock (Conv2d (kh,1) -> BatchNorm2d -> conv_act ->
+    MaxPool2d (ps,1) -> recombine Linear -> conv_act per stage); the new feature rows are concatenated behind the
+    embeddings to `combined` [B,T,E], and cat([combined.flatten(1), upper triangle of combined combined^T]) feeds the
+    MFP / RFD heads, or `dnn` + `fc_out` (fc_out alone when num_hidden_layers = 0).  Conv, batch norm, pooling and the
+    inner products are csrc/fgcnn.hip: at most 32 channels, odd kernel heights <= 15, T <= 192 rows, conv_act tanh |
+    relu, fp32.  Batch norm keeps per-replica buffers that the reference's DistributedDataParallel re-broadcasts from
+    rank 0 at every forward; that is not built, so the model trains on one replica only (`single_replica_only`)."""
+    used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
+                   "share_embedding", "channels", "kernel_heights", "pooling_sizes", "recombined_channels",
+                   "conv_act"]
+    MAX_ROWS = 192        # csrc/fgcnn.hip kIpMaxT
+    MAX_LDS = 128 * 1024  # csrc/fgcnn.hip kFgLdsLimit: weights + one sample's input and gradient slabs
+    single_replica_only = ("model_name=fgcnn trains on one replica: its BatchNorm buffers (running_mean, running_var, "
+                           "num_batches_tracked) would have to be broadcast from rank 0 at every forward, as the "
+                           "reference's DistributedDataParallel does, and that is not built")
+
+    def __init__(self, config: Config):
+        super().__init__(model_name="fgcnn", config=config)
+        lists = {k: _int_list(config, k) for k in ("channels", "kernel_heights", "pooling_sizes", "recombined_channels")}
+        if len({len(v) for v in lists.values()}) != 1:
+            raise ValueError("channels, kernel_heights, pooling_sizes and recombined_channels must list one value per "
+                             "stage each, got " + ", ".join(f"{k}={getattr(config, k)!r}" for k in lists))
+        if any(kh < 1 or kh % 2 == 0 for kh in lists["kernel_heights"]):
+            raise NotImplementedError(f"kernel_heights={config.kernel_heights!r}: odd heights only (an even height "
+                                      "changes the stage's height, which the reference's own bookkeeping of the "
+                                      "recombine layers' widths does not follow)")
+        if max(lists["kernel_heights"]) > 15 or max(lists["channels"]) > 32:
+            raise NotImplementedError(f"channels={config.channels!r}, kernel_heights={config.kernel_heights!r}: the "
+                                      "convolution kernels take at most 32 channels and kernel heights up to 15")
+        if min(lists["channels"] + lists["pooling_sizes"] + lists["recombined_channels"]) < 1:
+            raise ValueError("channels, pooling_sizes and recombined_channels must be positive")
+        c_in, height = 1, config.num_fields
+        for c, kh, ps in zip(lists["channels"], lists["kernel_heights"], lists["pooling_sizes"]):
+            lds = 4 * (c * c_in * kh + (c_in + c) * height * config.embed_size)
+            if lds > self.MAX_LDS:
+                raise NotImplementedError(
+                    f"fgcnn: a stage of {c_in} -> {c} channels over {height} rows of embed_size={config.embed_size} "
+                    f"needs {lds} bytes of LDS in the convolution's backward kernel, above {self.MAX_LDS}: lower "
+                    f"embed_size or channels={config.channels!r}")
+            c_in, height = c, -(-height // ps)
+        self.share_embedding = bool(config.share_embedding)
+        self.embed = Embeddings(config)
+        self.embed.defer_plan = True
+        if not self.share_embedding:
+            # a second table over the same ids, with its own optimizer state and fingerprint entries
+            self.fg_embed = Embeddings(config)
+            self.fg_embed.defer_plan = True
+            self.fg_embed.table = RowTable("fg_embed.embedding", self.fg_embed.embedding.weight)
+        else:
+            self.fg_embed = None
+        self.fgcnn_layer = FGCNNBlock(config.num_fields, config.embed_size, lists["channels"], lists["kernel_heights"],
+                                      lists["pooling_sizes"], lists["recombined_channels"], activation=config.conv_act)
+        final_dim, total = self.compute_input_dim(config.embed_size, config.num_fields, lists["channels"],
+                                                  lists["pooling_sizes"], lists["recombined_channels"])
+        if total > self.MAX_ROWS or config.embed_size > 64:
+            raise NotImplementedError(f"fgcnn: the inner-product kernel takes at most {self.MAX_ROWS} feature rows of "
+                                      f"embed_size <= 64 (num_fields, pooling_sizes and recombined_channels give "
+                                      f"{total} rows, embed_size={config.embed_size})")
+        self.final_dim, self.total_features = final_dim, total
+        self.ip_layer = _InnerProductBuffers(total)
+        if config.pretrain:
+            self.create_pretraining_predictor(final_dim)
+        elif config.num_hidden_layers > 0:
+            self.dnn = MLPBlock(input_dim=final_dim, hidden_size=config.hidden_size,
+                                num_hidden_layers=config.num_hidden_layers,
+                                hidden_dropout_rate=config.hidden_dropout_rate, hidden_act=config.hidden_act)
+            self.fc_out = HipLinear(config.hidden_size, 1)
+        else:
+            self.dnn = None
+            self.fc_out = HipLinear(final_dim, 1)
+
+    @staticmethod
+    def compute_input_dim(embedding_dim, num_fields, channels, pooling_sizes, recombined_channels):
+        """-> (width of the heads' input, T = rows of `combined`)   (models.py:369-382)."""
+        total = height = num_fields
+        for i in range(len(channels)):
+            height = -(-height // pooling_sizes[i])
+            total += height * recombined_channels[i]
+        return total * (total - 1) // 2 + total * embedding_dim, total
+
+    def combined_features(self, input_ids, between=None):
+        """cat([embed(ids), FGCNNBlock(fg_embed(ids))], dim=1) [B,T,E]; `between`: called behind the gathers."""
+        feat_embed = self.embed(input_ids)
+        feat_embed2 = feat_embed if self.fg_embed is None else self.fg_embed(input_ids)
+        if between is not None:
+            between()
+        return torch.cat([feat_embed, self.fgcnn_layer(feat_embed2.unsqueeze(1))], dim=1)
+
+    def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
+        early = [None, None]
+
+        def sample():           # (as the other single-stream trunks: behind the gathers, beside the trunk)
+            early[0], early[1] = self._sample_early(labels, masked_index, noise_samples)
+        combined = self.combined_features(input_ids, between=sample)
+        nce_idx, early = early
+        dense_input = torch.cat([combined.flatten(start_dim=1), inner_product(combined)], dim=1)
+        self._plans_and_join(nce_idx, early)
+        if self.config.pretrain:
+            return self.get_outputs(dense_input, labels, masked_index, noise_samples=noise_samples, nce_idx=nce_idx)
+        if self.dnn is not None:
+            dense_input = self.dnn(dense_input)
+        return self.get_outputs(self.fc_out(dense_input), labels)

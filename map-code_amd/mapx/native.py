@@ -134,6 +134,15 @@ SIGNATURES = {
     "mapx_table_adam": (_i, [_p, _p, _p, _i64, _i, _f, _p, _p, _p, _i64, _f, _p, _p, _i64, _i64, _p, _p, _p, _p,
                              _i, _p, _p, _i, _i, _d, _d, _d, _i, _p]),
     "mapx_fingerprint_words": (_i, [_p, _i64, _p, _p, _i, _p]),
+    "mapx_fgcnn_conv_fwd": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_bn_stats": (_i, [_p, _i64, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
+    "mapx_fgcnn_pool_fwd": (_i, [_p, _p, _p, _p, _f, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_pool_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_bn_bwd_sums": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p]),
+    "mapx_fgcnn_conv_bwd_groups": (_i, [_i64]),
+    "mapx_fgcnn_conv_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "mapx_inner_product_fwd": (_i, [_p, _i64, _i, _i, _p, _p]),
+    "mapx_inner_product_bwd": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
 }
 
 

@@ -708,6 +708,114 @@ def field_pool_bwd(g, x3, mode, weights=None):
     return dx, ds
 
 
+# --------------------------------------------------------------------------- FGCNN (csrc/fgcnn.hip)
+FGCNN_ACTS = {"tanh": 0, "relu": 1}
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1          # nn.BatchNorm2d's defaults, which the reference's FGCNNBlock takes
+
+
+def _f32c(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("fgcnn kernels take contiguous fp32 tensors")
+
+
+def fgcnn_conv_fwd(x, w, bias, stats=True):
+    """x [B,Cin,H,E], w [Cout,Cin,kh(,1)], bias [Cout] -> (z [B,Cout,H,E], part [B,Cout,2] fp64 | None): the
+    convolution and, with `stats`, the per-sample partial sums of the batch statistics from the same launch."""
+    require_gpu(x, w, bias)
+    _f32c(x, w, bias)
+    B, Cin, H, E = x.shape
+    Cout, kh = w.shape[0], w.shape[2]
+    if w.shape[1] != Cin or w.numel() != Cout * Cin * kh:
+        raise ValueError(f"fgcnn_conv_fwd: weight {tuple(w.shape)} does not fit the input {tuple(x.shape)}")
+    z = torch.empty(B, Cout, H, E, dtype=torch.float32, device=x.device)
+    part = torch.empty(B, Cout, 2, dtype=torch.float64, device=x.device) if stats else None
+    check(lib.mapx_fgcnn_conv_fwd(ptr(x), ptr(w), ptr(bias), B, Cin, Cout, H, E, kh, ptr(z), ptr(part), stream()))
+    return z, part
+
+
+def fgcnn_bn_stats(part, H, E, running_mean=None, running_var=None, tracked=None, eps=BN_EPS, momentum=BN_MOMENTUM):
+    """part [B,C,2] -> stats [C,2] = {mean, rstd} of the batch; moves the running statistics (unbiased variance) and
+    the int64 batch counter in place, on the device."""
+    require_gpu(part, running_mean, running_var, tracked)
+    B, C = part.shape[0], part.shape[1]
+    if tracked is not None and tracked.dtype != torch.int64:
+        raise TypeError("fgcnn_bn_stats: num_batches_tracked is an int64 tensor")
+    _f32c(running_mean, running_var)
+    stats = torch.empty(C, 2, dtype=torch.float32, device=part.device)
+    check(lib.mapx_fgcnn_bn_stats(ptr(part), B, C, H, E, float(eps), float(momentum), ptr(stats), ptr(running_mean),
+                                  ptr(running_var), ptr(tracked), stream()))
+    return stats
+
+
+def fgcnn_pool_shape(H, ps):
+    """-> (padding, pooled height) of MaxPool2d((ps, 1), padding=(H % ps, 0)) in floor mode."""
+    pad = H % ps
+    return pad, (H + 2 * pad - ps) // ps + 1
+
+
+def fgcnn_pool_fwd(z, gamma, beta, ps, act, stats=None, running_mean=None, running_var=None, eps=BN_EPS, save=True):
+    """BatchNorm (batch `stats` [C,2], or the running statistics) -> act -> max-pool over ps rows:
+    z [B,C,H,E] -> (y [B,C,Hp,E], idx uint8 [B,C,Hp,E] | None)."""
+    require_gpu(z, gamma, beta, stats, running_mean, running_var)
+    _f32c(z, gamma, beta, stats, running_mean, running_var)
+    B, C, H, E = z.shape
+    _, Hp = fgcnn_pool_shape(H, ps)
+    y = torch.empty(B, C, max(Hp, 0), E, dtype=torch.float32, device=z.device)
+    idx = torch.empty(B, C, max(Hp, 0), E, dtype=torch.uint8, device=z.device) if save else None
+    check(lib.mapx_fgcnn_pool_fwd(ptr(z), ptr(stats), ptr(running_mean), ptr(running_var), float(eps), ptr(gamma),
+                                  ptr(beta), B, C, H, E, int(ps), FGCNN_ACTS[act], ptr(y), ptr(idx), stream()))
+    return y, idx
+
+
+def fgcnn_bwd(dy, idx, z, x, w, stats, gamma, beta, ps, act, dw=None, db=None, dgamma=None, dbeta=None, need_dx=True):
+    """Backward of pool <- act <- BatchNorm (batch statistics) <- conv: -> (dx | None, dw, db, dgamma, dbeta).
+    dw / db / dgamma / dbeta: optional destinations (the optimizer's gradient slots)."""
+    require_gpu(dy, idx, z, x, w, stats, gamma, beta)
+    dy = dy.contiguous()
+    _f32c(dy, z, x, w, stats, gamma, beta, dw, db, dgamma, dbeta)
+    B, Cin, H, E = x.shape
+    Cout, kh = w.shape[0], w.shape[2]
+    dev = x.device
+    g = torch.empty_like(z)
+    part = torch.empty(B, Cout, 2, dtype=torch.float64, device=dev)
+    check(lib.mapx_fgcnn_pool_bwd(ptr(dy), ptr(idx), ptr(z), ptr(stats), ptr(gamma), ptr(beta), B, Cout, H, E, int(ps),
+                                  FGCNN_ACTS[act], ptr(g), ptr(part), stream()))
+    bsum = torch.empty(Cout, 2, dtype=torch.float32, device=dev)
+    dgamma = torch.empty_like(gamma) if dgamma is None else dgamma
+    dbeta = torch.empty_like(beta) if dbeta is None else dbeta
+    check(lib.mapx_fgcnn_bn_bwd_sums(ptr(part), B, Cout, H, E, ptr(bsum), ptr(dgamma), ptr(dbeta), stream()))
+    G = lib.mapx_fgcnn_conv_bwd_groups(B)
+    pw = torch.empty(G, Cout * Cin * kh, dtype=torch.float32, device=dev)
+    pb = torch.empty(G, Cout, dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w) if dw is None else dw
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if db is None else db
+    check(lib.mapx_fgcnn_conv_bwd(ptr(g), ptr(z), ptr(x), ptr(w), ptr(stats), ptr(gamma), ptr(bsum), B, Cin, Cout, H, E,
+                                  kh, ptr(dx), ptr(pw), ptr(pb), ptr(dw), ptr(db), stream()))
+    return dx, dw, db, dgamma, dbeta
+
+
+def inner_product_fwd(x3):
+    """x3 [B,T,E] -> [B, T(T-1)/2]: x_i . x_j over the pairs i < j, row-major (layers.py:132-135)."""
+    require_gpu(x3)
+    _f32c(x3)
+    B, T, E = x3.shape
+    out = torch.empty(B, T * (T - 1) // 2, dtype=torch.float32, device=x3.device)
+    check(lib.mapx_inner_product_fwd(ptr(x3), B, T, E, ptr(out), stream()))
+    return out
+
+
+def inner_product_bwd(g, x3):
+    require_gpu(g, x3)
+    g = g.contiguous()
+    _f32c(g, x3)
+    B, T, E = x3.shape
+    dx = torch.empty_like(x3)
+    check(lib.mapx_inner_product_bwd(ptr(g), ptr(x3), B, T, E, ptr(dx), stream()))
+    return dx
+
+
 # --------------------------------------------------------------------------- NCE
 def alias_build(probs_cpu):
     """Host Walker table, bit-identical to the reference's (alias_multinomial.py:39-72)."""

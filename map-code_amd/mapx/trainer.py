@@ -433,6 +433,8 @@ class Trainer:
         self.optimizer = None
         self.best_eval_auc, self.best_eval_step = 0, -1
         self.rank, self.world = parallel.rank(), parallel.world()
+        if self.world > 1 and getattr(model, "single_replica_only", None):
+            raise NotImplementedError(model.single_replica_only)
         self.use_graph = os.environ.get("MAPX_GRAPH", "1") != "0"
         self._graphs = {}
         self._splits = {}
