@@ -449,8 +449,7 @@ extern "C" int mapx_enc_grouped_fwd(const float* final_act, int64_t ld_final, in
   g.zero_out = zero_slots_opt;
   MAPX_REQUIRE(K % 8 == 0 && ld_final % 4 == 0 && ldw % 4 == 0 && (uintptr_t)final_act % 16 == 0 && (uintptr_t)W % 16 == 0,
                "enc_grouped_fwd: K %% 8 != 0 or operands not 16-byte aligned (use the dense encoder GEMM)");
-  static const bool h2 = [] { const char* e = getenv("MAPX_GEMM_H2"); return !e || atoi(e) != 0; }();
-  if (h2 && scale_opt && scale_opt->amax_a && scale_opt->amax_b) {      // both records: the two-piece fp16 arithmetic
+  if (gemm_h2_enabled() && scale_opt && scale_opt->amax_a && scale_opt->amax_b) {      // both records: the two-piece fp16 arithmetic
     g.amax_a = scale_opt->amax_a; g.amax_b = scale_opt->amax_b;
     MAPX_HIP(enc_grouped_fwd_h2_launch(g, cap_slots, stream));
   } else {
@@ -472,8 +471,7 @@ extern "C" int mapx_enc_grouped_dw(const float* dh_slots, const float* final_act
   g.gscale = gscale_opt;
   MAPX_REQUIRE(N % 8 == 0 && (uintptr_t)final_act % 16 == 0 && (uintptr_t)dh_slots % 16 == 0,
                "enc_grouped_dw: N %% 8 != 0 or operands not 16-byte aligned (use the dense encoder GEMM)");
-  static const bool h2 = [] { const char* e = getenv("MAPX_GEMM_H2"); return !e || atoi(e) != 0; }();
-  if (h2 && scale_opt && scale_opt->amax_a && scale_opt->amax_b) {
+  if (gemm_h2_enabled() && scale_opt && scale_opt->amax_a && scale_opt->amax_b) {
     g.amax_a = scale_opt->amax_a; g.amax_b = scale_opt->amax_b;
     MAPX_HIP(enc_grouped_dw_h2_launch(g, F, stream));
   } else {

@@ -35,9 +35,7 @@ __global__ void __launch_bounds__(512) gemm_grouped_h2_kernel(GroupedArgs a) {
   // (DW), the re-reads hit its L2.
   int f, kbeg, kend, n0 = 0, slot0 = 0;
   if (DW) {
-    const int nb = gridDim.x, per = nb / 8;
-    int lin = blockIdx.x;
-    if (lin < per * 8) lin = (lin % 8) * per + lin / 8;
+    const int lin = xcd_tile_order(blockIdx.x, gridDim.x);
     f = lin % a.F;                                   // column-slice-major: consecutive blocks share their columns
     n0 = (lin / a.F) * BN;
     kbeg = a.group_start[f];
@@ -184,12 +182,7 @@ static hipError_t launch_grouped_h2(const GroupedArgs& g, dim3 grid, hipStream_t
   using OpB = OperandH2<BN, 1, !DW, 512>;
   constexpr size_t lds = (size_t)2 * (OpA::LDS_ELEMS + OpB::LDS_ELEMS) * sizeof(f16_t);
   static_assert(lds >= 4 * 16 * 64 * sizeof(float) && lds <= 160 * 1024, "LDS budget");
-  auto* fn = &gemm_grouped_h2_kernel<DW>;
-  static hipError_t raised =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (raised != hipSuccess) return raised;
-  hipLaunchKernelGGL(fn, grid, dim3(512), lds, stream, g);
-  return hipSuccess;
+  return launch_dyn_lds<&gemm_grouped_h2_kernel<DW>, lds>(grid, dim3(512), stream, g);
 }
 
 hipError_t enc_grouped_fwd_h2_launch(const GroupedArgs& g, int cap_slots, hipStream_t stream) {

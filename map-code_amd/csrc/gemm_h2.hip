@@ -38,14 +38,7 @@ __host__ __device__ constexpr int h2_frag_order(int q, int what, int wnt) {
 template <int WR, int WC, int WMT, int WNT, bool A_KC, bool B_KC>
 __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_in) {
   constexpr int BM = 32 * WMT * WR, BN = 32 * WNT * WC, NT = 64 * WR * WC;
-  GemmX3Args a = a_in;
-  if (gridDim.z > 1) {                        // batched: problem blockIdx.z of gridDim.z equal-shaped ones
-    a.A = a_in.Az[blockIdx.z];
-    a.B = a_in.Bz[blockIdx.z];
-    a.C = a_in.Cz[blockIdx.z] + (int64_t)blockIdx.z * a_in.batch_slabs;
-    a.amax_a = a_in.amax_az[blockIdx.z];
-    a.amax_b = a_in.amax_bz[blockIdx.z];
-  }
+  const GemmX3Args a = dense_problem<true>(a_in);
   using OpA = OperandH2<BM, WMT, A_KC, NT>;
   using OpB = OperandH2<BN, WNT, B_KC, NT>;
   static_assert(!OpA::PARTIAL && !OpB::PARTIAL, "whole rounds of chunks");
@@ -65,8 +58,7 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
     ks = c % ns;
     lin = (c / ns) * (nb_tiles / (8 / ns)) + slot;
   } else {
-    const int per = nb_tiles / 8;
-    if (lin < per * 8) lin = (lin % 8) * per + lin / 8;      // XCD-aware tile order
+    lin = xcd_tile_order(lin, nb_tiles);
   }
   const int tm = lin / a.tiles_n, tn = lin % a.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -112,17 +104,8 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
   // fragments per k16 half, units before the first MFMA, slots that carry units (the last 4: the last chunk's two
   // LDS stores and two global loads)
   constexpr int kNM = 6 * WMT * WNT, kNCH = OpA::NV + OpB::NV, kU = 8 * kNCH, kFR = 2 * (WMT + WNT);
-#ifdef MAPX_H2_PRE
-  constexpr int kPre = MAPX_H2_PRE < kU - 1 ? MAPX_H2_PRE : kU - 1, kS = kNM - 4;      // experiment: units ahead of the MFMAs
-#else
   constexpr int kPre = kU >= 32 ? 4 : 2, kS = kNM - 4;
-#endif
   static_assert(kS >= 1 && kU > kPre, "slot budget");
-#ifdef MAPX_H2_ABLATE
-  constexpr int kDbg = MAPX_H2_ABLATE;       // 2 no cut / stores / loads, 4 no MFMAs, 16 no LDS stores (cut kept), 32 no global loads, 64 no cut VALU
-#else
-  constexpr int kDbg = 0;
-#endif
 
   // per chunk: element offset from the K-step's (uniform) operand base, out-of-range rows / columns of an edge tile
   // clamped to 0 (what they contribute lands in outputs the epilogue does not store), and the LDS offset of plane 0
@@ -149,14 +132,12 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
   do {                                                                                                 \
     constexpr bool isA_ = (c) < OpA::NV;                                                               \
     constexpr int i_ = isA_ ? (c) : (c) - OpA::NV, plane_ = isA_ ? OpA::PLANE : OpB::PLANE;            \
-    if (kDbg & 16) break;                                                                              \
     f16_t* const d_ = smem + ((CUR) ^ 1) * kBuf + (isA_ ? soffA[i_] : soffB[i_]) + (pl) * plane_;      \
     const uint32_t* const w_ = (pl) == 0 ? cH[(c) & 1] : cL[(c) & 1];                                  \
     *reinterpret_cast<uint4*>(d_) = make_uint4(w_[0], w_[1], w_[2], w_[3]);                            \
   } while (0)
 #define MAPX_H_WLOAD(CUR, c, hf)                                                                       \
   do {                                                                                                 \
-    if (kDbg & 32) break;                                                                              \
     constexpr bool isA_ = (c) < OpA::NV;                                                               \
     constexpr int i_ = isA_ ? (c) : (c) - OpA::NV;                                                     \
     const float* const q_ = (isA_ ? wA + goffA[i_] : wB + goffB[i_]) + 4 * (hf);                       \
@@ -171,16 +152,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
     constexpr int c_ = (u) / 8, pg_ = ((u) % 8) / 4, st_ = (u) % 4, m_ = (u) % 8;                      \
     constexpr bool isA_ = c_ < OpA::NV;                                                                \
     constexpr int i_ = isA_ ? c_ : c_ - OpA::NV;                                                       \
-    if ((kDbg & 128) && !isA_) {           /* ablation: operand B is not staged at all */              \
-      if (c_ == OpA::NV && m_ < 2) MAPX_H_WSTORE(CUR, (c_ > 0 ? c_ - 1 : 0), (m_ < 2 ? m_ : 0));       \
-      if (c_ == OpA::NV && m_ >= 2 && m_ < 4) MAPX_H_WLOAD(CUR, (c_ > 0 ? c_ - 1 : 0), (m_ >= 2 && m_ < 4 ? m_ - 2 : 0)); \
-      break;                                                                                           \
-    }                                                                                                  \
-    if (kDbg & 64) {        /* ablation: no VALU, the raw bits are stored */                           \
-      const float4 v_ = isA_ ? la[(CUR) ^ 1].r[i_][pg_] : lb[(CUR) ^ 1].r[i_][pg_];                    \
-      if (st_ == 0) { cH[c_ & 1][2 * pg_] = __float_as_uint(v_.x); cH[c_ & 1][2 * pg_ + 1] = __float_as_uint(v_.y);    \
-                      cL[c_ & 1][2 * pg_] = __float_as_uint(v_.z); cL[c_ & 1][2 * pg_ + 1] = __float_as_uint(v_.w); }  \
-    } else {                                                                                           \
     if (st_ == 0) {                                                                                    \
       const float4 v_ = isA_ ? la[(CUR) ^ 1].r[i_][pg_] : lb[(CUR) ^ 1].r[i_][pg_];                    \
       h2_unit0(v_.x, v_.y, v_.z, v_.w, isA_ ? sA : sB, cr);                                            \
@@ -188,7 +159,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
     if (st_ == 1) h2_unit1(cr, cH[c_ & 1][2 * pg_], cH[c_ & 1][2 * pg_ + 1]);                          \
     if (st_ == 2) h2_unit2(cr, cH[c_ & 1][2 * pg_], cH[c_ & 1][2 * pg_ + 1], k2048);                   \
     if (st_ == 3) h2_unit3(cr, k2048, cL[c_ & 1][2 * pg_], cL[c_ & 1][2 * pg_ + 1]);                   \
-    }                                                                                                  \
     if (c_ > 0 && m_ < 2) MAPX_H_WSTORE(CUR, (c_ > 0 ? c_ - 1 : 0), m_);                               \
     if (c_ > 0 && m_ >= 2 && m_ < 4) MAPX_H_WLOAD(CUR, (c_ > 0 ? c_ - 1 : 0), (m_ >= 2 && m_ < 4 ? m_ - 2 : 0)); \
   } while (0)
@@ -209,20 +179,16 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
     const float* const wA = a.A + (int64_t)wk_ * (A_KC ? 1 : a.lda);                                   \
     const float* const wB = a.B + (int64_t)wk_ * (B_KC ? 1 : a.ldb);                                   \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    if (!(kDbg & 2)) {                                                                                 \
-      unroll_seq([&](auto uc) __attribute__((always_inline)) {                                         \
-        MAPX_H_CUT_UNIT(CUR, decltype(uc)::value);                                                     \
-      }, std::make_integer_sequence<int, kPre>{});                                                     \
-    }                                                                                                  \
+    unroll_seq([&](auto uc) __attribute__((always_inline)) {                                           \
+      MAPX_H_CUT_UNIT(CUR, decltype(uc)::value);                                                       \
+    }, std::make_integer_sequence<int, kPre>{});                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     unroll_seq([&](auto zc) __attribute__((always_inline)) {                                           \
       constexpr int z = decltype(zc)::value;                                                           \
       constexpr int h = z / (kNM / 2), t3 = (z % (kNM / 2)) / 3, i = t3 / WNT, j = t3 % WNT, term = z % 3; \
-      if (!(kDbg & 4)) {                                                                               \
-        if (term == 0) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][1][i], fb[h][0][j], cor[i][j], 0, 0, 0); \
-        if (term == 1) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][0][i], fb[h][1][j], cor[i][j], 0, 0, 0); \
-        if (term == 2) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][0][i], fb[h][0][j], acc[i][j], 0, 0, 0); \
-      }                                                                                                \
+      if (term == 0) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][1][i], fb[h][0][j], cor[i][j], 0, 0, 0); \
+      if (term == 1) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][0][i], fb[h][1][j], cor[i][j], 0, 0, 0); \
+      if (term == 2) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[h][0][i], fb[h][0][j], acc[i][j], 0, 0, 0); \
       __builtin_amdgcn_sched_barrier(0);                                                               \
       if constexpr (z < kNM / 2) {            /* the second k16 half's fragments, under the first half's MFMAs */ \
         constexpr int q0 = z * kFR / (kNM / 2), q1 = (z + 1) * kFR / (kNM / 2);                        \
@@ -233,16 +199,14 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32h2_kernel(GemmX3Args a_i
           else fb[1][pl][t] = OpB::frag1(Bs_cur, pl, bbase, lane, 1, t);                               \
         }, std::make_integer_sequence<int, q1 - q0>{});                                                \
       }                                                                                                \
-      if (!(kDbg & 2)) {                                                                               \
-        if constexpr (z < kS) {                                                                        \
-          constexpr int u0 = kPre + z * (kU - kPre) / kS, u1 = kPre + (z + 1) * (kU - kPre) / kS;      \
-          unroll_seq([&](auto uc) __attribute__((always_inline)) {                                     \
-            MAPX_H_CUT_UNIT(CUR, u0 + decltype(uc)::value);                                            \
-          }, std::make_integer_sequence<int, u1 - u0>{});                                              \
-        }                                                                                              \
-        if constexpr (z >= kS && z < kS + 2) { if (!(kDbg & 128)) MAPX_H_WSTORE(CUR, kNCH - 1, (z >= kS && z < kS + 2 ? z - kS : 0)); } \
-        if constexpr (z >= kS + 2) { if (!(kDbg & 128)) MAPX_H_WLOAD(CUR, kNCH - 1, (z >= kS + 2 ? z - kS - 2 : 0)); } \
+      if constexpr (z < kS) {                                                                          \
+        constexpr int u0 = kPre + z * (kU - kPre) / kS, u1 = kPre + (z + 1) * (kU - kPre) / kS;        \
+        unroll_seq([&](auto uc) __attribute__((always_inline)) {                                       \
+          MAPX_H_CUT_UNIT(CUR, u0 + decltype(uc)::value);                                              \
+        }, std::make_integer_sequence<int, u1 - u0>{});                                                \
       }                                                                                                \
+      if constexpr (z >= kS && z < kS + 2) MAPX_H_WSTORE(CUR, kNCH - 1, (z >= kS && z < kS + 2 ? z - kS : 0)); \
+      if constexpr (z >= kS + 2) MAPX_H_WLOAD(CUR, kNCH - 1, (z >= kS + 2 ? z - kS - 2 : 0));          \
       __builtin_amdgcn_sched_barrier(0);                                                               \
     }, std::make_integer_sequence<int, kNM>{});                                                        \
     __syncthreads();                                                                                   \
@@ -284,13 +248,8 @@ static hipError_t launch_one_h2(const GemmX3Args& a, int nsplit, hipStream_t str
   constexpr size_t epi = ((size_t)BM * (BN + 4) + 4 * 256) * sizeof(float);     // the fp32 tile + the column-sum rows
   constexpr size_t lds = ops > epi ? ops : epi;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto* fn = &gemm_f32h2_kernel<WR, WC, WMT, WNT, A_KC, B_KC>;
-  static hipError_t raised = lds > 65536
-      ? hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-      : hipSuccess;
-  if (raised != hipSuccess) return raised;
-  hipLaunchKernelGGL(fn, dim3(a.tiles_m * a.tiles_n, nsplit, batch), dim3(NT), lds, stream, a);
-  return hipSuccess;
+  return launch_dyn_lds<&gemm_f32h2_kernel<WR, WC, WMT, WNT, A_KC, B_KC>, lds>(
+      dim3(a.tiles_m * a.tiles_n, nsplit, batch), dim3(NT), stream, a);
 }
 
 template <bool A_KC, bool B_KC>
@@ -317,8 +276,7 @@ static hipError_t launch_layout_h2(GemmX3Args& a, int tile, int nsplit, hipStrea
 // with its own kernels.
 bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, int nsplit,
                     int batch, hipStream_t stream, hipError_t* err) {
-  static const bool on = [] { const char* e = getenv("MAPX_GEMM_H2"); return !e || atoi(e) != 0; }();
-  if (!on || !vec) return false;
+  if (!gemm_h2_enabled() || !vec) return false;
   if (g.K - (int64_t)g.k_chunk * (nsplit - 1) <= kXBK) return false;        // every slab >= 2 K-steps
   if (tile != 0 && tile != 1 && tile != 2) tile = 3;
   if (!hinted && g.epi != MAPX_EPI_BWD_FUSED && g.epi != MAPX_EPI_RELU_MASK_COLSUM) {

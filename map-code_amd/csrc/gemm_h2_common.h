@@ -1,4 +1,4 @@
-// Shared pieces of the two-piece fp16 fp32-GEMM kernels (gemm_h2.hip, gemm_grouped_h2.hip): the cut of fp32 values into two
+// Shared pieces of the two-piece fp16 fp32-GEMM kernels (gemm_h2.hip, gemm_h2w.hip, gemm_grouped_h2.hip): the cut of fp32 values into two
 // fp16 planes and the operand class (global fp32 tile -> registers -> planes in LDS -> MFMA fragments).
 #pragma once
 #include "amax.h"
@@ -76,7 +76,7 @@ __device__ inline void cut2(const float (&x)[8], float s, uint4& hi, uint4& lo) 
 // 16-byte cells of a row XOR-swizzled by (row >> 2) & 3.  gemm_x3.hip's [row][32 + 8] rows serve the fragment reads
 // without conflicts (16 rows at one k offset) but not the stores: four lanes store one row's 64 bytes, and four rows
 // of 80 bytes wrap around the 256 bytes of the banks — two-way conflicts on every ds_write_b128, which measured as
-// THE cost of this K-step (tools/h2_ablate.sh: 1.09 us with the stores, 0.50 without, MFMAs alone 0.49).  Swizzled,
+// THE cost of this K-step (RESULTS.md section 3: 1.09 us with the stores, 0.50 without, MFMAs alone 0.49).  Swizzled,
 // four rows x 64 bytes are 256 consecutive bytes for the stores, and 16 rows at one k offset fall into 16 different
 // cells for the reads.
 template <int ROWS, int T, bool KC, int NT>

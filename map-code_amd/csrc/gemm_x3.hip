@@ -127,19 +127,14 @@ struct OperandX3 {
 template <int WR, int WC, int WMT, int WNT, bool A_KC, bool B_KC, bool VEC>
 __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_in) {
   constexpr int BM = 32 * WMT * WR, BN = 32 * WNT * WC, NT = 64 * WR * WC;
-  GemmX3Args a = a_in;
-  if (gridDim.z > 1) {                        // batched: problem blockIdx.z of gridDim.z equal-shaped ones
-    a.A = a_in.Az[blockIdx.z];
-    a.B = a_in.Bz[blockIdx.z];
-    a.C = a_in.Cz[blockIdx.z] + (int64_t)blockIdx.z * a_in.batch_slabs;
-  }
+  const GemmX3Args a = dense_problem<false>(a_in);
   using OpA = OperandX3<BM, WMT, A_KC, VEC, NT>;
   using OpB = OperandX3<BN, WNT, B_KC, VEC, NT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   bf16_t* const smem = reinterpret_cast<bf16_t*>(smem_raw);
   constexpr int kBuf = OpA::LDS_ELEMS + OpB::LDS_ELEMS;
 
-  const int nb = a.tiles_m * a.tiles_n;
+  const int nb_tiles = a.tiles_m * a.tiles_n;
   int lin = blockIdx.x, ks = blockIdx.y;
   if (a.xcd_slices) {
     // Split-K: workgroups reach the XCDs round-robin in launch order (x fastest), so XCD c = L % 8.  Dealing
@@ -147,12 +142,11 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
     // for the 1000 x 1000 x 4096 weight gradient, PMC: 138 MB per launch for 36 MB of operands and output).
     // Here XCD c takes k-slice c % nsplit of the tiles of group c / nsplit: 1/nsplit of both operands' k range,
     // the rows / columns of 1/(8/nsplit) of the tiles.
-    const int L = blockIdx.x + blockIdx.y * nb, c = L & 7, slot = L >> 3, ns = gridDim.y;
+    const int L = blockIdx.x + blockIdx.y * nb_tiles, c = L & 7, slot = L >> 3, ns = gridDim.y;
     ks = c % ns;
-    lin = (c / ns) * (nb / (8 / ns)) + slot;
+    lin = (c / ns) * (nb_tiles / (8 / ns)) + slot;
   } else {
-    const int per = nb / 8;
-    if (lin < per * 8) lin = (lin % 8) * per + lin / 8;      // XCD-aware tile order (see gemm.hip)
+    lin = xcd_tile_order(lin, nb_tiles);
   }
   const int tm = lin / a.tiles_n, tn = lin % a.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -227,14 +221,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
   __syncthreads();
   // K-step on LDS buffer CUR (= kt & 1, literal): at its start set CUR^1 holds tile kt+1 (landed),
   // set CUR holds tile kt+2 (in flight, issued one step ago)
-  // Timing experiments (tools/x3_ablate.sh): -DMAPX_X3_ABLATE=<bits> builds the K loop without some of its
-  // phases (1 no global loads, 2 no cut / LDS stores / loads, 4 no MFMAs; woven loop only: 8 B's cut
-  // skipped as if B came pre-split, 16 no LDS stores, 32 no global loads); results are then wrong.
-#ifdef MAPX_X3_ABLATE
-  constexpr int kDbg = MAPX_X3_ABLATE;       // compile-time: a run-time switch would put branches into the slots
-#else
-  constexpr int kDbg = 0;
-#endif
 #define MAPX_X_COMPUTE(CUR)                                                                            \
   do {                                                                                                 \
     const bf16_t* const As_cur = smem + (CUR) * kBuf;                                                  \
@@ -247,7 +233,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
       OpB::frags(Bs_cur, 1, bbase, lane, s2, bm);                                                      \
       OpA::frags(As_cur, 2, abase, lane, s2, al);                                                      \
       OpB::frags(Bs_cur, 2, bbase, lane, s2, bl);                                                      \
-      if (!(kDbg & 4))                                                                                \
       _Pragma("unroll") for (int i = 0; i < WMT; ++i)                                                  \
         _Pragma("unroll") for (int j = 0; j < WNT; ++j) {                                              \
           f32x16 c = cor[i][j];                 /* smallest terms first */                             \
@@ -263,20 +248,15 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
   } while (0)
 #define MAPX_X_STAGE(CUR, kt, STEADY, MASK)                                                            \
   do {                                                                                                 \
-    if (((STEADY) || (kt) + 1 < nk) && !(kDbg & 2)) MAPX_X_STORE((CUR) ^ 1, (CUR) ^ 1, MASK);         \
-    if (((STEADY) || (kt) + 3 < nk) && !(kDbg & 1)) MAPX_X_LOAD((CUR) ^ 1, (kt) + 3);                 \
+    if ((STEADY) || (kt) + 1 < nk) MAPX_X_STORE((CUR) ^ 1, (CUR) ^ 1, MASK);                           \
+    if ((STEADY) || (kt) + 3 < nk) MAPX_X_LOAD((CUR) ^ 1, (kt) + 3);                                   \
   } while (0)
-  // LATE (literal) swaps the two phases.  Tried for waves 4-7 (so one SIMD resident's MFMAs run beside
-  // the other's cut): 1.97 us per K-step against 1.90 without — the residents are not in lockstep here.
-#define MAPX_X_KSTEP(CUR, kt, STEADY, MASK, LATE)                                                      \
+  // (The stage before the compute — tried for waves 4-7, so that one SIMD resident's MFMAs run beside the other's
+  // cut — measured 1.97 us per K-step against 1.90: the residents are not in lockstep here.)
+#define MAPX_X_KSTEP(CUR, kt, STEADY, MASK)                                                            \
   do {                                                                                                 \
-    if (LATE) {                                                                                        \
-      MAPX_X_STAGE(CUR, kt, STEADY, MASK);                                                             \
-      MAPX_X_COMPUTE(CUR);                                                                             \
-    } else {                                                                                           \
-      MAPX_X_COMPUTE(CUR);                                                                             \
-      MAPX_X_STAGE(CUR, kt, STEADY, MASK);                                                             \
-    }                                                                                                  \
+    MAPX_X_COMPUTE(CUR);                                                                               \
+    MAPX_X_STAGE(CUR, kt, STEADY, MASK);                                                               \
     __syncthreads();                                                                                   \
   } while (0)
   // One wave per SIMD (kWeave: the 4-wave layouts): nothing but the ORDER of the wave's own instructions
@@ -297,7 +277,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
   // (only the K bound needs zeros, and the prologue has dealt with it).
 #define MAPX_X_WSTORE(CUR, c, pl)                                                                      \
   do {                                                                                                 \
-    if (kDbg & 16) break;                                                                              \
     constexpr bool isA_ = (c) < OpA::NV;                                                               \
     constexpr int i_ = isA_ ? (c) : (c) - OpA::NV, plane_ = isA_ ? OpA::PLANE : OpB::PLANE;            \
     bf16_t* const d_ = smem + ((CUR) ^ 1) * kBuf + (isA_ ? soffA[i_] : soffB[i_]) + (pl) * plane_;     \
@@ -306,7 +285,6 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
   } while (0)
 #define MAPX_X_WLOAD(CUR, c)                                                                           \
   do {                                                                                                 \
-    if (kDbg & 32) break;                                                                              \
     constexpr bool isA_ = (c) < OpA::NV;                                                               \
     constexpr int i_ = isA_ ? (c) : (c) - OpA::NV;                                                     \
     const float* const q_ = isA_ ? wA + goffA[i_] : wB + goffB[i_];                                    \
@@ -318,17 +296,12 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
       lb[(CUR) ^ 1].r[i_][1] = *reinterpret_cast<const float4*>(q_ + 4);                               \
     }                                                                                                  \
   } while (0)
-#define MAPX_X_CUT_UNIT(CUR, u)                                                                                  \
+#define MAPX_X_CUT_UNIT(CUR, u)                                                                        \
   do {                                                                                                 \
     constexpr int c_ = (u) / 12, e_ = ((u) % 12) / 3, st_ = (u) % 3;                                   \
     constexpr bool isA_ = c_ < OpA::NV;                                                                \
     constexpr int i_ = isA_ ? c_ : c_ - OpA::NV;                                                       \
-    if ((kDbg & 8) && !isA_) {      /* ablation: B as if it came pre-split (no VALU; wrong results) */   \
-      const float4 v_ = lb[(CUR) ^ 1].r[i_][e_ >> 1];                                                  \
-      if (st_ == 0) cH[c_ & 1][e_] = __float_as_uint(v_.x);                                            \
-      if (st_ == 1) cM[c_ & 1][e_] = __float_as_uint(v_.y);                                            \
-      if (st_ == 2) cL[c_ & 1][e_] = __float_as_uint(v_.z);                                            \
-    } else if (st_ == 0) {                                                                             \
+    if (st_ == 0) {                                                                                    \
       const float4 v_ = isA_ ? la[(CUR) ^ 1].r[i_][e_ >> 1] : lb[(CUR) ^ 1].r[i_][e_ >> 1];            \
       piece((e_ & 1) ? v_.z : v_.x, (e_ & 1) ? v_.w : v_.y, cH[c_ & 1][e_], cr0, cr1);                 \
     } else if (st_ == 1) {                                                                             \
@@ -347,14 +320,12 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
   unroll_seq([&](auto zc) __attribute__((always_inline)) {                                             \
     constexpr int z = decltype(zc)::value;                                                             \
     constexpr int h = z / (kNM / 2), t4 = (z % (kNM / 2)) / 6, i = t4 / WNT, j = t4 % WNT, term = z % 6; \
-    if (!(kDbg & 4)) {                                                                                 \
     if (term == 0) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][2][i], fb[h][0][j], cor[i][j], 0, 0, 0); \
     if (term == 1) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][0][i], fb[h][2][j], cor[i][j], 0, 0, 0); \
     if (term == 2) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][1][i], fb[h][1][j], cor[i][j], 0, 0, 0); \
     if (term == 3) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][1][i], fb[h][0][j], cor[i][j], 0, 0, 0); \
     if (term == 4) cor[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][0][i], fb[h][1][j], cor[i][j], 0, 0, 0); \
     if (term == 5) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[h][0][i], fb[h][0][j], acc[i][j], 0, 0, 0); \
-    }                                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     if constexpr (z < kNM / 2) {                                                                       \
       constexpr int q0 = z * kFR / (kNM / 2), q1 = (z + 1) * kFR / (kNM / 2);                          \
@@ -364,20 +335,18 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
         else fb[1][pl][t] = OpB::frag1(Bs_cur, pl, bbase, lane, 1, t);                                 \
       }                                                                                                \
     }                                                                                                  \
-    if (!(kDbg & 2)) {                                                                                 \
-      if constexpr (z < kS) {                                                                          \
-        constexpr int u0 = kPre + z * (kU - kPre) / kS, u1 = kPre + (z + 1) * (kU - kPre) / kS;        \
-        if constexpr (u0 < u1) MAPX_X_CUT_UNIT(CUR, u0);                                               \
-        if constexpr (u0 + 1 < u1) MAPX_X_CUT_UNIT(CUR, (u0 + 1 < u1 ? u0 + 1 : 0));                   \
-        if constexpr (u0 + 2 < u1) MAPX_X_CUT_UNIT(CUR, (u0 + 2 < u1 ? u0 + 2 : 0));                   \
-        static_assert(u1 - u0 <= 3, "at most three units of the cut per slot");                        \
-      }                                                                                                \
-      if constexpr (z >= kS && z < kS + 3) MAPX_X_WSTORE(CUR, kNCH - 1, (z >= kS && z < kS + 3 ? z - kS : 0)); \
-      if constexpr (z == kS + 3) MAPX_X_WLOAD(CUR, kNCH - 1);                                          \
+    if constexpr (z < kS) {                                                                            \
+      constexpr int u0 = kPre + z * (kU - kPre) / kS, u1 = kPre + (z + 1) * (kU - kPre) / kS;          \
+      if constexpr (u0 < u1) MAPX_X_CUT_UNIT(CUR, u0);                                                 \
+      if constexpr (u0 + 1 < u1) MAPX_X_CUT_UNIT(CUR, (u0 + 1 < u1 ? u0 + 1 : 0));                     \
+      if constexpr (u0 + 2 < u1) MAPX_X_CUT_UNIT(CUR, (u0 + 2 < u1 ? u0 + 2 : 0));                     \
+      static_assert(u1 - u0 <= 3, "at most three units of the cut per slot");                          \
     }                                                                                                  \
+    if constexpr (z >= kS && z < kS + 3) MAPX_X_WSTORE(CUR, kNCH - 1, (z >= kS && z < kS + 3 ? z - kS : 0)); \
+    if constexpr (z == kS + 3) MAPX_X_WLOAD(CUR, kNCH - 1);                                            \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
   }, std::make_integer_sequence<int, kNM>{})
-#define MAPX_X_KSTEP_WEAVE(CUR, kt)                                                                             \
+#define MAPX_X_KSTEP_WEAVE(CUR, kt)                                                                    \
   do {                                                                                                 \
     const bf16_t* const As_cur = smem + (CUR) * kBuf;                                                  \
     const bf16_t* const Bs_cur = As_cur + OpA::LDS_ELEMS;                                              \
@@ -394,31 +363,29 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
     const float* const wB = a.B + (int64_t)wk_ * (B_KC ? 1 : a.ldb);                                   \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     static_assert(kPre == 6 && kU >= 12, "the units before the first MFMA are written out");           \
-    if (!(kDbg & 2)) {                                                                                 \
-      MAPX_X_CUT_UNIT(CUR, 0); MAPX_X_CUT_UNIT(CUR, 1); MAPX_X_CUT_UNIT(CUR, 2);                       \
-      MAPX_X_CUT_UNIT(CUR, 3); MAPX_X_CUT_UNIT(CUR, 4); MAPX_X_CUT_UNIT(CUR, 5);                       \
-    }                                                                                                  \
+    MAPX_X_CUT_UNIT(CUR, 0); MAPX_X_CUT_UNIT(CUR, 1); MAPX_X_CUT_UNIT(CUR, 2);                         \
+    MAPX_X_CUT_UNIT(CUR, 3); MAPX_X_CUT_UNIT(CUR, 4); MAPX_X_CUT_UNIT(CUR, 5);                         \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    MAPX_X_WSLOTS(CUR);                                                                                             \
+    MAPX_X_WSLOTS(CUR);                                                                                \
     __syncthreads();                                                                                   \
   } while (0)
-#define MAPX_X_LOOPS(LATE)                                                                             \
+#define MAPX_X_LOOPS()                                                                                 \
   do {                                                                                                 \
     int kt = 0;                                                                                        \
     if (interior) {                                                                                    \
       for (; kt + 4 < nk; kt += 2) {                                                                   \
-        MAPX_X_KSTEP(0, kt, true, false, LATE);                                                        \
-        MAPX_X_KSTEP(1, kt + 1, true, false, LATE);                                                    \
+        MAPX_X_KSTEP(0, kt, true, false);                                                              \
+        MAPX_X_KSTEP(1, kt + 1, true, false);                                                          \
       }                                                                                                \
     } else {                                                                                           \
       for (; kt + 4 < nk; kt += 2) {                                                                   \
-        MAPX_X_KSTEP(0, kt, true, true, LATE);                                                         \
-        MAPX_X_KSTEP(1, kt + 1, true, true, LATE);                                                     \
+        MAPX_X_KSTEP(0, kt, true, true);                                                               \
+        MAPX_X_KSTEP(1, kt + 1, true, true);                                                           \
       }                                                                                                \
     }                                                                                                  \
     for (; kt < nk; kt += 2) {                                                                         \
-      MAPX_X_KSTEP(0, kt, false, true, LATE);                                                          \
-      if (kt + 1 < nk) MAPX_X_KSTEP(1, kt + 1, false, true, LATE);                                     \
+      MAPX_X_KSTEP(0, kt, false, true);                                                                \
+      if (kt + 1 < nk) MAPX_X_KSTEP(1, kt + 1, false, true);                                           \
     }                                                                                                  \
   } while (0)
   if constexpr (kWeave) {
@@ -459,7 +426,7 @@ __global__ void __launch_bounds__(64 * WR * WC) gemm_f32x3_kernel(GemmX3Args a_i
     }
     if (kt < nk) MAPX_X_KSTEP_WEAVE(0, kt);
   } else {
-    MAPX_X_LOOPS(false);
+    MAPX_X_LOOPS();
   }
 #undef MAPX_X_LOOPS
 #undef MAPX_X_KSTEP_WEAVE
@@ -494,13 +461,8 @@ static hipError_t launch_one_x3(const GemmX3Args& a, int nsplit, hipStream_t str
   constexpr size_t lds = (size_t)2 * (OpA::LDS_ELEMS + OpB::LDS_ELEMS) * sizeof(bf16_t);
   static_assert(lds >= (size_t)BM * (BN + 4) * sizeof(float), "the epilogue's fp32 tile must fit");
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto* fn = &gemm_f32x3_kernel<WR, WC, WMT, WNT, A_KC, B_KC, VEC>;
-  static hipError_t raised = lds > 65536
-      ? hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-      : hipSuccess;
-  if (raised != hipSuccess) return raised;
-  hipLaunchKernelGGL(fn, dim3(a.tiles_m * a.tiles_n, nsplit, batch), dim3(NT), lds, stream, a);
-  return hipSuccess;
+  return launch_dyn_lds<&gemm_f32x3_kernel<WR, WC, WMT, WNT, A_KC, B_KC, VEC>, lds>(
+      dim3(a.tiles_m * a.tiles_n, nsplit, batch), dim3(NT), stream, a);
 }
 
 // tile 2 (and 3): 128 x 128 by 8 waves (2 x 4, wave tile 64 x 32; 4 waves of 64 x 64 would need 256
@@ -689,9 +651,7 @@ __global__ void __launch_bounds__(512) gemm_grouped_x3_kernel(GroupedArgs a) {
   // (DW), the re-reads hit its L2.
   int f, kbeg, kend, n0 = 0, slot0 = 0;
   if (DW) {
-    const int nb = gridDim.x, per = nb / 8;
-    int lin = blockIdx.x;
-    if (lin < per * 8) lin = (lin % 8) * per + lin / 8;
+    const int lin = xcd_tile_order(blockIdx.x, gridDim.x);
     f = lin % a.F;                                   // column-slice-major: consecutive blocks share their columns
     n0 = (lin / a.F) * BN;
     kbeg = a.group_start[f];
@@ -845,12 +805,7 @@ static hipError_t launch_grouped_x3(const GroupedArgs& g, dim3 grid, hipStream_t
   using OpB = OperandX3<BN, 1, !DW, true, 512>;
   constexpr size_t lds = (size_t)2 * (OpA::LDS_ELEMS + OpB::LDS_ELEMS) * sizeof(bf16_t);
   static_assert(lds >= 4 * 16 * 64 * sizeof(float) && lds <= 160 * 1024, "LDS budget");
-  auto* fn = &gemm_grouped_x3_kernel<DW>;
-  static hipError_t raised =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (raised != hipSuccess) return raised;
-  hipLaunchKernelGGL(fn, grid, dim3(512), lds, stream, g);
-  return hipSuccess;
+  return launch_dyn_lds<&gemm_grouped_x3_kernel<DW>, lds>(grid, dim3(512), stream, g);
 }
 
 hipError_t enc_grouped_fwd_x3_launch(const GroupedArgs& g, int cap_slots, hipStream_t stream) {

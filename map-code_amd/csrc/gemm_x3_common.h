@@ -4,6 +4,7 @@
 #include "../../include/mapx_hip.h"
 #include "amax.h"
 #include "common.h"
+#include <stdlib.h>
 #include <utility>
 
 namespace mapx {
@@ -78,6 +79,50 @@ struct GemmX3Extra {
 #define MAPX_EPI_BWD_FUSED 7        // internal to the library: reached through mapx_gemm_f32_bwd_fused only
 
 constexpr int kXBK = 32;
+
+// "Is the two-piece fp16 arithmetic on?" (MAPX_GEMM_H2, default 1; read once)
+inline bool gemm_h2_enabled() {
+  static const bool on = [] { const char* e = getenv("MAPX_GEMM_H2"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
+// Launch Kernel with LDS bytes of dynamic shared memory; above the 64 KB default its limit is raised first, once per
+// kernel (one instantiation, hence one `raised`, per kernel and size).
+template <auto Kernel, size_t LDS, class... Args>
+inline hipError_t launch_dyn_lds(dim3 grid, dim3 block, hipStream_t stream, const Args&... args) {
+  static const hipError_t raised =
+      LDS > 65536 ? hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS)
+                  : hipSuccess;
+  if (raised != hipSuccess) return raised;
+  hipLaunchKernelGGL(Kernel, grid, block, LDS, stream, args...);
+  return hipSuccess;
+}
+
+// XCD-aware tile order: workgroups reach the 8 XCDs round-robin in launch order, so block b of nb takes tile
+// (b % 8) * (nb / 8) + b / 8 — every XCD (its own 4 MB L2) a contiguous eighth of the tiles (see gemm.hip).
+__device__ inline int xcd_tile_order(int lin, int nb) {
+  const int per = nb / 8;
+  if (lin < per * 8) lin = (lin % 8) * per + lin / 8;
+  return lin;
+}
+
+// The dense kernels' batched launch: the argument block of problem blockIdx.z (H2: with its operands' magnitude
+// records).
+template <bool H2>
+__device__ inline GemmX3Args dense_problem(const GemmX3Args& a_in) {
+  GemmX3Args a = a_in;
+  if (gridDim.z > 1) {                        // batched: problem blockIdx.z of gridDim.z equal-shaped ones
+    a.A = a_in.Az[blockIdx.z];
+    a.B = a_in.Bz[blockIdx.z];
+    a.C = a_in.Cz[blockIdx.z] + (int64_t)blockIdx.z * a_in.batch_slabs;
+    if (H2) {
+      a.amax_a = a_in.amax_az[blockIdx.z];
+      a.amax_b = a_in.amax_bz[blockIdx.z];
+    }
+  }
+  return a;
+}
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): a loop whose index is a constant expression
 template <class F, int... Z>
@@ -389,11 +434,11 @@ __device__ inline void epilogue_dispatch(const GemmX3Args& a, float* __restrict_
       case MAPX_EPI_BIAS_CROSS: epilogue_rows_x3_vec<MAPX_EPI_BIAS_CROSS, BM, BN, NT>(a, C, tile, m0, n0); break;
       case MAPX_EPI_ADD: epilogue_rows_x3_vec<MAPX_EPI_ADD, BM, BN, NT>(a, C, tile, m0, n0); break;
       case MAPX_EPI_RELU_MASK: epilogue_rows_x3_vec<MAPX_EPI_RELU_MASK, BM, BN, NT>(a, C, tile, m0, n0); break;
-      case MAPX_EPI_RELU_MASK_COLSUM:       // (launchers: tiles of 128 rows, or 64 x 256)
-        if constexpr (BM == 128 || BN == 256) epilogue_rows_x3_vec<MAPX_EPI_RELU_MASK_COLSUM, BM, BN, NT>(a, C, tile, m0, n0);
+      case MAPX_EPI_RELU_MASK_COLSUM:       // (launchers: tiles of 128 rows)
+        if constexpr (BM == 128) epilogue_rows_x3_vec<MAPX_EPI_RELU_MASK_COLSUM, BM, BN, NT>(a, C, tile, m0, n0);
         break;
       case MAPX_EPI_BWD_FUSED:
-        if constexpr (BM == 128 || BN == 256) epilogue_bwd_fused<BM, BN, NT>(a, C, tile, m0, n0);
+        if constexpr (BM == 128) epilogue_bwd_fused<BM, BN, NT>(a, C, tile, m0, n0);
         break;
       default: epilogue_rows_x3_vec<MAPX_EPI_NONE, BM, BN, NT>(a, C, tile, m0, n0); break;
     }

@@ -36,7 +36,7 @@ def run(a_kc, b_kc, M, N, K, epi=EPI_NONE, nsplit=1, tile=-1):
 
 if __name__ == "__main__" and not (len(sys.argv) > 1 and sys.argv[1] == "fixed"):
     print("mode", os.environ.get("MAPX_GEMM", "x3"))
-    if len(sys.argv) > 1 and sys.argv[1] == "ablate":       # one line per 128 x 128 layout; see tools/x3_ablate.sh
+    if len(sys.argv) > 1 and sys.argv[1] == "ablate":       # one line per 128 x 128 layout
         for tile in (2, 3):
             us, _ = run(True, True, 4096, 1000, 4096, epi=EPI_BIAS_RELU, tile=tile)
             print(f"  tile {tile}: {us:7.1f} us   {(us - 10) / 128:5.2f} us/K-step")
