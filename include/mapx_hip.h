@@ -604,6 +604,38 @@ int mapx_emb_gather_fwd_bf16(const int64_t* ids, int64_t n, const float* table, 
 int mapx_seg_reduce_rows_bf16(int64_t n, const int32_t* perm, const int32_t* rank, const int32_t* seg_start,
                               const mapx_bf16* src, const mapx_bf16* src2_opt, int W, float* out, void* ws,
                               size_t ws_bytes, int32_t* zeroed_counter_opt, hipStream_t stream);
+/* mapx_seg_reduce_rows_extra over bf16 source rows (ld_src in bf16 elements, % 4 == 0): the extra scalar per batch
+ * row, the sums and both outputs stay fp32; the plan's fixed order, bit-reproducible like mapx_seg_reduce_rows_bf16.
+ * (Added inside ABI 48 with the entries below: purely additive.) */
+int mapx_seg_reduce_rows_extra_bf16(int64_t n, const int32_t* perm, const int32_t* rank, const int32_t* seg_start,
+                                    const mapx_bf16* src, int W, int64_t ld_src, const float* extra, int group,
+                                    int64_t extra_stride, float* out, float* out_extra, void* ws, size_t ws_bytes,
+                                    int32_t* zeroed_counter_opt, hipStream_t stream);
+/* mapx_fm_fwd / mapx_fm_bwd on bf16 rows: x [B,F,E] bf16 (the bf16 gather's output), out [B] and s [B,E] fp32;
+ * backward g [B] and s fp32, dx bf16 = round(g (s - x)), rounded once.  E in {8,16,32,64} (the bf16 gather needs
+ * E % 8 == 0: E = 4 returns MAPX_EINVAL).  Sums in fp32, in mapx_fm_fwd's order. */
+int mapx_fm_fwd_bf16(const mapx_bf16* x, int64_t B, int F, int E, float* out, float* s, hipStream_t stream);
+int mapx_fm_bwd_bf16(const float* g, const float* s, const mapx_bf16* x, int64_t B, int F, int E, mapx_bf16* dx,
+                     hipStream_t stream);
+/* bf16 I/O forms of the AutoInt attention core: the kernels of mapx_attn_fwd / _bwd / _drop_fwd / _drop_bwd on bf16
+ * elements.  q, k, v, d_o are read as bf16 and widened into the same fp32 LDS staging; logits, softmax, P V and every
+ * backward sum are the fp32 arithmetic of the fp32 entries; o, dq, dk, dv are rounded to nearest even once where they
+ * are stored; p / probs [G,F,F] stays fp32 (state of the fused node, not an activation).  Same group layout (group g =
+ * elements [g*F*A, (g+1)*F*A), 2-byte aligned only when F*A is odd: any F, A <= 64 is taken), same two-groups-per-wave
+ * choice at F <= 32, same LDS, same Philox masks (mapx_attn_dropout_masks serves both element types); p = 0 runs the
+ * plain bf16 kernels.  No atomics. */
+int mapx_attn_fwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, int64_t G, int F, int A, int scaled,
+                       mapx_bf16* o, float* p, hipStream_t stream);
+int mapx_attn_bwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, const float* p, const mapx_bf16* d_o,
+                       int64_t G, int F, int A, int scaled, mapx_bf16* dq, mapx_bf16* dk, mapx_bf16* dv,
+                       hipStream_t stream);
+int mapx_attn_drop_fwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, int64_t G, int F, int A,
+                            int scaled, float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
+                            const int32_t* offset_dev_opt, mapx_bf16* o, float* probs, hipStream_t stream);
+int mapx_attn_drop_bwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, const float* probs,
+                            const mapx_bf16* d_o, int64_t G, int F, int A, int scaled, float p, uint64_t seed,
+                            uint64_t offset_p, uint64_t offset_o, const int32_t* offset_dev_opt, mapx_bf16* dq,
+                            mapx_bf16* dk, mapx_bf16* dv, hipStream_t stream);
 /* bf16 counterparts of mapx_colsum / mapx_relu_mask_colsum / mapx_cross_bwd_pre_colsum /
  * mapx_relu_mask: activations and their gradients bf16, column sums (bias gradients) and the running
  * dL/dX0 of the cross tower fp32.  Any N and leading dimensions.  out / db == NULL: the chunk rows stay in `ws`

@@ -17,12 +17,99 @@ namespace mapx {
 
 constexpr int kAttnMaxF = 64, kAttnMaxA = 64;   // one lane per field; LDS budget
 
+// Element type T of q, k, v, o, dO, dq, dk, dv: float, or bf16_t (bf16 compute mode).  Only the global
+// loads and stores differ: a load widens to fp32 into the LDS staging (which stays fp32: the same LDS budget), all
+// arithmetic is the fp32 code below, a store rounds to nearest even once.  P is fp32 for both.
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+// Elements per staging load.  A group starts at element g*F*A, which is only 2-byte aligned when F*A is odd: 8-byte
+// loads when F*A % 4 == 0, 4-byte ones when it is even, single elements otherwise (A = 7, A = 1 with odd F).
+template <class T>
+__device__ inline int attn_vec(int FA, const void* a, const void* b, const void* c, const void* d) {
+  if constexpr (sizeof(T) == 4) {
+    return 1;
+  } else {
+    const uintptr_t bits = (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d;
+    return (FA % 4 == 0 && bits % 8 == 0) ? 4 : ((FA % 2 == 0 && bits % 4 == 0) ? 2 : 1);
+  }
+}
+
+template <int V, class T>
+__device__ inline void attn_load(const T* __restrict__ p, float (&f)[V]) {
+  if constexpr (V == 4) {
+    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
+    f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2]; f[3] = (float)v[3];
+  } else if constexpr (V == 2) {
+    const bf16x2_t v = *reinterpret_cast<const bf16x2_t*>(p);
+    f[0] = (float)v[0]; f[1] = (float)v[1];
+  } else {
+    f[0] = (float)p[0];
+  }
+}
+
+// Stages NT tensors' [F*A] elements of one group into their padded LDS rows [F][LD], V elements per load.
+template <int V, int NT, class T>
+__device__ inline void attn_stage_v(const T* const (&src)[NT], float* const (&dst)[NT], int64_t base, int FA, int A,
+                                    int LD, int li, int LW) {
+  for (int t = V * li; t < FA; t += V * LW) {
+    float f[NT][V];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) attn_load<V>(src[n] + base + t, f[n]);
+    int r = t / A, c = t - r * A;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+#pragma unroll
+      for (int n = 0; n < NT; ++n) dst[n][r * LD + c] = f[n][e];
+      if (++c == A) { c = 0; ++r; }
+    }
+  }
+}
+
+template <int NT, class T>
+__device__ inline void attn_stage(const T* const (&src)[NT], float* const (&dst)[NT], int64_t base, int FA, int A,
+                                  int LD, int li, int LW, int vec) {
+  if constexpr (sizeof(T) == 4) {
+    attn_stage_v<1>(src, dst, base, FA, A, LD, li, LW);
+  } else {
+    if (vec == 4) attn_stage_v<4>(src, dst, base, FA, A, LD, li, LW);
+    else if (vec == 2) attn_stage_v<2>(src, dst, base, FA, A, LD, li, LW);
+    else attn_stage_v<1>(src, dst, base, FA, A, LD, li, LW);
+  }
+}
+
+// One lane's output row [A]: put(a, v) for a = 0 .. A-1 in order.  bf16 with an even A on 4-byte aligned rows: the
+// even column waits in a register for the odd one and both leave as one 4-byte store.
+template <class T>
+struct AttnRowOut {
+  T* p;
+  bool pair;
+  float held;
+  __device__ inline AttnRowOut(T* row, int A) : p(row), pair(sizeof(T) == 2 && A % 2 == 0 && (uintptr_t)row % 4 == 0), held(0.f) {}
+  __device__ inline void put(int a, float v) {
+    if constexpr (sizeof(T) == 4) {
+      p[a] = v;
+    } else {
+      if (!pair) {
+        p[a] = (T)v;                                   // v_cvt_pk_bf16_f32: round to nearest even
+      } else if (a & 1) {
+        bf16x2_t o;
+        o[0] = (bf16_t)held; o[1] = (bf16_t)v;
+        *reinterpret_cast<bf16x2_t*>(p + a - 1) = o;
+      } else {
+        held = v;
+      }
+    }
+  }
+};
+
 // GPW groups per wave: with F <= 32 fields a wave takes TWO groups, one per half (lane & 31 = the query row): the
 // one-group form left 41 of 64 lanes idle at Avazu's 23 fields.
-template <int GPW>
-__global__ void __launch_bounds__(64) attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                      const float* __restrict__ v, int64_t G, int F, int A,
-                                                      float inv_scale, float* __restrict__ o, float* __restrict__ p) {
+template <int GPW, class T>
+__global__ void __launch_bounds__(64) attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                      const T* __restrict__ v, int64_t G, int F, int A,
+                                                      float inv_scale, T* __restrict__ o, float* __restrict__ p) {
   extern __shared__ float sm[];                 // per group: Q, K, V [F][A+1]; P [F][F+1]
   constexpr int LW = 64 / GPW;                  // lanes per group
   const int LD = A + 1, LF = F + 1;
@@ -34,11 +121,10 @@ __global__ void __launch_bounds__(64) attn_fwd_kernel(const float* __restrict__ 
   const int64_t g = (int64_t)blockIdx.x * GPW + half;
   const bool have = g < G;
   const int64_t base = g * F * A;
-  for (int t = li; have && t < F * A; t += LW) {
-    const int r = t / A, c = t - r * A;
-    Qs[r * LD + c] = q[base + t];
-    Ks[r * LD + c] = k[base + t];
-    Vs[r * LD + c] = v[base + t];
+  if (have) {
+    const T* const src[3] = {q, k, v};
+    float* const dst[3] = {Qs, Ks, Vs};
+    attn_stage(src, dst, base, F * A, A, LD, li, LW, attn_vec<T>(F * A, q, k, v, nullptr));
   }
   __syncthreads();
   const int i = li;
@@ -59,10 +145,11 @@ __global__ void __launch_bounds__(64) attn_fwd_kernel(const float* __restrict__ 
     }
     const float rden = 1.f / den;
     for (int j = 0; j < F; ++j) Ps[i * LF + j] *= rden;
+    AttnRowOut<T> orow(o + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       float acc = 0.f;
       for (int j = 0; j < F; ++j) acc += Ps[i * LF + j] * Vs[j * LD + a];
-      o[base + i * A + a] = acc;
+      orow.put(a, acc);
     }
   }
   __syncthreads();
@@ -73,12 +160,12 @@ __global__ void __launch_bounds__(64) attn_fwd_kernel(const float* __restrict__ 
 }
 
 // dV = P^T dO;  dP = dO V^T;  dS = P (dP - rowsum(P dP)) * inv_scale;  dQ = dS K;  dK = dS^T Q
-template <int GPW>
-__global__ void __launch_bounds__(64) attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                      const float* __restrict__ v, const float* __restrict__ p,
-                                                      const float* __restrict__ d_o, int64_t G, int F, int A,
-                                                      float inv_scale, float* __restrict__ dq,
-                                                      float* __restrict__ dk, float* __restrict__ dv) {
+template <int GPW, class T>
+__global__ void __launch_bounds__(64) attn_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                      const T* __restrict__ v, const float* __restrict__ p,
+                                                      const T* __restrict__ d_o, int64_t G, int F, int A,
+                                                      float inv_scale, T* __restrict__ dq,
+                                                      T* __restrict__ dk, T* __restrict__ dv) {
   extern __shared__ float sm[];                 // per group: K, V, Q, dO [F][A+1] each; dS [F][F+1]; P [F][F+1]
   constexpr int LW = 64 / GPW;
   const int LD = A + 1, LF = F + 1;
@@ -92,12 +179,10 @@ __global__ void __launch_bounds__(64) attn_bwd_kernel(const float* __restrict__ 
   const int64_t g = (int64_t)blockIdx.x * GPW + half;
   const bool have = g < G;
   const int64_t base = g * F * A;
-  for (int t = li; have && t < F * A; t += LW) {
-    const int r = t / A, c = t - r * A;
-    Ks[r * LD + c] = k[base + t];
-    Vs[r * LD + c] = v[base + t];
-    Qs[r * LD + c] = q[base + t];
-    Ds[r * LD + c] = d_o[base + t];
+  if (have) {
+    const T* const src[4] = {k, v, q, d_o};
+    float* const dst[4] = {Ks, Vs, Qs, Ds};
+    attn_stage(src, dst, base, F * A, A, LD, li, LW, attn_vec<T>(F * A, q, k, v, d_o));
   }
   for (int t = li; have && t < F * F; t += LW) {
     const int r = t / F, c = t - r * F;
@@ -114,22 +199,24 @@ __global__ void __launch_bounds__(64) attn_bwd_kernel(const float* __restrict__ 
       dot += Ps[i * LF + j] * dp;
     }
     for (int j = 0; j < F; ++j) dS[i * LF + j] = Ps[i * LF + j] * (dS[i * LF + j] - dot) * inv_scale;
+    AttnRowOut<T> qrow(dq + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       float s = 0.f;
       for (int j = 0; j < F; ++j) s += dS[i * LF + j] * Ks[j * LD + a];
-      dq[base + i * A + a] = s;
+      qrow.put(a, s);
     }
   }
   __syncthreads();
   if (have && i < F) {                           // lane i now owns key / value row i: column sums over queries
+    AttnRowOut<T> krow(dk + base + i * A, A), vrow(dv + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       float sk = 0.f, sv = 0.f;
       for (int r = 0; r < F; ++r) {
         sk += dS[r * LF + i] * Qs[r * LD + a];
         sv += Ps[r * LF + i] * Ds[r * LD + a];
       }
-      dk[base + i * A + a] = sk;
-      dv[base + i * A + a] = sv;
+      krow.put(a, sk);
+      vrow.put(a, sv);
     }
   }
 }
@@ -167,12 +254,12 @@ __device__ inline uint32_t attn_keep_o(const AttnDrop& d, int64_t row, int c) {
   return attn_keep_bits(philox4x32_10(d.seed, (uint64_t)(row * d.na4 + c), d.off_o), d.thr);
 }
 
-template <int GPW>
-__global__ void __launch_bounds__(64) attn_drop_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                           const float* __restrict__ v, int64_t G, int F, int A,
+template <int GPW, class T>
+__global__ void __launch_bounds__(64) attn_drop_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                           const T* __restrict__ v, int64_t G, int F, int A,
                                                            float inv_scale, float p, uint64_t seed, uint64_t offset_p,
                                                            uint64_t offset_o, const int32_t* __restrict__ offset_dev,
-                                                           float* __restrict__ o, float* __restrict__ probs) {
+                                                           T* __restrict__ o, float* __restrict__ probs) {
   extern __shared__ float sm[];                 // per group: Q, K, V [F][A+1]; P (then P~) [F][F+1]
   constexpr int LW = 64 / GPW;
   const int LD = A + 1, LF = F + 1;
@@ -184,11 +271,10 @@ __global__ void __launch_bounds__(64) attn_drop_fwd_kernel(const float* __restri
   const int64_t g = (int64_t)blockIdx.x * GPW + half;
   const bool have = g < G;
   const int64_t base = g * F * A;
-  for (int t = li; have && t < F * A; t += LW) {
-    const int r = t / A, c = t - r * A;
-    Qs[r * LD + c] = q[base + t];
-    Ks[r * LD + c] = k[base + t];
-    Vs[r * LD + c] = v[base + t];
+  if (have) {
+    const T* const src[3] = {q, k, v};
+    float* const dst[3] = {Qs, Ks, Vs};
+    attn_stage(src, dst, base, F * A, A, LD, li, LW, attn_vec<T>(F * A, q, k, v, nullptr));
   }
   __syncthreads();
   const int i = li;
@@ -224,25 +310,26 @@ __global__ void __launch_bounds__(64) attn_drop_fwd_kernel(const float* __restri
       if ((j & 3) == 0) keep = attn_keep_p(d, row, j >> 2);
       Ps[i * LF + j] = ((keep >> (j & 3)) & 1u) ? Ps[i * LF + j] * d.rkeep : 0.f;
     }
+    AttnRowOut<T> orow(o + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       if ((a & 3) == 0) keep = attn_keep_o(d, row, a >> 2);
       float acc = 0.f;
       for (int j = 0; j < F; ++j) acc += Ps[i * LF + j] * Vs[j * LD + a];
-      o[base + i * A + a] = ((keep >> (a & 3)) & 1u) ? acc * d.rkeep : 0.f;
+      orow.put(a, ((keep >> (a & 3)) & 1u) ? acc * d.rkeep : 0.f);
     }
   }
 }
 
 // dO' = dO m_o / (1-p);  dV = P~^T dO';  dP = (dO' V^T) m_p / (1-p);  dS = P (dP - rowsum(P dP)) * inv_scale;
 // dQ = dS K;  dK = dS^T Q
-template <int GPW>
-__global__ void __launch_bounds__(64) attn_drop_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                           const float* __restrict__ v, const float* __restrict__ probs,
-                                                           const float* __restrict__ d_o, int64_t G, int F, int A,
+template <int GPW, class T>
+__global__ void __launch_bounds__(64) attn_drop_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                           const T* __restrict__ v, const float* __restrict__ probs,
+                                                           const T* __restrict__ d_o, int64_t G, int F, int A,
                                                            float inv_scale, float p, uint64_t seed, uint64_t offset_p,
                                                            uint64_t offset_o, const int32_t* __restrict__ offset_dev,
-                                                           float* __restrict__ dq, float* __restrict__ dk,
-                                                           float* __restrict__ dv) {
+                                                           T* __restrict__ dq, T* __restrict__ dk,
+                                                           T* __restrict__ dv) {
   extern __shared__ float sm[];                 // per group: K, V, Q, dO' [F][A+1] each; dS [F][F+1]; P, then P~ [F][F+1]
   constexpr int LW = 64 / GPW;
   const int LD = A + 1, LF = F + 1;
@@ -257,18 +344,17 @@ __global__ void __launch_bounds__(64) attn_drop_bwd_kernel(const float* __restri
   const bool have = g < G;
   const int64_t base = g * F * A;
   const AttnDrop d = attn_drop_setup(p, seed, offset_p, offset_o, offset_dev, F, A);
-  for (int t = li; have && t < F * A; t += LW) {
-    const int r = t / A, c = t - r * A;
-    Ks[r * LD + c] = k[base + t];
-    Vs[r * LD + c] = v[base + t];
-    Qs[r * LD + c] = q[base + t];
+  if (have) {
+    const T* const src[3] = {k, v, q};
+    float* const dst[3] = {Ks, Vs, Qs};
+    attn_stage(src, dst, base, F * A, A, LD, li, LW, attn_vec<T>(F * A, q, k, v, nullptr));
   }
   for (int t = li; have && t < F * d.na4; t += LW) {     // dO' staged by the O mask's draws: 4 outputs of a row each
     const int r = t / d.na4, c4 = t - r * d.na4;
     const uint32_t keep = attn_keep_o(d, g * F + r, c4);
     for (int e = 0; e < 4; ++e) {
       const int c = 4 * c4 + e;
-      if (c < A) Ds[r * LD + c] = ((keep >> e) & 1u) ? d_o[base + r * A + c] * d.rkeep : 0.f;
+      if (c < A) Ds[r * LD + c] = ((keep >> e) & 1u) ? (float)d_o[base + r * A + c] * d.rkeep : 0.f;
     }
   }
   for (int t = li; have && t < F * F; t += LW) {
@@ -294,22 +380,24 @@ __global__ void __launch_bounds__(64) attn_drop_bwd_kernel(const float* __restri
       dS[i * LF + j] = pij * (dS[i * LF + j] - dot) * inv_scale;
       Ps[i * LF + j] = ((keep >> j) & 1ull) ? pij * d.rkeep : 0.f;      // P~ for dV below
     }
+    AttnRowOut<T> qrow(dq + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       float s = 0.f;
       for (int j = 0; j < F; ++j) s += dS[i * LF + j] * Ks[j * LD + a];
-      dq[base + i * A + a] = s;
+      qrow.put(a, s);
     }
   }
   __syncthreads();
   if (have && i < F) {                           // lane i now owns key / value row i: column sums over queries
+    AttnRowOut<T> krow(dk + base + i * A, A), vrow(dv + base + i * A, A);
     for (int a = 0; a < A; ++a) {
       float sk = 0.f, sv = 0.f;
       for (int r = 0; r < F; ++r) {
         sk += dS[r * LF + i] * Qs[r * LD + a];
         sv += Ps[r * LF + i] * Ds[r * LD + a];
       }
-      dk[base + i * A + a] = sk;
-      dv[base + i * A + a] = sv;
+      krow.put(a, sk);
+      vrow.put(a, sv);
     }
   }
 }
@@ -336,12 +424,13 @@ __global__ void __launch_bounds__(256) attn_mask_kernel(int64_t rows, int F, int
 }
 
 // F = A = 64 needs 100 KB of dynamic LDS in backward: above the 64 KB default, inside the CU's 160 KB
+template <class T>
 static hipError_t raise_lds_limit() {
   static hipError_t done = [] {
-    for (const void* fn : {reinterpret_cast<const void*>(&attn_fwd_kernel<1>), reinterpret_cast<const void*>(&attn_fwd_kernel<2>),
-                           reinterpret_cast<const void*>(&attn_bwd_kernel<1>), reinterpret_cast<const void*>(&attn_bwd_kernel<2>),
-                           reinterpret_cast<const void*>(&attn_drop_fwd_kernel<1>), reinterpret_cast<const void*>(&attn_drop_fwd_kernel<2>),
-                           reinterpret_cast<const void*>(&attn_drop_bwd_kernel<1>), reinterpret_cast<const void*>(&attn_drop_bwd_kernel<2>)}) {
+    for (const void* fn : {reinterpret_cast<const void*>(&attn_fwd_kernel<1, T>), reinterpret_cast<const void*>(&attn_fwd_kernel<2, T>),
+                           reinterpret_cast<const void*>(&attn_bwd_kernel<1, T>), reinterpret_cast<const void*>(&attn_bwd_kernel<2, T>),
+                           reinterpret_cast<const void*>(&attn_drop_fwd_kernel<1, T>), reinterpret_cast<const void*>(&attn_drop_fwd_kernel<2, T>),
+                           reinterpret_cast<const void*>(&attn_drop_bwd_kernel<1, T>), reinterpret_cast<const void*>(&attn_drop_bwd_kernel<2, T>)}) {
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       if (e != hipSuccess) return e;
     }
@@ -350,100 +439,159 @@ static hipError_t raise_lds_limit() {
   return done;
 }
 
-}  // namespace mapx
-
-extern "C" int mapx_attn_fwd(const float* q, const float* k, const float* v, int64_t G, int F, int A, int scaled,
-                             float* o, float* p, hipStream_t stream) {
-  using namespace mapx;
+template <class T>
+static int attn_fwd_launch(const char* what, const T* q, const T* k, const T* v, int64_t G, int F, int A, int scaled,
+                           T* o, float* p, hipStream_t stream) {
   MAPX_REQUIRE(G >= 0 && F >= 1 && F <= kAttnMaxF && A >= 1 && A <= kAttnMaxA,
-               "attn_fwd: F <= %d fields, attention size <= %d", kAttnMaxF, kAttnMaxA);
+               "%s: F <= %d fields, attention size <= %d", what, kAttnMaxF, kAttnMaxA);
   if (G == 0) return MAPX_OK;
-  MAPX_REQUIRE(q && k && v && o && p, "attn_fwd: null pointer");
+  MAPX_REQUIRE(q && k && v && o && p, "%s: null pointer", what);
   const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
   const size_t lds = ((size_t)3 * F * (A + 1) + (size_t)F * (F + 1)) * sizeof(float);
-  MAPX_HIP(raise_lds_limit());
+  MAPX_HIP(raise_lds_limit<T>());
   if (F <= 32)
-    hipLaunchKernelGGL(attn_fwd_kernel<2>, dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, G, F, A,
+    hipLaunchKernelGGL((attn_fwd_kernel<2, T>), dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, G, F, A,
                        inv_scale, o, p);
   else
-    hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3((unsigned)G), dim3(64), lds, stream, q, k, v, G, F, A, inv_scale, o, p);
-  return check_launch("attn_fwd");
+    hipLaunchKernelGGL((attn_fwd_kernel<1, T>), dim3((unsigned)G), dim3(64), lds, stream, q, k, v, G, F, A, inv_scale, o, p);
+  return check_launch(what);
 }
 
-extern "C" int mapx_attn_bwd(const float* q, const float* k, const float* v, const float* p, const float* d_o,
-                             int64_t G, int F, int A, int scaled, float* dq, float* dk, float* dv,
-                             hipStream_t stream) {
-  using namespace mapx;
+template <class T>
+static int attn_bwd_launch(const char* what, const T* q, const T* k, const T* v, const float* p, const T* d_o, int64_t G,
+                           int F, int A, int scaled, T* dq, T* dk, T* dv, hipStream_t stream) {
   MAPX_REQUIRE(G >= 0 && F >= 1 && F <= kAttnMaxF && A >= 1 && A <= kAttnMaxA,
-               "attn_bwd: F <= %d fields, attention size <= %d", kAttnMaxF, kAttnMaxA);
+               "%s: F <= %d fields, attention size <= %d", what, kAttnMaxF, kAttnMaxA);
   if (G == 0) return MAPX_OK;
-  MAPX_REQUIRE(q && k && v && p && d_o && dq && dk && dv, "attn_bwd: null pointer");
+  MAPX_REQUIRE(q && k && v && p && d_o && dq && dk && dv, "%s: null pointer", what);
   const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
   const size_t lds = ((size_t)4 * F * (A + 1) + (size_t)2 * F * (F + 1)) * sizeof(float);
-  MAPX_HIP(raise_lds_limit());
+  MAPX_HIP(raise_lds_limit<T>());
   if (F <= 32)
-    hipLaunchKernelGGL(attn_bwd_kernel<2>, dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, p, d_o, G,
+    hipLaunchKernelGGL((attn_bwd_kernel<2, T>), dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, p, d_o, G,
                        F, A, inv_scale, dq, dk, dv);
   else
-    hipLaunchKernelGGL(attn_bwd_kernel<1>, dim3((unsigned)G), dim3(64), lds, stream, q, k, v, p, d_o, G, F, A,
+    hipLaunchKernelGGL((attn_bwd_kernel<1, T>), dim3((unsigned)G), dim3(64), lds, stream, q, k, v, p, d_o, G, F, A,
                        inv_scale, dq, dk, dv);
-  return check_launch("attn_bwd");
+  return check_launch(what);
 }
 
 static int attn_drop_check(const char* what, int64_t G, int F, int A, float p) {
-  using namespace mapx;
   MAPX_REQUIRE(G >= 0 && F >= 1 && F <= kAttnMaxF && A >= 1 && A <= kAttnMaxA && p >= 0.f && p < 1.f,
                "%s: F <= %d fields, attention size <= %d, 0 <= p < 1 (got F=%d A=%d p=%g)", what, kAttnMaxF, kAttnMaxA, F,
                A, (double)p);
   return MAPX_OK;
 }
 
+template <class T>
+static int attn_drop_fwd_launch(const char* what, const char* plain, const T* q, const T* k, const T* v, int64_t G, int F,
+                                int A, int scaled, float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
+                                const int32_t* offset_dev_opt, T* o, float* probs, hipStream_t stream) {
+  if (int st = attn_drop_check(what, G, F, A, p)) return st;
+  if (p == 0.f) return attn_fwd_launch<T>(plain, q, k, v, G, F, A, scaled, o, probs, stream);
+  if (G == 0) return MAPX_OK;
+  MAPX_REQUIRE(q && k && v && o && probs, "%s: null pointer", what);
+  const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
+  const size_t lds = ((size_t)3 * F * (A + 1) + (size_t)F * (F + 1)) * sizeof(float);
+  MAPX_HIP(raise_lds_limit<T>());
+  if (F <= 32)
+    hipLaunchKernelGGL((attn_drop_fwd_kernel<2, T>), dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, G, F,
+                       A, inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, o, probs);
+  else
+    hipLaunchKernelGGL((attn_drop_fwd_kernel<1, T>), dim3((unsigned)G), dim3(64), lds, stream, q, k, v, G, F, A, inv_scale,
+                       p, seed, offset_p, offset_o, offset_dev_opt, o, probs);
+  return check_launch(what);
+}
+
+template <class T>
+static int attn_drop_bwd_launch(const char* what, const char* plain, const T* q, const T* k, const T* v,
+                                const float* probs, const T* d_o, int64_t G, int F, int A, int scaled, float p,
+                                uint64_t seed, uint64_t offset_p, uint64_t offset_o, const int32_t* offset_dev_opt, T* dq,
+                                T* dk, T* dv, hipStream_t stream) {
+  if (int st = attn_drop_check(what, G, F, A, p)) return st;
+  if (p == 0.f) return attn_bwd_launch<T>(plain, q, k, v, probs, d_o, G, F, A, scaled, dq, dk, dv, stream);
+  if (G == 0) return MAPX_OK;
+  MAPX_REQUIRE(q && k && v && probs && d_o && dq && dk && dv, "%s: null pointer", what);
+  const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
+  const size_t lds = ((size_t)4 * F * (A + 1) + (size_t)2 * F * (F + 1)) * sizeof(float);
+  MAPX_HIP(raise_lds_limit<T>());
+  if (F <= 32)
+    hipLaunchKernelGGL((attn_drop_bwd_kernel<2, T>), dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v,
+                       probs, d_o, G, F, A, inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, dq, dk, dv);
+  else
+    hipLaunchKernelGGL((attn_drop_bwd_kernel<1, T>), dim3((unsigned)G), dim3(64), lds, stream, q, k, v, probs, d_o, G, F, A,
+                       inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, dq, dk, dv);
+  return check_launch(what);
+}
+
+static inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
+static inline bf16_t* hm(mapx_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
+
+}  // namespace mapx
+
+extern "C" int mapx_attn_fwd(const float* q, const float* k, const float* v, int64_t G, int F, int A, int scaled,
+                             float* o, float* p, hipStream_t stream) {
+  return mapx::attn_fwd_launch<float>("attn_fwd", q, k, v, G, F, A, scaled, o, p, stream);
+}
+
+extern "C" int mapx_attn_bwd(const float* q, const float* k, const float* v, const float* p, const float* d_o,
+                             int64_t G, int F, int A, int scaled, float* dq, float* dk, float* dv,
+                             hipStream_t stream) {
+  return mapx::attn_bwd_launch<float>("attn_bwd", q, k, v, p, d_o, G, F, A, scaled, dq, dk, dv, stream);
+}
+
 extern "C" int mapx_attn_drop_fwd(const float* q, const float* k, const float* v, int64_t G, int F, int A, int scaled,
                                   float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
                                   const int32_t* offset_dev_opt, float* o, float* probs, hipStream_t stream) {
-  using namespace mapx;
-  if (int st = attn_drop_check("attn_drop_fwd", G, F, A, p)) return st;
-  if (p == 0.f) return mapx_attn_fwd(q, k, v, G, F, A, scaled, o, probs, stream);
-  if (G == 0) return MAPX_OK;
-  MAPX_REQUIRE(q && k && v && o && probs, "attn_drop_fwd: null pointer");
-  const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
-  const size_t lds = ((size_t)3 * F * (A + 1) + (size_t)F * (F + 1)) * sizeof(float);
-  MAPX_HIP(raise_lds_limit());
-  if (F <= 32)
-    hipLaunchKernelGGL(attn_drop_fwd_kernel<2>, dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, G, F, A,
-                       inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, o, probs);
-  else
-    hipLaunchKernelGGL(attn_drop_fwd_kernel<1>, dim3((unsigned)G), dim3(64), lds, stream, q, k, v, G, F, A, inv_scale, p,
-                       seed, offset_p, offset_o, offset_dev_opt, o, probs);
-  return check_launch("attn_drop_fwd");
+  return mapx::attn_drop_fwd_launch<float>("attn_drop_fwd", "attn_fwd", q, k, v, G, F, A, scaled, p, seed, offset_p,
+                                           offset_o, offset_dev_opt, o, probs, stream);
 }
 
 extern "C" int mapx_attn_drop_bwd(const float* q, const float* k, const float* v, const float* probs, const float* d_o,
                                   int64_t G, int F, int A, int scaled, float p, uint64_t seed, uint64_t offset_p,
                                   uint64_t offset_o, const int32_t* offset_dev_opt, float* dq, float* dk, float* dv,
                                   hipStream_t stream) {
+  return mapx::attn_drop_bwd_launch<float>("attn_drop_bwd", "attn_bwd", q, k, v, probs, d_o, G, F, A, scaled, p, seed,
+                                           offset_p, offset_o, offset_dev_opt, dq, dk, dv, stream);
+}
+
+// bf16 I/O forms: the same kernel templates on bf16 elements (q, k, v, dO in; o, dq, dk, dv out); P stays fp32.
+extern "C" int mapx_attn_fwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, int64_t G, int F, int A,
+                                  int scaled, mapx_bf16* o, float* p, hipStream_t stream) {
   using namespace mapx;
-  if (int st = attn_drop_check("attn_drop_bwd", G, F, A, p)) return st;
-  if (p == 0.f) return mapx_attn_bwd(q, k, v, probs, d_o, G, F, A, scaled, dq, dk, dv, stream);
-  if (G == 0) return MAPX_OK;
-  MAPX_REQUIRE(q && k && v && probs && d_o && dq && dk && dv, "attn_drop_bwd: null pointer");
-  const float inv_scale = scaled ? 1.0f / sqrtf((float)A) : 1.0f;
-  const size_t lds = ((size_t)4 * F * (A + 1) + (size_t)2 * F * (F + 1)) * sizeof(float);
-  MAPX_HIP(raise_lds_limit());
-  if (F <= 32)
-    hipLaunchKernelGGL(attn_drop_bwd_kernel<2>, dim3((unsigned)((G + 1) / 2)), dim3(64), 2 * lds, stream, q, k, v, probs,
-                       d_o, G, F, A, inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, dq, dk, dv);
-  else
-    hipLaunchKernelGGL(attn_drop_bwd_kernel<1>, dim3((unsigned)G), dim3(64), lds, stream, q, k, v, probs, d_o, G, F, A,
-                       inv_scale, p, seed, offset_p, offset_o, offset_dev_opt, dq, dk, dv);
-  return check_launch("attn_drop_bwd");
+  return attn_fwd_launch<bf16_t>("attn_fwd_bf16", hc(q), hc(k), hc(v), G, F, A, scaled, hm(o), p, stream);
+}
+
+extern "C" int mapx_attn_bwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, const float* p,
+                                  const mapx_bf16* d_o, int64_t G, int F, int A, int scaled, mapx_bf16* dq,
+                                  mapx_bf16* dk, mapx_bf16* dv, hipStream_t stream) {
+  using namespace mapx;
+  return attn_bwd_launch<bf16_t>("attn_bwd_bf16", hc(q), hc(k), hc(v), p, hc(d_o), G, F, A, scaled, hm(dq), hm(dk), hm(dv),
+                                 stream);
+}
+
+extern "C" int mapx_attn_drop_fwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, int64_t G, int F,
+                                       int A, int scaled, float p, uint64_t seed, uint64_t offset_p, uint64_t offset_o,
+                                       const int32_t* offset_dev_opt, mapx_bf16* o, float* probs, hipStream_t stream) {
+  using namespace mapx;
+  return attn_drop_fwd_launch<bf16_t>("attn_drop_fwd_bf16", "attn_fwd_bf16", hc(q), hc(k), hc(v), G, F, A, scaled, p, seed,
+                                      offset_p, offset_o, offset_dev_opt, hm(o), probs, stream);
+}
+
+extern "C" int mapx_attn_drop_bwd_bf16(const mapx_bf16* q, const mapx_bf16* k, const mapx_bf16* v, const float* probs,
+                                       const mapx_bf16* d_o, int64_t G, int F, int A, int scaled, float p, uint64_t seed,
+                                       uint64_t offset_p, uint64_t offset_o, const int32_t* offset_dev_opt, mapx_bf16* dq,
+                                       mapx_bf16* dk, mapx_bf16* dv, hipStream_t stream) {
+  using namespace mapx;
+  return attn_drop_bwd_launch<bf16_t>("attn_drop_bwd_bf16", "attn_bwd_bf16", hc(q), hc(k), hc(v), probs, hc(d_o), G, F, A,
+                                      scaled, p, seed, offset_p, offset_o, offset_dev_opt, hm(dq), hm(dk), hm(dv), stream);
 }
 
 extern "C" int mapx_attn_dropout_masks(int64_t G, int F, int A, float p, uint64_t seed, uint64_t offset_p,
                                        uint64_t offset_o, const int32_t* offset_dev_opt, uint8_t* keep_p,
                                        uint8_t* keep_o, hipStream_t stream) {
   using namespace mapx;
-  if (int st = attn_drop_check("attn_dropout_masks", G, F, A, p)) return st;
+  if (int st = mapx::attn_drop_check("attn_dropout_masks", G, F, A, p)) return st;
   if (G == 0) return MAPX_OK;
   MAPX_REQUIRE(keep_p && keep_o, "attn_dropout_masks: null pointer");
   const int64_t rows = G * F;

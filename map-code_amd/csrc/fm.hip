@@ -30,18 +30,22 @@ __global__ void __launch_bounds__(256) lr_sum_kernel(const int64_t* __restrict__
   }
 }
 
-// One lane per (row, e): walks the F fields (the E lanes of a row read E consecutive floats).
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+// One lane per (row, e): walks the F fields (the E lanes of a row read E consecutive elements).
 // s[b,e] = sum_f x is kept for backward.  E <= 64 and a power of two (host-checked).
-template <int E>
-__global__ void __launch_bounds__(256) fm_fwd_kernel(const float* __restrict__ x, int64_t B, int F,
+// T: the element type of x, float or bf16_t (bf16 compute mode: widened on load, sums and outputs fp32).
+template <int E, class T>
+__global__ void __launch_bounds__(256) fm_fwd_kernel(const T* __restrict__ x, int64_t B, int F,
                                                      float* __restrict__ out, float* __restrict__ s) {
   const int e = threadIdx.x % E;
   for (int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / E; b < B;
        b += ((int64_t)gridDim.x * blockDim.x) / E) {
-    const float* __restrict__ xb = x + b * F * E + e;
+    const T* __restrict__ xb = x + b * F * E + e;
     float sum = 0.f, sq = 0.f;
     for (int f = 0; f < F; ++f) {
-      const float v = xb[(int64_t)f * E];
+      const float v = (float)xb[(int64_t)f * E];
       sum += v;
       sq += v * v;
     }
@@ -51,10 +55,24 @@ __global__ void __launch_bounds__(256) fm_fwd_kernel(const float* __restrict__ x
   }
 }
 
-// dx[b,f,e] = g[b] * (s[b,e] - x[b,f,e])
+// Four consecutive elements of x / dx: one 16-byte (fp32) or 8-byte (bf16) access
+__device__ inline float4 fm_load4(const float* p, int64_t i) { return reinterpret_cast<const float4*>(p)[i]; }
+__device__ inline float4 fm_load4(const bf16_t* p, int64_t i) {
+  const bf16x4_t v = reinterpret_cast<const bf16x4_t*>(p)[i];
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ inline void fm_store4(float* p, int64_t i, const float4& v) { reinterpret_cast<float4*>(p)[i] = v; }
+__device__ inline void fm_store4(bf16_t* p, int64_t i, const float4& v) {      // round to nearest even, once
+  bf16x4_t o;
+  o[0] = (bf16_t)v.x; o[1] = (bf16_t)v.y; o[2] = (bf16_t)v.z; o[3] = (bf16_t)v.w;
+  reinterpret_cast<bf16x4_t*>(p)[i] = o;
+}
+
+// dx[b,f,e] = g[b] * (s[b,e] - x[b,f,e])      (g, s fp32; x, dx of type T)
+template <class T>
 __global__ void __launch_bounds__(256) fm_bwd_kernel(const float* __restrict__ g, const float* __restrict__ s,
-                                                     const float* __restrict__ x, int64_t B, int F, int E,
-                                                     float* __restrict__ dx) {
+                                                     const T* __restrict__ x, int64_t B, int F, int E,
+                                                     T* __restrict__ dx) {
   const int64_t n4 = B * F * E / 4;
   const int e4 = E / 4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
@@ -63,9 +81,8 @@ __global__ void __launch_bounds__(256) fm_bwd_kernel(const float* __restrict__ g
     const int c = (int)(i % e4);
     const float gb = g[b];
     const float4 sv = reinterpret_cast<const float4*>(s)[b * e4 + c];
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    reinterpret_cast<float4*>(dx)[i] = make_float4(gb * (sv.x - xv.x), gb * (sv.y - xv.y),
-                                                   gb * (sv.z - xv.z), gb * (sv.w - xv.w));
+    const float4 xv = fm_load4(x, i);
+    fm_store4(dx, i, make_float4(gb * (sv.x - xv.x), gb * (sv.y - xv.y), gb * (sv.z - xv.z), gb * (sv.w - xv.w)));
   }
 }
 
@@ -87,7 +104,7 @@ extern "C" int mapx_fm_fwd(const float* x, int64_t B, int F, int E, float* out, 
   if (B == 0) return MAPX_OK;
   MAPX_REQUIRE(x && out && s, "fm_fwd: null pointer");
   const int grid = mapx::grid_for(B * E, 256);
-#define MAPX_FM(E_) hipLaunchKernelGGL(mapx::fm_fwd_kernel<E_>, dim3(grid), dim3(256), 0, stream, x, B, F, out, s)
+#define MAPX_FM(E_) hipLaunchKernelGGL((mapx::fm_fwd_kernel<E_, float>), dim3(grid), dim3(256), 0, stream, x, B, F, out, s)
   switch (E) {
     case 4: MAPX_FM(4); break;
     case 8: MAPX_FM(8); break;
@@ -106,7 +123,40 @@ extern "C" int mapx_fm_bwd(const float* g, const float* s, const float* x, int64
   MAPX_REQUIRE(g && s && x && dx, "fm_bwd: null pointer");
   MAPX_REQUIRE(((uintptr_t)s % 16 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dx % 16 == 0),
                "fm_bwd: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(mapx::fm_bwd_kernel, dim3(mapx::grid_for(B * F * E / 4, 256)), dim3(256), 0, stream, g, s, x,
+  hipLaunchKernelGGL(mapx::fm_bwd_kernel<float>, dim3(mapx::grid_for(B * F * E / 4, 256)), dim3(256), 0, stream, g, s, x,
                      B, F, E, dx);
   return mapx::check_launch("fm_bwd");
+}
+
+// bf16 compute mode: x (the gathered rows) and dx are bf16; fm, s and g stay fp32.  E in {8,16,32,64}: the bf16 gather
+// writes 16-byte rows (E % 8 == 0), so E = 4 has no producer and is refused.
+extern "C" int mapx_fm_fwd_bf16(const mapx_bf16* x, int64_t B, int F, int E, float* out, float* s, hipStream_t stream) {
+  MAPX_REQUIRE(B >= 0 && F > 0, "fm_fwd_bf16: bad sizes");
+  MAPX_REQUIRE(E == 8 || E == 16 || E == 32 || E == 64, "fm_fwd_bf16: embed_size %d (8, 16, 32, 64)", E);
+  if (B == 0) return MAPX_OK;
+  MAPX_REQUIRE(x && out && s, "fm_fwd_bf16: null pointer");
+  const int grid = mapx::grid_for(B * E, 256);
+  const mapx::bf16_t* xh = reinterpret_cast<const mapx::bf16_t*>(x);
+#define MAPX_FM(E_) hipLaunchKernelGGL((mapx::fm_fwd_kernel<E_, mapx::bf16_t>), dim3(grid), dim3(256), 0, stream, xh, B, F, out, s)
+  switch (E) {
+    case 8: MAPX_FM(8); break;
+    case 16: MAPX_FM(16); break;
+    case 32: MAPX_FM(32); break;
+    default: MAPX_FM(64); break;
+  }
+#undef MAPX_FM
+  return mapx::check_launch("fm_fwd_bf16");
+}
+
+extern "C" int mapx_fm_bwd_bf16(const float* g, const float* s, const mapx_bf16* x, int64_t B, int F, int E,
+                                mapx_bf16* dx, hipStream_t stream) {
+  MAPX_REQUIRE(B >= 0 && F > 0, "fm_bwd_bf16: bad sizes");
+  MAPX_REQUIRE(E == 8 || E == 16 || E == 32 || E == 64, "fm_bwd_bf16: embed_size %d (8, 16, 32, 64)", E);
+  if (B == 0) return MAPX_OK;
+  MAPX_REQUIRE(g && s && x && dx, "fm_bwd_bf16: null pointer");
+  MAPX_REQUIRE(((uintptr_t)s % 16 == 0) && ((uintptr_t)x % 8 == 0) && ((uintptr_t)dx % 8 == 0),
+               "fm_bwd_bf16: s must be 16-byte, x and dx 8-byte aligned");
+  hipLaunchKernelGGL(mapx::fm_bwd_kernel<mapx::bf16_t>, dim3(mapx::grid_for(B * F * E / 4, 256)), dim3(256), 0, stream, g, s,
+                     reinterpret_cast<const mapx::bf16_t*>(x), B, F, E, reinterpret_cast<mapx::bf16_t*>(dx));
+  return mapx::check_launch("fm_bwd_bf16");
 }

@@ -309,6 +309,25 @@ extern "C" int mapx_seg_reduce_rows_extra(int64_t n, const int32_t* perm, const 
                                        "seg_reduce_rows_extra");
 }
 
+// mapx_seg_reduce_rows_extra over bf16 rows: the same plan order, fp32 sums and outputs, the scalar fp32.
+extern "C" int mapx_seg_reduce_rows_extra_bf16(int64_t n, const int32_t* perm, const int32_t* rank,
+                                               const int32_t* seg_start, const mapx_bf16* src, int W, int64_t ld_src,
+                                               const float* extra, int group, int64_t extra_stride, float* out,
+                                               float* out_extra, void* ws, size_t ws_bytes,
+                                               int32_t* zeroed_counter_opt, hipStream_t stream) {
+  MAPX_REQUIRE(n >= 0 && group >= 1 && ld_src >= W && ld_src % 4 == 0 && extra_stride >= 1,
+               "seg_reduce_rows_extra_bf16: bad sizes");
+  if (n == 0) return MAPX_OK;
+  MAPX_REQUIRE(perm && rank && seg_start && src && extra && out && out_extra,
+               "seg_reduce_rows_extra_bf16: null pointer");
+  MAPX_REQUIRE(((uintptr_t)src % 8 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)ws % 16 == 0),
+               "seg_reduce_rows_extra_bf16: pointers must be 8 / 16-byte aligned");
+  mapx::SegPlanView pl{n, perm, rank, seg_start};
+  mapx::RowsExtraBf16Contrib c{reinterpret_cast<const __bf16*>(src), W, ld_src, extra, group, extra_stride};
+  return mapx::seg_reduce_launch<true>(pl, c, W, out, out_extra, ws, ws_bytes, zeroed_counter_opt, stream,
+                                       "seg_reduce_rows_extra_bf16");
+}
+
 // Data-parallel exchange (mapx/parallel.py): the first n_uniq (id, gradient row) pairs of a rank's
 // sparse gradient as a fixed-size message of `maxc` entries: keys_out[i] = uniq[i], rows_out[i] =
 // {rows0[i, :] * scale, rows1[i] * scale, 0, 0, 0} (rows1 optional: then W0 columns only); entries

@@ -121,6 +121,23 @@ struct RowsExtraContrib {
   }
 };
 
+// The same with bf16 rows (bf16 compute mode: DeepFM's / AutoInt's dL/dX); the scalar stays fp32.
+struct RowsExtraBf16Contrib {
+  const __bf16* src;   // [n, ld]
+  int W;
+  int64_t ld;
+  const float* extra;
+  int group;
+  int64_t estride;
+  __device__ inline void prepare() {}
+  __device__ inline float4 operator()(int32_t p, int sub, float& ex) const {
+    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+    ex = extra[(int64_t)(p / group) * estride];
+    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(src + (int64_t)p * ld + 4 * sub);
+    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+  }
+};
+
 struct NceContrib {
   const float* dlogit;  // [T*(K+1)]
   const float* h;       // [T, P]

@@ -250,10 +250,10 @@ class _GatherLinear(Function):
     both gradients with the table's one segment plan (rows + a scalar per batch row)."""
 
     @staticmethod
-    def forward(ctx, weight, lin_weight, ids, table):
+    def forward(ctx, weight, lin_weight, ids, table, out_dtype=torch.float32):
         ctx.table, ctx.plan, ctx.width, ctx.F = table, table.plan, weight.shape[1], ids.shape[1]
-        x = ops.emb_gather(ids, weight)
-        lr = ops.lr_sum(ids, lin_weight.view(-1))
+        x = ops.emb_gather(ids, weight, out_dtype=out_dtype)      # bf16 rows in bf16 compute mode
+        lr = ops.lr_sum(ids, lin_weight.view(-1))                 # the LR sum stays fp32
         return x, lr
 
     @staticmethod
@@ -261,14 +261,15 @@ class _GatherLinear(Function):
         if ctx.plan is None:
             raise RuntimeError("embedding backward without a segment plan")
         plan = ctx.plan.get()
-        gx = gx.contiguous().view(-1, ctx.width)
+        gx = gx.contiguous().view(-1, ctx.width)          # bf16 rows in bf16 mode: summed in fp32, like the scalar
         rows0, rows1 = ops.seg_reduce_rows_extra(plan, gx, ctx.width, glr.contiguous().view(-1), ctx.F)
         ctx.table.sparse_grad = (plan, rows0, rows1)
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class _FmProductSum(Function):
-    """InnerProductLayer(output='product_sum') (reference layers.py:123-131) on [B,F,E] -> [B,1]."""
+    """InnerProductLayer(output='product_sum') (reference layers.py:123-131) on [B,F,E] -> [B,1].
+    bf16 x3 (bf16 compute mode): the term and the field sums stay fp32, backward returns bf16 dx."""
 
     @staticmethod
     def forward(ctx, x3):
@@ -285,6 +286,23 @@ class _FmProductSum(Function):
 
 def fm_product_sum(x3):
     return _FmProductSum.apply(x3)
+
+
+class _ToBf16(Function):
+    """An fp32 tensor enters the bf16 trunk (DeepFM's lr + fm column of the heads' input): rounded once by the
+    library's cast kernel; its gradient comes back as fp32."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.cast_bf16(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.cast_f32(g) if ops.is_bf16(g) else g
+
+
+def to_bf16(x):
+    return _ToBf16.apply(x)
 
 
 class _Dropout(Function):
@@ -426,7 +444,7 @@ class Embeddings(nn.Module):
             if (need_grad or self.table.lazy is not None) else None
         if keys is not None:
             self.table.prepare(keys, need_grad, defer_plan=self.defer_plan)
-        x, lr = _GatherLinear.apply(w, lin_weight, input_ids, self.table)
+        x, lr = _GatherLinear.apply(w, lin_weight, input_ids, self.table, self.compute_dtype)
         if self.embed_norm:
             x = self.layer_norm(x)
         return self.dropout(x), lr
@@ -541,6 +559,7 @@ class _Linear(Function):
         x = x.contiguous()
         half = ops.is_bf16(x)
         ctx.kpad, ctx.sw_real = 0, None
+        wop = None
         if (not half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
                 and link_in is None):
             # An input width that is not a multiple of 8 floats (DeepFM's heads read cat([dnn, lr + fm]): 1001 columns)
@@ -550,9 +569,16 @@ class _Linear(Function):
             ctx.kpad, ctx.sw_real = (-x.shape[1]) % 8, _grad_slot(w)
             x = torch.nn.functional.pad(x, (0, ctx.kpad))
             w = torch.nn.functional.pad(w.detach(), (0, ctx.kpad))
+        elif (half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
+                and link_in is None):
+            # the same in bf16 mode (the bf16 GEMM's 16-byte chunks hold 8 elements): x and the weight's shadow padded
+            ctx.kpad, ctx.sw_real = (-x.shape[1]) % 8, _grad_slot(w)
+            x = torch.nn.functional.pad(x, (0, ctx.kpad))
+            wop = torch.nn.functional.pad(ops.bf16_weight(w), (0, ctx.kpad))
         if half and relu and out_f32:
             raise NotImplementedError("a ReLU layer with an fp32 result inside the bf16 trunk")
-        wop = ops.bf16_weight(w) if half else w           # bf16 mode: the optimizer's bf16 shadow of w
+        if wop is None:
+            wop = ops.bf16_weight(w) if half else w       # bf16 mode: the optimizer's bf16 shadow of w
         y = ops.linear_fwd(x, wop, b, relu=relu, out=out, out_dtype=torch.float32 if (half and out_f32) else None)
         ctx.relu, ctx.half = relu, half
         ctx.slots = (_grad_slot(w) if not ctx.kpad else None, _grad_slot(b))
@@ -828,7 +854,9 @@ class _SelfAttention(Function):
     of x [B,F,Din]; heads are the reference's .view(B*H, -1, A) chunks.  Projections and all
     weight / input gradients are MFMA GEMMs, the F x F core is csrc/attn.hip.  `drops`: None, or the layer's two
     dropout sites (on the probabilities, on the heads' output: layers.py:740-742, 901-904), whose masks the core's
-    dropout forms draw themselves; the output they return is already dropped, so the residual branches do not change."""
+    dropout forms draw themselves; the output they return is already dropped, so the residual branches do not change.
+    bf16 x (bf16 compute mode): the projections are bf16 GEMMs on the weights' bf16 shadows; q, k, v, o,
+    the output and dq, dk, dv, dpre, dx are bf16; the probabilities P and every weight gradient stay fp32."""
 
     @staticmethod
     def forward(ctx, x, wq, wk, wv, wres, heads, attn_size, res_conn, scaled, drops=None):
@@ -836,6 +864,10 @@ class _SelfAttention(Function):
         HA = heads * attn_size
         x2 = x.contiguous().view(B * F, Din)
         M = B * F
+        ctx.slots = [_grad_slot(w) if w is not None else None for w in (wq, wk, wv, wres)]
+        if ops.is_bf16(x2):            # the optimizer's bf16 shadows are the GEMM operands (saved for backward too)
+            wq, wk, wv = ops.bf16_weight(wq), ops.bf16_weight(wk), ops.bf16_weight(wv)
+            wres = ops.bf16_weight(wres) if wres is not None else None
         q = ops.gemm(x2, wq, True, True, M, HA, Din)
         k = ops.gemm(x2, wk, True, True, M, HA, Din)
         v = ops.gemm(x2, wv, True, True, M, HA, Din)
@@ -857,7 +889,6 @@ class _SelfAttention(Function):
         out = torch.relu(pre)
         ctx.cfg = (B, F, Din, heads, attn_size, res_conn, scaled)
         ctx.drop = drop
-        ctx.slots = [_grad_slot(w) if w is not None else None for w in (wq, wk, wv, wres)]
         ctx.save_for_backward(x2, wq, wk, wv, wres, q, k, v, p, out)
         return out.view(B, F, HA)
 
@@ -866,6 +897,8 @@ class _SelfAttention(Function):
         x2, wq, wk, wv, wres, q, k, v, p, out = ctx.saved_tensors
         B, F, Din, heads, A, res_conn, scaled = ctx.cfg
         HA = heads * A
+        if ops.is_bf16(out) and g.dtype == torch.float32:
+            g = ops.cast_bf16(g)                   # an fp32 gradient enters the bf16 trunk
         dpre = ops.relu_mask(g.contiguous().view(B * F, HA), out)
         if ctx.drop is None:
             dq, dk, dv = ops.attn_bwd(q, k, v, p, dpre, B * heads, F, A, scaled)

@@ -11,7 +11,7 @@ from . import ops
 from .arguments import Config
 from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, FGCNNBlock, HipLinear, MLPBlock,
                      MultiHeadSelfAttention, RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer,
-                     bce_with_logits, field_pool, fm_product_sum, inner_product)
+                     bce_with_logits, field_pool, fm_product_sum, inner_product, to_bf16)
 from .nce import IndexLinear
 
 logger = logging.getLogger(__name__)
@@ -42,6 +42,19 @@ def plan_after_main(pretrain, f32_trunk, D):
 _OTHER_BACKBONES = ("fignn",)
 
 
+def _refuse_bf16_mlp_options(config, act_flag, drop_flag):
+    """DeepFM / AutoInt in compute_dtype=bf16: what MLPBlock.forward refuses for a bf16 input (a non-ReLU activation,
+    dropout between the layers) is refused when the model is built, with MLPBlock's messages and the flag's name."""
+    from .layers import compute_dtype_of
+    if compute_dtype_of(config) == torch.float32:
+        return
+    act = str(getattr(config, act_flag)).lower()
+    if act != "relu":
+        raise NotImplementedError(f"{act_flag}: hidden_act={act!r} is built for compute_dtype=fp32")
+    if float(getattr(config, drop_flag) or 0.0) > 0:
+        raise NotImplementedError(f"{drop_flag}: hidden_dropout_rate > 0 is built for compute_dtype=fp32")
+
+
 class _RfdPredictor(nn.ModuleDict):
     """Linear -> ReLU -> Linear with the reference nn.Sequential's keys "0" and "2"
     (models.py:119-123); the ReLU is fused into the first GEMM's epilogue."""
@@ -65,8 +78,9 @@ class BaseModel(nn.Module):
     def from_config(cls, config: Config):
         name = config.model_name.lower()
         from .layers import compute_dtype_of
-        if compute_dtype_of(config) != torch.float32 and name not in ("dcnv2", "dnn"):
-            raise NotImplementedError(f"compute_dtype=bf16 is built for DCNv2 and DNN, not {config.model_name}")
+        if compute_dtype_of(config) != torch.float32 and name not in ("dcnv2", "dnn", "deepfm", "autoint"):
+            raise NotImplementedError("compute_dtype=bf16 is built for DCNv2, DNN, DeepFM and AutoInt, "
+                                      f"not {config.model_name}")
         if name == "dcnv2":
             return DCNV2(config)
         if name == "dnn":
@@ -386,11 +400,14 @@ class _InnerProductBuffers(nn.Module):
 
 class DeepFM(BaseModel):
     """LR + FM(product_sum) + MLP (reference models.py:196-233).  Pretraining feeds
-    cat([dnn_vec, lr + fm]) [B, H+1] to the MFP / RFD heads; CTR sums the three logits."""
+    cat([dnn_vec, lr + fm]) [B, H+1] to the MFP / RFD heads; CTR sums the three logits.
+    compute_dtype=bf16: the gathered rows and the MLP are bf16; the LR sum, the FM term and lr + bias + fm [B,1] stay
+    fp32 — rounded once where that column joins the heads' bf16 input, added in fp32 to the CTR logit."""
     used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act"]
 
     def __init__(self, config: Config):
         super().__init__(model_name="DeepFM", config=config)
+        _refuse_bf16_mlp_options(config, "hidden_act", "hidden_dropout_rate")
         self.embed = Embeddings(config)
         self.embed.defer_plan = True
         self.lr_layer = LR(config)
@@ -403,7 +420,7 @@ class DeepFM(BaseModel):
         if config.pretrain:
             self.create_pretraining_predictor(config.hidden_size + 1)
         else:
-            self.dnn_fc_out = HipLinear(config.hidden_size, 1)
+            self.dnn_fc_out = HipLinear(config.hidden_size, 1, out_fp32=True)
 
     def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
         x3, lr = self.embed.forward_with_linear(input_ids, self.lr_layer.embed_w.weight)
@@ -412,7 +429,7 @@ class DeepFM(BaseModel):
         self._plans_and_join(nce_idx, early)
         lr_fm = lr.view(-1, 1) + self.lr_layer.bias + fm_product_sum(x3)
         if self.config.pretrain:
-            final_vec = torch.cat([dnn_vec, lr_fm], dim=1)
+            final_vec = torch.cat([dnn_vec, to_bf16(lr_fm) if ops.is_bf16(dnn_vec) else lr_fm], dim=1)
             return self.get_outputs(final_vec, labels, masked_index, noise_samples=noise_samples, nce_idx=nce_idx)
         return self.get_outputs(self.dnn_fc_out(dnn_vec) + lr_fm, labels)
 
@@ -422,7 +439,10 @@ class AutoInt(BaseModel):
     the flattened [B, F*heads*attn_size] output feeds the MFP / RFD heads or `attn_out`; the finetune model adds
     the LR term (use_lr: its weight is the secondary parameter of the embedding's RowTable, as in DeepFM) and an MLP
     tower over the flattened embeddings (num_dnn_layers > 0: `dnn` + `dnn_out`), models.py:464-471, 482-486.
-    attn_probs_dropout_rate > 0: two dropouts per attention layer, drawn inside csrc/attn.hip."""
+    attn_probs_dropout_rate > 0: two dropouts per attention layer, drawn inside csrc/attn.hip.
+    compute_dtype=bf16: the gathered rows, q, k, v, the attention output and every layer's output are bf16 (the bf16
+    I/O forms of csrc/attn.hip, bf16 GEMMs on the weights' shadows); the probabilities, the LR term and the logits of
+    attn_out / dnn_out stay fp32; attn_probs_dropout_rate > 0 works as in fp32 mode."""
     used_params = ["embed_size", "num_attn_layers", "attn_size", "num_attn_heads", "attn_probs_dropout_rate",
                    "use_lr", "res_conn", "attn_scale", "dnn_size", "num_dnn_layers", "dnn_act", "dnn_drop"]
 
@@ -440,7 +460,7 @@ class AutoInt(BaseModel):
         if config.pretrain:
             self.create_pretraining_predictor(final_dim)
         else:
-            self.attn_out = HipLinear(final_dim, 1)
+            self.attn_out = HipLinear(final_dim, 1, out_fp32=True)       # (bf16 mode: the logits stay fp32)
             # (the reference creates these for the finetune model only: models.py:463-471)
             self.lr_layer = LR(config) if config.use_lr else None
             if self.lr_layer is not None:       # one row table for both [V, *] parameters read with input_ids
@@ -448,6 +468,8 @@ class AutoInt(BaseModel):
             # The reference sizes the tower's input as final_dim (fields x heads x attn_size, models.py:466) and feeds
             # it the flattened EMBEDDINGS (fields x embed_size, models.py:486): the option runs only when the two
             # agree; the same shapes and the same error otherwise.
+            if config.num_dnn_layers:
+                _refuse_bf16_mlp_options(config, "dnn_act", "dnn_drop")
             if config.num_dnn_layers and final_dim != config.num_fields * config.embed_size:
                 raise ValueError("AutoInt with num_dnn_layers > 0 needs embed_size == num_attn_heads * attn_size "
                                  "(reference models.py:466, 486: the tower is sized for the attention output and fed "
@@ -455,7 +477,7 @@ class AutoInt(BaseModel):
             self.dnn = MLPBlock(input_dim=final_dim, hidden_size=config.dnn_size,
                                 num_hidden_layers=config.num_dnn_layers, hidden_dropout_rate=config.dnn_drop,
                                 hidden_act=config.dnn_act) if config.num_dnn_layers else None
-            self.dnn_out = HipLinear(config.dnn_size, 1) if config.num_dnn_layers else None
+            self.dnn_out = HipLinear(config.dnn_size, 1, out_fp32=True) if config.num_dnn_layers else None
 
     def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
         lr = None

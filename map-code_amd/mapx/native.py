@@ -81,6 +81,13 @@ SIGNATURES = {
     "mapx_cast_bf16_f32": (_i, [_p, _i64, _p, _p]),
     "mapx_emb_gather_fwd_bf16": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p]),
     "mapx_seg_reduce_rows_bf16": (_i, [_i64, _p, _p, _p, _p, _p, _i, _p, _p, _sz, _p, _p]),
+    "mapx_seg_reduce_rows_extra_bf16": (_i, [_i64, _p, _p, _p, _p, _i, _i64, _p, _i, _i64, _p, _p, _p, _sz, _p, _p]),
+    "mapx_fm_fwd_bf16": (_i, [_p, _i64, _i, _i, _p, _p, _p]),
+    "mapx_fm_bwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _p, _p]),
+    "mapx_attn_fwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p]),
+    "mapx_attn_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p]),
+    "mapx_attn_drop_fwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _u64, _p, _p, _p, _p]),
+    "mapx_attn_drop_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
     "mapx_colsum_bf16_workspace_bytes": (_sz, [_i]),
     "mapx_colsum_bf16": (_i, [_p, _i64, _i, _i, _p, _p, _sz, _p]),
     "mapx_relu_mask_colsum_bf16": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _p, _p, _sz, _p]),

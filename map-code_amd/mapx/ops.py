@@ -457,16 +457,20 @@ def seg_reduce_rows(plan, src, W, src2=None):
 def seg_reduce_rows_extra(plan, src, W, extra, group, extra_stride=1):
     """-> (rows [cap,W], scalars [cap]): the row reduction of seg_reduce_rows over the first W columns
     of src plus, per unique key, the sum of extra[(position // group) * extra_stride] (DeepFM's LR
-    weight gradient rides with the embedding's; DP merge of rows that carry a scalar column)."""
+    weight gradient rides with the embedding's; DP merge of rows that carry a scalar column).
+    bf16 src (bf16 compute mode): fp32 sums and outputs, `extra` stays fp32."""
     require_gpu(src, extra)
+    if extra.dtype != torch.float32:
+        raise TypeError("seg_reduce_rows_extra: the extra scalars are fp32")
     out = torch.empty(max(plan.n, 1), W, dtype=torch.float32, device=src.device)
     out1 = torch.empty(max(plan.n, 1), dtype=torch.float32, device=src.device)
     ws = scratch(lib.mapx_seg_reduce_workspace_bytes(plan.n, W), src.device)
-    with _timed("seg_reduce_rows", plan.n * (4.0 * W + 12)):
-        check(lib.mapx_seg_reduce_rows_extra(plan.n, ptr(plan.perm), ptr(plan.rank), ptr(plan.seg_start),
-                                             src.data_ptr(), W, src.stride(0), extra.data_ptr(), group,
-                                             extra_stride, ptr(out), ptr(out1), ptr(ws), ws.numel(),
-                                             plan.take_counter(), stream()))
+    fn = lib.mapx_seg_reduce_rows_extra_bf16 if is_bf16(src) else lib.mapx_seg_reduce_rows_extra
+    with _timed("seg_reduce_rows", plan.n * (float(src.element_size()) * W + 12)):
+        check(fn(plan.n, ptr(plan.perm), ptr(plan.rank), ptr(plan.seg_start),
+                 src.data_ptr(), W, src.stride(0), extra.data_ptr(), group,
+                 extra_stride, ptr(out), ptr(out1), ptr(ws), ws.numel(),
+                 plan.take_counter(), stream()))
     return out, out1
 
 
@@ -586,37 +590,62 @@ def lr_sum(ids, w, validate=False):
 
 
 def fm_fwd(x3):
-    """x3 [B,F,E] -> (fm [B], s [B,E] = sum over fields, kept for backward)   (layers.py:123-131)."""
+    """x3 [B,F,E] (fp32 or bf16) -> (fm [B], s [B,E] = sum over fields, kept for backward), both fp32
+    (layers.py:123-131)."""
     require_gpu(x3)
     x3 = x3.contiguous()
     B, F, E = x3.shape
     out = torch.empty(B, dtype=torch.float32, device=x3.device)
     s = torch.empty(B, E, dtype=torch.float32, device=x3.device)
-    check(lib.mapx_fm_fwd(ptr(x3), B, F, E, ptr(out), ptr(s), stream()))
+    fn = lib.mapx_fm_fwd_bf16 if is_bf16(x3) else lib.mapx_fm_fwd
+    check(fn(ptr(x3), B, F, E, ptr(out), ptr(s), stream()))
     return out, s
 
 
 def fm_bwd(g, s, x3):
+    """g [B] fp32, s [B,E] fp32, x3 [B,F,E] -> dx of x3's dtype (bf16: rounded once)."""
+    require_gpu(g, s, x3)
     B, F, E = x3.shape
     dx = torch.empty_like(x3)
-    check(lib.mapx_fm_bwd(ptr(g.contiguous()), ptr(s), ptr(x3), B, F, E, ptr(dx), stream()))
+    fn = lib.mapx_fm_bwd_bf16 if is_bf16(x3) else lib.mapx_fm_bwd
+    check(fn(ptr(_f32(g, "fm_bwd: g").contiguous()), ptr(s), ptr(x3), B, F, E, ptr(dx), stream()))
     return dx
 
 
 # --------------------------------------------------------------------------- AutoInt attention core
+def _f32(t, what):
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} is fp32, got {t.dtype}")
+    return t
+
+
+def _attn_half(what, *ts):
+    """True: the bf16 I/O forms (every tensor bf16); False: the fp32 entries.  Mixed element types are an error."""
+    half = is_bf16(ts[0])
+    for t in ts:
+        if t.dtype != (BF16 if half else torch.float32) or not t.is_contiguous():
+            raise TypeError(f"{what}: q, k, v (and d_o) are contiguous tensors of one element type, fp32 or bf16")
+    return half
+
+
 def attn_fwd(q, k, v, G, F, A, scaled):
-    """q, k, v: G*F*A floats each (G = B*heads groups of [F, A]) -> (o same size, p [G,F,F])."""
+    """q, k, v: G*F*A elements each, fp32 or bf16 (G = B*heads groups of [F, A]) -> (o same size and dtype,
+    p [G,F,F] fp32)."""
     require_gpu(q, k, v)
+    fn = lib.mapx_attn_fwd_bf16 if _attn_half("attn_fwd", q, k, v) else lib.mapx_attn_fwd
     o = torch.empty_like(q)
     p = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
-    check(lib.mapx_attn_fwd(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), ptr(o), ptr(p), stream()))
+    check(fn(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), ptr(o), ptr(p), stream()))
     return o, p
 
 
 def attn_bwd(q, k, v, p, d_o, G, F, A, scaled):
+    require_gpu(q, k, v, p, d_o)
+    d_o = d_o.contiguous()
+    fn = lib.mapx_attn_bwd_bf16 if _attn_half("attn_bwd", q, k, v, d_o) else lib.mapx_attn_bwd
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(lib.mapx_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(p), ptr(d_o.contiguous()), G, F, A, int(bool(scaled)),
-                            ptr(dq), ptr(dk), ptr(dv), stream()))
+    check(fn(ptr(q), ptr(k), ptr(v), ptr(_f32(p, "attn_bwd: p")), ptr(d_o), G, F, A, int(bool(scaled)),
+             ptr(dq), ptr(dk), ptr(dv), stream()))
     return dq, dk, dv
 
 
@@ -624,20 +653,23 @@ def attn_drop_fwd(q, k, v, G, F, A, scaled, p, seed, offset_p, offset_o, offset_
     """attn_fwd with the layer's two dropouts inside the kernel: O = ((P * m_p / (1-p)) V) * m_o / (1-p) with
     (m_p, m_o) = attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev) -> (o, p undropped)."""
     require_gpu(q, k, v)
+    fn = lib.mapx_attn_drop_fwd_bf16 if _attn_half("attn_drop_fwd", q, k, v) else lib.mapx_attn_drop_fwd
     o = torch.empty_like(q)
     probs = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
-    check(lib.mapx_attn_drop_fwd(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), float(p), int(seed), int(offset_p),
-                                 int(offset_o), ptr(offset_dev), ptr(o), ptr(probs), stream()))
+    check(fn(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), float(p), int(seed), int(offset_p),
+             int(offset_o), ptr(offset_dev), ptr(o), ptr(probs), stream()))
     return o, probs
 
 
 def attn_drop_bwd(q, k, v, probs, d_o, G, F, A, scaled, p, seed, offset_p, offset_o, offset_dev=None):
     """-> (dq, dk, dv); both masks are regenerated from (seed, offsets)."""
     require_gpu(q, k, v, probs, d_o)
+    d_o = d_o.contiguous()
+    fn = lib.mapx_attn_drop_bwd_bf16 if _attn_half("attn_drop_bwd", q, k, v, d_o) else lib.mapx_attn_drop_bwd
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(lib.mapx_attn_drop_bwd(ptr(q), ptr(k), ptr(v), ptr(probs), ptr(d_o.contiguous()), G, F, A, int(bool(scaled)),
-                                 float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev), ptr(dq), ptr(dk),
-                                 ptr(dv), stream()))
+    check(fn(ptr(q), ptr(k), ptr(v), ptr(_f32(probs, "attn_drop_bwd: probs")), ptr(d_o), G, F, A, int(bool(scaled)),
+             float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev), ptr(dq), ptr(dk),
+             ptr(dv), stream()))
     return dq, dk, dv
 
 
