@@ -502,13 +502,27 @@ int mapx_bce_with_logits(const float* logits, const float* labels, int64_t n, fl
 size_t mapx_eval_metrics_workspace_bytes(int64_t n);
 int mapx_eval_metrics(const float* logits, const float* labels, int64_t n, double* out6, void* ws,
                       size_t ws_bytes, hipStream_t stream);
-/* trainer.py:217-232 (MFP, sampling_method="randint"): masked_index_in NULL -> Philox.
+/* trainer.py:217-232 (MFP): masked_index_in NULL -> Philox, keyed by (seed, offset + *offset_dev).
+ * draw (ignored when masked_index_in is given; the same in mapx_dynamic_mask_mfp_rows and mapx_dynamic_mask_rfd):
+ *   0  with replacement (sampling_method="randint"): masked_index[b,l] = word x of Philox(counter b*L + l) scaled to
+ *      [0, F) — a row may name a field twice;
+ *   1  distinct (sampling_method="normal", trainer.py:222 torch.randperm(F)[:L]); needs L <= F.  Field f of batch row
+ *      b owns the 32-bit key  key(b,f) = word f & 3 of Philox(counter 2^63 | (b*ceil(F/4) + f/4))  — four fields share
+ *      one 128-bit draw, and bit 63 keeps these counters apart from the b*L + l counters of draw 0 and of the RFD
+ *      replacement draws under the same seed and offset.  With
+ *        rank(b,f) = #{ g : key(b,g) < key(b,f) or (key(b,g) == key(b,f) and g < f) },
+ *      masked_index[b,r] = the f of rank r, r < L: argsort(key[b,:], stable)[:L], the ordered L-prefix of a uniform
+ *      random permutation.  Equal keys fall to the lower field number, a bias of order 2^-32.  Under row references
+ *      b is the batch row, not the split row.  mapx_mask_distinct_keys returns the keys.
  * keys_out_opt [B*F] int32: the masked ids once more as the int32 row keys the embedding table's
  * catch-up and segment plan take (saves the mapx_ids_to_i32 launch at the head of the step). */
 int mapx_dynamic_mask_mfp(const int64_t* ids, int64_t B, int F, int L,
                           const int64_t* masked_index_in, uint64_t seed, uint64_t offset,
                           const int32_t* offset_dev, int64_t* ids_out, int64_t* labels,
-                          int64_t* masked_index_out, int32_t* keys_out_opt, hipStream_t stream);
+                          int64_t* masked_index_out, int32_t* keys_out_opt, int draw, hipStream_t stream);
+/* Test entry: keys [B,F] = key(b,f) of the distinct draw above, from the device function the mask kernels call. */
+int mapx_mask_distinct_keys(int64_t B, int F, uint64_t seed, uint64_t offset, const int32_t* offset_dev,
+                            uint32_t* keys, hipStream_t stream);
 /* mapx_dynamic_mask_mfp on batch rows that are still in the HBM-resident split: batch row b is row
  * sel[b] (0 <= sel[b] < N, caller-checked) of split_ids [N,F].  Replaces the DataLoader's collate of
  * trainer.py:51-58, 306-313 (and the row-gather + copy launches a resident split otherwise needs in
@@ -519,7 +533,7 @@ int mapx_dynamic_mask_mfp_rows(const int64_t* split_ids, int64_t N, const int64_
                                const int64_t* sel_cursor_dev_opt, int64_t B, int F, int L,
                                const int64_t* masked_index_in, uint64_t seed, uint64_t offset,
                                const int32_t* offset_dev, int64_t* ids_out, int64_t* labels,
-                               int64_t* masked_index_out, int32_t* keys_out_opt, hipStream_t stream);
+                               int64_t* masked_index_out, int32_t* keys_out_opt, int draw, hipStream_t stream);
 /* out [B,F] = rows sel[c .. c + B) of src [N,F] (c = *sel_cursor_dev_opt, 0 when NULL): the batch of an RFD or
  * finetune step cut from the HBM-resident split inside the step — the DataLoader's collate of trainer.py:51-58,
  * 122-129, 431-438 — so that a captured step walks an epoch's permutation by itself (mapx_step_advance moves the
@@ -529,13 +543,15 @@ int mapx_take_rows_i64(const int64_t* src, int64_t N, int F, const int64_t* sel,
                        const int64_t* sel_cursor_dev_opt, int64_t B, int64_t* out, float* out_f32_opt,
                        hipStream_t stream);
 /* trainer.py:233-262 (RFD).  mode = RFD_replace: 0 Unigram, 1 Uniform (idx_low/idx_high [F]),
- * 2 Whole-Uniform (ids 10..V-1), 3 Whole-Unigram; x_train [N,F] device-resident; labels f32 [B,F]. */
+ * 2 Whole-Uniform (ids 10..V-1), 3 Whole-Unigram; x_train [N,F] device-resident; labels f32 [B,F].
+ * draw: as in mapx_dynamic_mask_mfp.  Either way the field masked at position l of row b takes its replacement from
+ * words y, z, w of Philox(counter b*L + l), so the returned masked_index, injected again, reproduces the outputs. */
 int mapx_dynamic_mask_rfd(const int64_t* ids, int64_t B, int F, int L,
                           const int64_t* masked_index_in, const int64_t* replace_in,
                           const int64_t* x_train, int64_t N, int mode, const int64_t* idx_low,
                           const int64_t* idx_high, int64_t V, uint64_t seed, uint64_t offset,
                           const int32_t* offset_dev, int64_t* ids_out, float* labels,
-                          int64_t* masked_index_out, hipStream_t stream);
+                          int64_t* masked_index_out, int draw, hipStream_t stream);
 
 /* ------------------------------------------------------------------ optimizer (a13)
  * transformers-4.26 AdamW semantics (trainer.py:60-85).  sched [sched_len][2] f32 =

@@ -54,11 +54,72 @@ __global__ void bce_finalize_kernel(const float* __restrict__ part, int nblocks,
   if (threadIdx.x == 0) { out[0] = a * inv_n; out[1] = b * inv_n; out[2] = c * inv_n; }
 }
 
+// ---------------------------------------------------------------- distinct-field draw
+// sampling_method == "normal" (trainer.py:222, torch.randperm(F)[:L] per row): L DISTINCT fields per row, ordered.
+// Every (row b, field f) owns a 32-bit key, word f & 3 of the Philox draw with counter kMaskDistinctCtr | (b*ceil(F/4)
+// + f/4) (four fields share one 128-bit draw; bit 63 keeps these counters apart from the b*L + l counters of the
+// with-replacement draw and of the RFD replacement draws, which share seed and offset).  The row's fields sorted by
+// (key, f) are a uniform random permutation, and masked_index[b, r] is the field of rank r, r < L:
+//   rank(b, f) = #{ g : key(b,g) < key(b,f) or (key(b,g) == key(b,f) and g < f) }
+// i.e. argsort(keys, stable)[:, :L].  Equal keys are ordered by field number; two of a row's keys collide with
+// probability F^2 / 2^33, so the bias towards low field numbers is of order 2^-32 per pair.
+// These three functions are the one definition: both mask kernels and mask_distinct_keys_kernel call them.
+constexpr uint64_t kMaskDistinctCtr = 1ull << 63;
+__device__ inline Philox4 mask_key_draw(uint64_t seed, uint64_t offset, int64_t b, int nf4, int q) {
+  return philox4x32_10(seed, kMaskDistinctCtr | (uint64_t)(b * nf4 + q), offset);
+}
+__device__ inline uint32_t mask_key_word(const Philox4& r, int j) {
+  return j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w));
+}
+// rank[i] of field f0 + i, i < N.  The N fields lie inside one draw: N == 1, or N == 4 and f0 % 4 == 0 (ranks of
+// fields >= F are meaningless).  Nothing is shared between threads: a thread recomputes the row's ceil(F/4) draws
+// (6 at F = 23; the with-replacement form of the RFD kernel recomputes L = 6), so any F works and no LDS is held.
+template <int N>
+__device__ inline void mask_distinct_ranks(uint64_t seed, uint64_t offset, int64_t b, int F, int f0, int* rank) {
+  const int nf4 = (F + 3) >> 2;
+  const Philox4 mine = mask_key_draw(seed, offset, b, nf4, f0 >> 2);
+  uint32_t key[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    key[i] = mask_key_word(mine, (f0 + i) & 3);
+    rank[i] = 0;
+  }
+  for (int q = 0; q < nf4; ++q) {
+    const Philox4 r = mask_key_draw(seed, offset, b, nf4, q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int g = 4 * q + j;
+      const uint32_t kg = mask_key_word(r, j);
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+        rank[i] += (g < F && (kg < key[i] || (kg == key[i] && g < f0 + i))) ? 1 : 0;
+    }
+  }
+}
+
+// The keys themselves (tests restate the definition from them): keys[b, f].
+__global__ void __launch_bounds__(256) mask_distinct_keys_kernel(int64_t B, int F, uint64_t seed, uint64_t offset,
+                                                                 const int32_t* __restrict__ offset_dev,
+                                                                 uint32_t* __restrict__ keys) {
+  if (offset_dev) offset += (uint64_t)(uint32_t)*offset_dev;
+  const int nf4 = (F + 3) >> 2;
+  const int64_t total = B * F;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = e / F;
+    const int f = (int)(e - b * F);
+    keys[e] = mask_key_word(mask_key_draw(seed, offset, b, nf4, f >> 2), f & 3);
+  }
+}
+
 // MFP branch of dynamic_mask (trainer.py:224-232).  A block owns kMaskRows rows: all threads
 // copy them (coalesced), then one thread per row draws / applies its L masks.
-//   masked_index[b,l] ~ U{0..F-1} with replacement (sampling_method == "randint")
+//   DISTINCT = false: masked_index[b,l] ~ U{0..F-1} with replacement (sampling_method == "randint"), or injected
+//   DISTINCT = true:  masked_index[b,:] = the L-prefix of a random permutation (sampling_method == "normal"); one
+//                     thread per (row, four fields) ranks its fields and applies those of rank < L at l = rank
 //   labels[b,l] = ids[b, masked_index[b,l]];  ids_out = ids with those fields set to 3
 constexpr int kMaskRows = 32;
+template <bool DISTINCT>
 __global__ void __launch_bounds__(256) mask_mfp_kernel(const int64_t* __restrict__ ids, int64_t B,
                                                        int F, int L,
                                                        const int64_t* __restrict__ mi_in,
@@ -94,18 +155,36 @@ __global__ void __launch_bounds__(256) mask_mfp_kernel(const int64_t* __restrict
     }
     __threadfence_block();
     __syncthreads();
-    for (int64_t w = threadIdx.x; w < rows * L; w += blockDim.x) {     // draws: one per thread
-      const int64_t b = b0 + w / L, l = w % L;
-      int64_t f;
-      if (mi_in) {
-        f = mi_in[b * L + l];
-      } else {
-        const Philox4 r = philox4x32_10(seed, (uint64_t)(b * L + l), offset);
-        f = bounded(r.x, (uint32_t)F);
+    if constexpr (DISTINCT) {
+      const int nf4 = (F + 3) >> 2;
+      for (int64_t w = threadIdx.x; w < rows * nf4; w += blockDim.x) {   // four fields of a row per thread
+        const int64_t b = b0 + w / nf4;
+        const int f0 = 4 * (int)(w % nf4);
+        int rank[4];
+        mask_distinct_ranks<4>(seed, offset, b, F, f0, rank);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int f = f0 + j, l = rank[j];
+          if (f >= F || l >= L) continue;
+          if (mi_out) mi_out[b * L + l] = f;
+          labels[b * L + l] = ids[(sel ? row_of(b) : b) * F + f];
+          ids_out[b * F + f] = 3;
+        }
       }
-      if (mi_out) mi_out[b * L + l] = f;
-      labels[b * L + l] = ids[(sel ? row_of(b) : b) * F + f];
-      ids_out[b * F + f] = 3;  // '<mask>' (duplicates of f write the same value)
+    } else {
+      for (int64_t w = threadIdx.x; w < rows * L; w += blockDim.x) {     // draws: one per thread
+        const int64_t b = b0 + w / L, l = w % L;
+        int64_t f;
+        if (mi_in) {
+          f = mi_in[b * L + l];
+        } else {
+          const Philox4 r = philox4x32_10(seed, (uint64_t)(b * L + l), offset);
+          f = bounded(r.x, (uint32_t)F);
+        }
+        if (mi_out) mi_out[b * L + l] = f;
+        labels[b * L + l] = ids[(sel ? row_of(b) : b) * F + f];
+        ids_out[b * F + f] = 3;  // '<mask>' (duplicates of f write the same value)
+      }
     }
     __threadfence_block();
     __syncthreads();
@@ -125,6 +204,26 @@ __global__ void __launch_bounds__(256) mask_mfp_kernel(const int64_t* __restrict
 // One thread per (row, field) ELEMENT (round 3; before: one thread per row walked its F ids and its L dependent
 // draws alone — 34 us at the head of every RFD step): reads and writes are coalesced, every thread of a row
 // recomputes the row's L draws (Philox is cheap) and only the thread whose field is hit fetches the replacement.
+// DISTINCT (sampling_method == "normal", mask_distinct_ranks above): thread (b, f) needs only its own rank; with
+// rank < L it is masked at position l = rank and draws its replacement from the same words of the same
+// philox(seed, b*L + l, offset) as the with-replacement form, so an injected masked_index reproduces it.
+struct RfdReplace {
+  const int64_t* x_train; int64_t N; int mode; const int64_t* idx_low; const int64_t* idx_high; int64_t V; int F;
+};
+__device__ inline int64_t rfd_replacement(const RfdReplace& p, const Philox4& r, int64_t fl) {
+  // 64-bit draw from two words (N and V may exceed 2^32 in principle)
+  const uint64_t w = ((uint64_t)r.y << 32) | r.z;
+  if (p.mode == 0 || p.mode == 3) {
+    const uint64_t hi = (uint64_t)(((unsigned __int128)w * (unsigned __int128)p.N) >> 64);
+    const int64_t col = p.mode == 0 ? fl : (int64_t)bounded(r.w, (uint32_t)p.F);
+    return p.x_train[(int64_t)hi * p.F + col];
+  }
+  const int64_t lo = p.mode == 1 ? p.idx_low[fl] : 10;
+  const int64_t span = (p.mode == 1 ? p.idx_high[fl] : p.V) - lo;
+  return lo + (int64_t)(((unsigned __int128)w * (unsigned __int128)span) >> 64);
+}
+
+template <bool DISTINCT>
 __global__ void __launch_bounds__(256) mask_rfd_kernel(const int64_t* __restrict__ ids, int64_t B,
                                                        int F, int L,
                                                        const int64_t* __restrict__ mi_in,
@@ -138,6 +237,7 @@ __global__ void __launch_bounds__(256) mask_rfd_kernel(const int64_t* __restrict
                                                        float* __restrict__ labels,
                                                        int64_t* __restrict__ mi_out) {
   if (offset_dev) offset += (uint64_t)(uint32_t)*offset_dev;
+  const RfdReplace rep{x_train, N, mode, idx_low, idx_high, V, F};
   const int64_t total = B * F;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -145,25 +245,21 @@ __global__ void __launch_bounds__(256) mask_rfd_kernel(const int64_t* __restrict
     const int f = (int)(e - b * F);
     const int64_t orig = ids[e];
     int64_t out = orig;
-    for (int l = 0; l < L; ++l) {
-      const Philox4 r = philox4x32_10(seed, (uint64_t)(b * L + l), offset);
-      const int64_t fl = mi_in ? mi_in[b * L + l] : (int64_t)bounded(r.x, (uint32_t)F);
-      if (mi_out && f == 0) mi_out[b * L + l] = fl;
-      if (fl != f) continue;
-      if (replace_in) {
-        out = replace_in[b * L + l];
-      } else {
-        // 64-bit draw from two words (N and V may exceed 2^32 in principle)
-        const uint64_t w = ((uint64_t)r.y << 32) | r.z;
-        if (mode == 0 || mode == 3) {
-          const uint64_t hi = (uint64_t)(((unsigned __int128)w * (unsigned __int128)N) >> 64);
-          const int64_t col = mode == 0 ? fl : (int64_t)bounded(r.w, (uint32_t)F);
-          out = x_train[(int64_t)hi * F + col];
-        } else {
-          const int64_t lo = mode == 1 ? idx_low[fl] : 10;
-          const int64_t span = (mode == 1 ? idx_high[fl] : V) - lo;
-          out = lo + (int64_t)(((unsigned __int128)w * (unsigned __int128)span) >> 64);
-        }
+    if constexpr (DISTINCT) {
+      int l;
+      mask_distinct_ranks<1>(seed, offset, b, F, f, &l);
+      if (l < L) {
+        if (mi_out) mi_out[b * L + l] = f;
+        out = replace_in ? replace_in[b * L + l]
+                         : rfd_replacement(rep, philox4x32_10(seed, (uint64_t)(b * L + l), offset), f);
+      }
+    } else {
+      for (int l = 0; l < L; ++l) {
+        const Philox4 r = philox4x32_10(seed, (uint64_t)(b * L + l), offset);
+        const int64_t fl = mi_in ? mi_in[b * L + l] : (int64_t)bounded(r.x, (uint32_t)F);
+        if (mi_out && f == 0) mi_out[b * L + l] = fl;
+        if (fl != f) continue;
+        out = replace_in ? replace_in[b * L + l] : rfd_replacement(rep, r, fl);
       }
     }
     ids_out[e] = out;
@@ -214,12 +310,16 @@ extern "C" int mapx_bce_with_logits(const float* logits, const float* labels, in
 extern "C" int mapx_dynamic_mask_mfp(const int64_t* ids, int64_t B, int F, int L,
                                      const int64_t* masked_index_in, uint64_t seed, uint64_t offset,
                                      const int32_t* offset_dev, int64_t* ids_out, int64_t* labels,
-                                     int64_t* masked_index_out, int32_t* keys_out_opt, hipStream_t stream) {
+                                     int64_t* masked_index_out, int32_t* keys_out_opt, int draw,
+                                     hipStream_t stream) {
   using namespace mapx;
-  MAPX_REQUIRE(ids && ids_out && labels && B >= 0 && F > 0 && L >= 0, "dynamic_mask_mfp: bad arguments");
+  MAPX_REQUIRE(ids && ids_out && (labels || L == 0) && B >= 0 && F > 0 && L >= 0, "dynamic_mask_mfp: bad arguments");
   MAPX_REQUIRE(ids != ids_out, "dynamic_mask_mfp: in-place masking is not supported");
+  MAPX_REQUIRE(draw == 0 || draw == 1, "dynamic_mask_mfp: draw %d", draw);
+  const bool distinct = draw == 1 && !masked_index_in;
+  if (distinct) MAPX_REQUIRE(L <= F, "dynamic_mask_mfp: the distinct draw needs L <= F (L = %d, F = %d)", L, F);
   if (B == 0) return MAPX_OK;
-  hipLaunchKernelGGL(mask_mfp_kernel, dim3(grid_for(B, kMaskRows)), dim3(256), 0, stream, ids, B, F, L,
+  hipLaunchKernelGGL(distinct ? mask_mfp_kernel<true> : mask_mfp_kernel<false>, dim3(grid_for(B, kMaskRows)), dim3(256), 0, stream, ids, B, F, L,
                      masked_index_in, seed, offset, offset_dev, ids_out, labels, masked_index_out, keys_out_opt,
                      (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int64_t)0);
   return check_launch("dynamic_mask_mfp");
@@ -229,12 +329,17 @@ extern "C" int mapx_dynamic_mask_mfp_rows(const int64_t* split_ids, int64_t N, c
                                           const int64_t* sel_cursor_dev_opt, int64_t B, int F,
                                           int L, const int64_t* masked_index_in, uint64_t seed, uint64_t offset,
                                           const int32_t* offset_dev, int64_t* ids_out, int64_t* labels,
-                                          int64_t* masked_index_out, int32_t* keys_out_opt, hipStream_t stream) {
+                                          int64_t* masked_index_out, int32_t* keys_out_opt, int draw,
+                                          hipStream_t stream) {
   using namespace mapx;
-  MAPX_REQUIRE(split_ids && sel && ids_out && labels && B >= 0 && N > 0 && F > 0 && L >= 0 && sel_len >= 1,
+  MAPX_REQUIRE(split_ids && sel && ids_out && (labels || L == 0) && B >= 0 && N > 0 && F > 0 && L >= 0 &&
+                   sel_len >= 1,
                "dynamic_mask_mfp_rows: bad arguments");
+  MAPX_REQUIRE(draw == 0 || draw == 1, "dynamic_mask_mfp_rows: draw %d", draw);
+  const bool distinct = draw == 1 && !masked_index_in;
+  if (distinct) MAPX_REQUIRE(L <= F, "dynamic_mask_mfp_rows: the distinct draw needs L <= F (L = %d, F = %d)", L, F);
   if (B == 0) return MAPX_OK;
-  hipLaunchKernelGGL(mask_mfp_kernel, dim3(grid_for(B, kMaskRows)), dim3(256), 0, stream, split_ids, B, F, L,
+  hipLaunchKernelGGL(distinct ? mask_mfp_kernel<true> : mask_mfp_kernel<false>, dim3(grid_for(B, kMaskRows)), dim3(256), 0, stream, split_ids, B, F, L,
                      masked_index_in, seed, offset, offset_dev, ids_out, labels, masked_index_out, keys_out_opt, sel,
                      sel_cursor_dev_opt, N, sel_len);
   return check_launch("dynamic_mask_mfp_rows");
@@ -279,7 +384,7 @@ extern "C" int mapx_dynamic_mask_rfd(const int64_t* ids, int64_t B, int F, int L
                                      const int64_t* x_train, int64_t N, int mode,
                                      const int64_t* idx_low, const int64_t* idx_high, int64_t V,
                                      uint64_t seed, uint64_t offset, const int32_t* offset_dev,
-                                     int64_t* ids_out, float* labels, int64_t* masked_index_out,
+                                     int64_t* ids_out, float* labels, int64_t* masked_index_out, int draw,
                                      hipStream_t stream) {
   using namespace mapx;
   MAPX_REQUIRE(ids && ids_out && labels && B >= 0 && F > 0 && L >= 0, "dynamic_mask_rfd: bad arguments");
@@ -290,9 +395,22 @@ extern "C" int mapx_dynamic_mask_rfd(const int64_t* ids, int64_t B, int F, int L
     if (mode == 2) MAPX_REQUIRE(V > 10, "dynamic_mask_rfd: Whole-Uniform needs the vocabulary size");
   }
   MAPX_REQUIRE(ids != ids_out, "dynamic_mask_rfd: in-place replacement is not supported");
+  MAPX_REQUIRE(draw == 0 || draw == 1, "dynamic_mask_rfd: draw %d", draw);
+  const bool distinct = draw == 1 && !masked_index_in;
+  if (distinct) MAPX_REQUIRE(L <= F, "dynamic_mask_rfd: the distinct draw needs L <= F (L = %d, F = %d)", L, F);
   if (B == 0) return MAPX_OK;
-  hipLaunchKernelGGL(mask_rfd_kernel, dim3(grid_for(B * F, 256)), dim3(256), 0, stream, ids, B, F, L,
+  hipLaunchKernelGGL(distinct ? mask_rfd_kernel<true> : mask_rfd_kernel<false>, dim3(grid_for(B * F, 256)), dim3(256), 0, stream, ids, B, F, L,
                      masked_index_in, replace_in, x_train, N, mode, idx_low, idx_high, V, seed, offset,
                      offset_dev, ids_out, labels, masked_index_out);
   return check_launch("dynamic_mask_rfd");
+}
+
+extern "C" int mapx_mask_distinct_keys(int64_t B, int F, uint64_t seed, uint64_t offset, const int32_t* offset_dev,
+                                       uint32_t* keys, hipStream_t stream) {
+  using namespace mapx;
+  MAPX_REQUIRE(keys && B >= 0 && F > 0, "mask_distinct_keys: bad arguments");
+  if (B == 0) return MAPX_OK;
+  hipLaunchKernelGGL(mask_distinct_keys_kernel, dim3(grid_for(B * F, 256)), dim3(256), 0, stream, B, F, seed, offset,
+                     offset_dev, keys);
+  return check_launch("mask_distinct_keys");
 }

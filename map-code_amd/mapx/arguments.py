@@ -38,7 +38,7 @@ TRAINING_FLAGS = [
     ("no_cuda", bool, False, "refuse the GPU (mapx has no CPU path: raises)"),
     ("seed", int, 42, "seed for parameter init, shuffling, masks and negative sampling"),
     ("local_rank", int, -1, "rank inside the node; set from LOCAL_RANK under torchrun"),
-    ("sampling_method", str, "normal", "masked-field sampling: normal (no replacement) | randint"),
+    ("sampling_method", str, "normal", "masked-field sampling, drawn inside the mask kernels either way (same captured step): normal (L distinct fields per row) | randint (with replacement: a row may name a field twice)"),
     ("mask_ratio", float, 0.1, "fraction of fields masked / replaced per row"),
     ("pretrain", bool, False, "run self-supervised pretraining instead of CTR training"),
     ("pt_type", str, "MFP", "pretraining task: MFP | RFD"),

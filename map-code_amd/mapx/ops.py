@@ -1919,14 +1919,34 @@ def eval_metrics(logits, labels):
     return dict(auc=auc, logloss=ll, avg_logits=ml, avg_probs=mp, positives=int(npos), negatives=int(nneg))
 
 
+def _check_distinct(name, L, F):
+    if L > F:
+        raise ValueError(f"{name}: distinct=True draws L distinct fields per row and needs L <= F (L = {L}, F = {F})")
+
+
+def mask_distinct_keys(B, F, seed, offset, offset_dev=None, device="cuda"):
+    """-> int64 [B,F]: the unsigned 32-bit keys of the distinct draw (include/mapx_hip.h, mapx_dynamic_mask_mfp,
+    draw = 1), from the device function the mask kernels call.  masked_index of a distinct=True call is
+    argsort(keys, stable)[:, :L] for the same (seed, offset, offset_dev, B, F).  Test entry."""
+    keys = torch.empty(B, F, dtype=torch.int32, device=device)
+    require_gpu(keys)
+    check(lib.mapx_mask_distinct_keys(B, F, seed, offset, ptr(offset_dev), ptr(keys), stream()))
+    return keys.to(torch.int64) & 0xFFFFFFFF
+
+
 def dynamic_mask_mfp(ids, L, masked_index=None, seed=0, offset=0, offset_dev=None, sel=None, sel_cursor=None,
-                     batch=None):
+                     batch=None, distinct=False):
     """-> (masked ids [B,F], labels [B,L], masked_index [B,L])  (trainer.py:217-232).
+    Without `masked_index` the fields are drawn on the device: with replacement (sampling_method "randint"), or
+    distinct=True: L distinct fields per row, the ordered prefix of a random permutation ("normal"; needs L <= F).
     `sel` int64 [B]: `ids` is the whole HBM-resident split [N,F] and the batch is its rows sel.
     `sel_cursor` (device int64 scalar) + `batch`: sel is a whole epoch's permutation and the batch is
     sel[*cursor : *cursor + batch] (a captured step walks the epoch without host copies)."""
     require_gpu(ids)
     ids = ids.contiguous()
+    distinct = bool(distinct) and masked_index is None
+    if distinct:
+        _check_distinct("dynamic_mask_mfp", L, ids.shape[1])
     if sel is not None:
         require_gpu(sel)
         sel = sel.contiguous()
@@ -1937,7 +1957,8 @@ def dynamic_mask_mfp(ids, L, masked_index=None, seed=0, offset=0, offset_dev=Non
         mi_in = masked_index.contiguous() if masked_index is not None else None
         keys = torch.empty(B * F, dtype=torch.int32, device=ids.device)
         check(lib.mapx_dynamic_mask_mfp_rows(ptr(ids), ids.shape[0], ptr(sel), sel.numel(), ptr(sel_cursor), B, F, L, ptr(mi_in), seed, offset,
-                                             ptr(offset_dev), ptr(out), ptr(labels), ptr(mi_out), ptr(keys), stream()))
+                                             ptr(offset_dev), ptr(out), ptr(labels), ptr(mi_out), ptr(keys), int(distinct),
+                                             stream()))
         _keys_of[0], _keys_of[1] = out, keys
         return out, labels, mi_out
     B, F = ids.shape
@@ -1947,7 +1968,7 @@ def dynamic_mask_mfp(ids, L, masked_index=None, seed=0, offset=0, offset_dev=Non
     mi_in = masked_index.contiguous() if masked_index is not None else None
     keys = torch.empty(B * F, dtype=torch.int32, device=ids.device)
     check(lib.mapx_dynamic_mask_mfp(ptr(ids), B, F, L, ptr(mi_in), seed, offset, ptr(offset_dev), ptr(out),
-                                    ptr(labels), ptr(mi_out), ptr(keys), stream()))
+                                    ptr(labels), ptr(mi_out), ptr(keys), int(distinct), stream()))
     _keys_of[0], _keys_of[1] = out, keys        # Embeddings.forward asks ids_to_i32 for exactly this matrix next
     return out, labels, mi_out
 
@@ -1956,11 +1977,15 @@ RFD_MODES = {"Unigram": 0, "Uniform": 1, "Whole-Uniform": 2, "Whole-Unigram": 3}
 
 
 def dynamic_mask_rfd(ids, L, masked_index=None, replace_feat=None, x_train=None, seed=0, offset=0,
-                     offset_dev=None, mode="Unigram", idx_low=None, idx_high=None, vocab=0):
-    """-> (replaced ids [B,F], labels f32 [B,F], masked_index [B,L])  (trainer.py:233-240)."""
+                     offset_dev=None, mode="Unigram", idx_low=None, idx_high=None, vocab=0, distinct=False):
+    """-> (replaced ids [B,F], labels f32 [B,F], masked_index [B,L])  (trainer.py:233-240).
+    distinct=True (no `masked_index`): L distinct fields per row, as in dynamic_mask_mfp."""
     require_gpu(ids)
     ids = ids.contiguous()
     B, F = ids.shape
+    distinct = bool(distinct) and masked_index is None
+    if distinct:
+        _check_distinct("dynamic_mask_rfd", L, F)
     out = torch.empty_like(ids)
     labels = torch.empty(B, F, dtype=torch.float32, device=ids.device)
     mi_out = torch.empty(B, L, dtype=torch.int64, device=ids.device)
@@ -1971,7 +1996,7 @@ def dynamic_mask_rfd(ids, L, masked_index=None, replace_feat=None, x_train=None,
         raise NotImplementedError(mode)                     # trainer.py:261-262
     check(lib.mapx_dynamic_mask_rfd(ptr(ids), B, F, L, ptr(mi_in), ptr(rep), ptr(x_train), nrows,
                                     RFD_MODES[mode], ptr(idx_low), ptr(idx_high), int(vocab), seed, offset,
-                                    ptr(offset_dev), ptr(out), ptr(labels), ptr(mi_out), stream()))
+                                    ptr(offset_dev), ptr(out), ptr(labels), ptr(mi_out), int(distinct), stream()))
     return out, labels, mi_out
 
 

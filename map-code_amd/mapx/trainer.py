@@ -572,13 +572,14 @@ class Trainer:
         """One training step.  Full-size batches run from a captured hipGraph after a few eager
         steps: the whole step on one GPU; mask + forward + backward when a gradient exchange
         (N > 1) or gradient clipping needs host-side decisions before the optimizer.  Ragged
-        batches and host-side mask sampling ("normal") stay eager."""
+        batches stay eager.  Both mask sampling methods are drawn inside the mask kernels ("randint" with
+        replacement, "normal" distinct fields) from streams that advance with the device-side update counter."""
         fn = {"mfp": self._mfp_step, "rfd": self._rfd_step, "ctr": self._ctr_step}[kind]
         if isinstance(X, RowsRef) and kind == "mfp" and self.args.pt_type != "MFP":
             ref = X                                        # (the MFP mask kernel is what reads rows through `sel`)
             X, Y = ref.X, (ref.Y if Y is ref else Y)
         graphable = (self.use_graph and X.shape[0] == self.args.per_gpu_train_batch_size
-                     and (kind == "ctr" or self.args.sampling_method == "randint"))
+                     and (kind == "ctr" or self.args.sampling_method in ("randint", "normal")))
         if not graphable:
             return fn(X, Y)
         # (a step captured on row references walks the permutation by itself and cannot take tensor batches)
@@ -637,16 +638,14 @@ class Trainer:
         else:
             self._mask_calls += 1
             offset, offset_dev = (self.rank << 40) + (3 << 36) + self._mask_calls, None
-        if masked_index is None:
-            if sampling_method == "normal":        # L distinct fields per row (trainer.py:222)
-                masked_index = torch.rand(ids.shape[0] if sel is None else batch, F, device=ids.device,
-                                          generator=self._generator()).argsort(1)[:, :L].contiguous()
-            elif sampling_method != "randint":
-                raise NotImplementedError(sampling_method)
+        if sampling_method not in ("normal", "randint") and masked_index is None:
+            raise NotImplementedError(sampling_method)
+        # "normal": L distinct fields per row (trainer.py:222), "randint": with replacement — both drawn by the kernels
+        distinct = sampling_method == "normal" and masked_index is None
         if self.args.pt_type == "MFP":
             inputs["input_ids"], inputs["labels"], inputs["masked_index"] = ops.dynamic_mask_mfp(
                 ids, L, masked_index=masked_index, seed=seed, offset=offset, offset_dev=offset_dev, sel=sel,
-                sel_cursor=sel_cursor, batch=batch)
+                sel_cursor=sel_cursor, batch=batch, distinct=distinct)
         elif self.args.pt_type == "RFD":
             x_train = self._split(self.train_dataset).X
             cfg = self.model_config
@@ -658,7 +657,8 @@ class Trainer:
                 ids, L, masked_index=masked_index, replace_feat=replace_feat, x_train=x_train,
                 seed=seed, offset=offset, offset_dev=offset_dev, mode=self.args.RFD_replace,
                 idx_low=low if self.args.RFD_replace == "Uniform" else None,
-                idx_high=high if self.args.RFD_replace == "Uniform" else None, vocab=cfg.input_size)
+                idx_high=high if self.args.RFD_replace == "Uniform" else None, vocab=cfg.input_size,
+                distinct=distinct)
         else:
             raise NotImplementedError(self.args.pt_type)
         return inputs

@@ -1,7 +1,10 @@
 """Step time of the OTHER BASELINE configs on one GPU (no bench line: the headline metric is bench.py's MFP step):
 configs[3] DCNv2 + RFD (Unigram replacement) and configs[4] DCNv2 finetune (CTR), Avazu / Criteo shapes, batch 4096,
 the Trainer's own captured step.
-    python tools/step_bench.py --pt RFD|CTR|MFP [--workload avazu|criteo] [--dtype f32|bf16] [--steps 200]"""
+    python tools/step_bench.py --pt RFD|CTR|MFP [--workload avazu|criteo] [--dtype f32|bf16] [--steps 200]
+                               [--sampling randint|normal]
+--sampling: the pretraining steps' mask draw (--sampling_method of run.py): randint = with replacement (the run
+scripts' and bench.py's), normal = L distinct fields per row (run.py's default)."""
 import argparse
 import json
 import os
@@ -26,12 +29,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--preroll", type=int, default=200)
+    ap.add_argument("--sampling", default="randint", choices=["randint", "normal"])
     ap.add_argument("--tensors", action="store_true", help="deal the batches as tensors (A/B of the row references)")
     a = ap.parse_args()
     a.uniform = False
     device = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     tr, cfg, ids, labels, _ = bench.build(a, device, 0)
+    tr.args.sampling_method = a.sampling
     train = tr._begin("bench")
     gen = tr._generator()
     kind = a.pt.lower()
@@ -56,7 +61,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(json.dumps({"step": f"{a.model} {a.pt}", "workload": a.workload, "dtype": a.dtype, "batch": a.batch,
-                      "ms_per_step": 1e3 * dt / a.steps, "samples_per_s": a.batch * a.steps / dt,
+                      "sampling": a.sampling, "ms_per_step": 1e3 * dt / a.steps, "samples_per_s": a.batch * a.steps / dt,
                       "graphed": bool(tr.use_graph and live), "loss": float(out[0].detach())}))
 
 
