@@ -1078,6 +1078,10 @@ def gemm_bf16(a, b, a_kc, b_kc, M, N, K, out=None, out_dtype=BF16, ldc=None, epi
 # fp16 arithmetic (csrc/gemm_h2.hip), any other by the six-product bf16 one (csrc/gemm_x3.hip).  Here a record travels
 # as the attribute `_amax` of the tensor object: outputs of autograd Functions, saved INPUTS and gradients handed from
 # one backward node to the next keep their attributes; saved OUTPUTS and slices do not (carry / amax_pack below).
+# An attribute also survives what torch does to the tensor in place (autograd sums a fan-out's second gradient into the
+# first-arrived one), so tag() notes the tensor's version counter and amax_of() lets go of a record whose tensor has
+# been written through torch since (the product then takes the six-product arithmetic); a record of the eager ring
+# knows which hand-out it was and is not believed once its slot has gone to another tensor.
 H2 = os.environ.get("MAPX_GEMM_H2", "1") == "1"          # A/B switch: 0 = no records anywhere, x3 arithmetic only
 _epoch_word = {}
 _cap_pool = [None, 0]          # records of the capture in progress: (int32 [2 n] tensor, next free)
@@ -1128,31 +1132,44 @@ def amax_record(device):
     ring = _ring.get(key)
     if ring is None:
         ring = _ring[key] = [torch.zeros(REC * _RING, dtype=torch.int32, device=device), 0]
-    i = ring[1]
-    ring[1] = (i + 1) % _RING
+    n = ring[1]                   # hand-outs so far: this one's generation (its slot goes to hand-out n + _RING next)
+    ring[1] = n + 1
+    i = n % _RING
     rec = ring[0][REC * i:REC * (i + 1)]
     rec.zero_()
+    rec._ring, rec._ring_n = ring, n
     return rec
+
+
+def _recycled(rec):
+    """Has the ring slot of record `rec` been handed to another tensor since?"""
+    ring = getattr(rec, "_ring", None)
+    return ring is not None and ring[1] - rec._ring_n > _RING
 
 
 def amax_of(t):
     """The record of tensor `t`, or None.  A parameter's record is kept by the optimizer's kernel; when something else
-    wrote the parameter through torch (load_state_dict, copy_: its version counter moved) it is recomputed here."""
+    wrote the parameter through torch (load_state_dict, copy_: its version counter moved) it is recomputed here.
+    Any other tensor's record is dropped when the tensor was written through torch after tag() (an in-place add_ of
+    autograd's: the record no longer bounds it) or when its ring slot has been handed out again."""
     if not H2 or t is None:
         return None
     rec = getattr(t, "_amax", None)
     if rec is not None:
         ver = getattr(t, "_amax_ver", None)
-        if ver is not None and ver != t._version:
-            amax(t.detach(), rec=rec, reset=True)
-            t._amax_ver = t._version
-            refresh_weight_planes(t)
+        if ver is not None:
+            if ver != t._version:
+                amax(t.detach(), rec=rec, reset=True)
+                t._amax_ver = t._version
+                refresh_weight_planes(t)
+        elif getattr(t, "_amax_at", t._version) != t._version or _recycled(rec):
+            t._amax = rec = None
     return rec
 
 
 def tag(t, rec):
     if rec is not None and t is not None:
-        t._amax = rec
+        t._amax, t._amax_at = rec, t._version
     return t
 
 
@@ -1235,7 +1252,9 @@ def _check_record(x, rec, what):
 # Weight planes (include/mapx_hip.h: mapx_h2_weight_planes; csrc/gemm_h2w.hip): a weight that is operand B of large
 # products is cut into its two fp16 pieces once per optimizer step instead of once per row tile of every product.  The
 # optimizer owns the cache: `p._planes` {(b_kc, c0, c1): planes} on a parameter, filled at first use, refreshed by
-# MapxOptimizer right after the AdamW kernel (and by refresh_bf16 after anything else wrote the parameter).
+# MapxOptimizer right after the AdamW kernel (and by refresh_bf16 after anything else wrote the parameter); each set
+# is stamped with the update count it was cut at, and one that a captured step's refresh launch does not know is cut
+# again at its next use (PlaneClock below).
 H2W = os.environ.get("MAPX_GEMM_H2W", "1") == "1"
 
 
@@ -1270,24 +1289,70 @@ def weight_planes(w, b_kc, M):
         return None
     key = (bool(b_kc), c0, c1)
     pl = reg.get(key)
-    if pl is None:
+    clock = getattr(base, "_planes_clock", None)
+    if pl is None or (clock is not None and not clock.current(base, key)):
         if torch.cuda.is_current_stream_capturing():
-            return None               # (registered by the eager steps that precede a capture)
-        pl = reg[key] = h2_weight_planes(base.detach()[:, c0:c1] if (c0, c1) != (0, None) else base.detach(), b_kc, rec)
+            return None               # (registered by the eager steps that precede a capture; a stale set: cut in-kernel)
+        # first use, or a set no launch has re-cut since the optimizer last wrote the weight (registered after the
+        # step was captured): cut now, into the same buffer — a later capture may have its address baked in
+        pl = reg[key] = h2_weight_planes(base.detach()[:, c0:c1] if (c0, c1) != (0, None) else base.detach(), b_kc, rec,
+                                         out=pl)
+        if clock is not None:
+            base._planes_at[key] = clock.step
     return pl
 
 
-def refresh_weight_planes(params):
+class PlaneClock:
+    """How a plane set is known to be current.  `step` counts the optimizer's updates of the weights (MapxOptimizer
+    .steps_done lives here); every cut stamps its set with the count the weights are at (`p._planes_at[key]`).  A
+    captured step re-cuts, on every replay, exactly the sets that were registered when it was captured and runs no
+    Python doing so: the replay notes that frozen set of (id(p), key) as `covered` at the new count instead of
+    stamping each.  A set is current when its stamp or the covered note says so; any other — one first cut by an
+    eval between two replays — is cut again at its next use (weight_planes)."""
+    __slots__ = ("step", "covered", "covered_at")
+
+    def __init__(self):
+        self.step, self.covered, self.covered_at = 0, frozenset(), -1
+
+    def current(self, p, key):
+        return p._planes_at.get(key) == self.step or (self.covered_at == self.step and (id(p), key) in self.covered)
+
+    def replayed(self, keys):
+        """A captured optimizer step that re-cuts `keys` has been replayed."""
+        self.step += 1
+        self.covered, self.covered_at = keys, self.step
+
+    def covers(self, keys):
+        """Did the last update of the weights come from a replay that re-cut all of `keys`?"""
+        return self.covered_at == self.step and (self.covered is keys or keys <= self.covered)
+
+
+def plane_keys(params):
+    """The registered plane sets of the parameters as a frozenset of (id(p), key): what a refresh_weight_planes launch
+    captured now re-cuts on every replay."""
+    return frozenset((id(p), key) for p in params for key in (getattr(p, "_planes", None) or ()))
+
+
+def refresh_weight_planes(params, at=None, stamp=True, stale_only=False):
     """Re-cut every registered plane set of the parameters (their records must be current on this stream): one
-    launch per 16 sets."""
+    launch per 16 sets.  The sets are stamped with the update count `at` (default: the PlaneClock's present one;
+    stamp=False inside a capture, which runs no kernel); stale_only: only the sets that are not current."""
     if isinstance(params, torch.Tensor):
         params = [params]
     todo = []
     for p in params:
-        for (b_kc, c0, c1), pl in (getattr(p, "_planes", None) or {}).items():
+        reg = getattr(p, "_planes", None)
+        if not reg:
+            continue
+        clock = getattr(p, "_planes_clock", None)
+        for (b_kc, c0, c1), pl in reg.items():
+            if stale_only and (clock is None or clock.current(p, (b_kc, c0, c1))):
+                continue
             w = p.detach()[:, c0:c1] if (c0, c1) != (0, None) else p.detach()
             Nn, K = (w.shape[0], w.shape[1]) if b_kc else (w.shape[1], w.shape[0])
             todo.append((w, Nn, K, b_kc, p._amax, pl))
+            if stamp and clock is not None:
+                p._planes_at[(b_kc, c0, c1)] = clock.step if at is None else at
     for i in range(0, len(todo), 16):
         part = todo[i:i + 16]
         arr = (N.PlaneTask * len(part))()

@@ -136,7 +136,7 @@ class MapxOptimizer:
         self.sched = ops.make_sched(self.lr0, lambdas, b1, b2).to(dev)
         self.aux = ops.make_replay_aux(self.lr0, lambdas, b1, b2, self.wd).to(dev)
         self.done = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.steps_done = 0
+        self.steps_done = 0                         # (kept in an ops.PlaneClock: the weight planes' stamps are read against it)
         table_ids = model.table_parameter_ids()
         named = [(n, p) for n, p in model.named_parameters() if id(p) not in table_ids and p.requires_grad]
         self.dense_params = [p for _, p in named]
@@ -149,6 +149,9 @@ class MapxOptimizer:
                             (0.0, [(n, p) for n, p in named if not decays(n)])):
             if members:
                 self.groups.append(self._flatten(members, wd, dev, self.bf16))
+        for p in self.dense_params:
+            if getattr(p, "_planes", None) is not None:
+                p._planes_clock = self._clock
         self.refresh_bf16()
         names = {id(p): n for n, p in model.named_parameters()}
         self.tables = []
@@ -159,6 +162,31 @@ class MapxOptimizer:
         # (int64 device cursor, stride) of a captured step that walks the epoch's permutation: moved to the next
         # batch by the launch that advances the update counter (trainer.GraphedStep sets it around its capture)
         self.walk_cursor = None
+
+    @property
+    def steps_done(self):
+        return self._clock.step
+
+    @steps_done.setter
+    def steps_done(self, n):
+        if "_clock" not in self.__dict__:
+            self._clock = ops.PlaneClock()
+        self._clock.step = int(n)
+
+    def plane_keys(self):
+        """The plane sets registered now: what the refresh launches of an optimizer step captured now re-cut on every
+        replay (ops.PlaneClock)."""
+        return ops.plane_keys(self.dense_params)
+
+    def replayed(self, keys):
+        """A captured step() that re-cuts the plane sets `keys` has been replayed (a replay runs no Python)."""
+        self._clock.replayed(keys)
+
+    def planes_ready(self, keys):
+        """Before a captured forward that reads the plane sets `keys` is replayed: whatever wrote the weights last
+        re-cut them — else (another graph's replay that knows fewer sets) the stale ones are cut here."""
+        if keys and not self._clock.covers(keys):
+            ops.refresh_weight_planes(self.dense_params, stale_only=True)
 
     def backward_window(self, open_):
         """Between backward_window(True) and (False) — the Trainer brackets loss.backward() of a step
@@ -191,6 +219,7 @@ class MapxOptimizer:
                 p._amax = recs[i]
                 if p.dim() == 2:
                     p._planes = {}           # ops.weight_planes: filled at first use, refreshed behind every update
+                    p._planes_at = {}        # ... and the update count each set was cut at (ops.PlaneClock)
             view = flat_p[off:off + p.numel()].view_as(p)
             view.copy_(p.data)
             p.data = view
@@ -295,9 +324,12 @@ class MapxOptimizer:
         for g in self.groups:
             ops.adamw_dense(g["p"], g["g"], g["m"], g["v"], self.sched, self.done, b1, b2, eps, g["wd"],
                             shadow=g["h"], seg_off=g.get("seg_off"), seg_amax=g.get("amax"))
+        # the weights' fp16 pieces for the next step's products, stamped with the count step() is about to reach (a
+        # capture runs no kernel and stamps nothing: its replays report the sets they re-cut, MapxOptimizer.replayed)
+        eager = not torch.cuda.is_current_stream_capturing()
         for g in self.groups:
             if g.get("amax") is not None:
-                ops.refresh_weight_planes(g["params"])       # the weights' fp16 pieces for the next step's products
+                ops.refresh_weight_planes(g["params"], at=self.steps_done + 1, stamp=eager)
 
     def zero_grad(self):
         """Dense gradients are overwritten by the next backward (see layers._grad_slot); only

@@ -175,6 +175,8 @@ class GraphedStep:
             # the capture pass ran the Python bookkeeping but no kernel
             trainer.optimizer.walk_cursor = None
             trainer.global_step, trainer.optimizer.steps_done = gs, sd
+        # the weight planes this graph reads and re-cuts: the sets registered by now, for good (ops.PlaneClock)
+        self.plane_keys = trainer.optimizer.plane_keys()
 
     def __call__(self, X, Y):
         if self.walk:
@@ -194,10 +196,11 @@ class GraphedStep:
             self.X.copy_(X)
             if self.Y is not self.X:
                 self.Y.copy_(Y)
+        opt = self.trainer.optimizer
+        opt.planes_ready(self.plane_keys)
         self.graph.replay()
         # the step's host-side effects (a replay runs no Python)
-        opt = self.trainer.optimizer
-        opt.steps_done += 1
+        opt.replayed(self.plane_keys)           # steps_done += 1; plane sets registered since the capture are stale now
         for t in opt.tables:
             t.stale = True
         self.trainer.global_step += 1
@@ -270,6 +273,7 @@ class GraphedBackward:
             if self.early:
                 layers.plan_observers.remove(publish)
         self.sparse = [tb.sparse_grad for tb in tables]
+        self.plane_keys = trainer.optimizer.plane_keys()        # the weight planes the captured forward reads
         if self.early:
             with_grad = [i for i, tb in enumerate(tables) if tb.sparse_grad is not None]
             if sorted(self.published) != with_grad:
@@ -332,6 +336,7 @@ class GraphedBackward:
         self.X.copy_(X)
         if self.Y is not self.X:
             self.Y.copy_(Y)
+        self.trainer.optimizer.planes_ready(self.plane_keys)
         self._t_launch = time.perf_counter()
         self.graph.replay()
         self.replays += 1
@@ -405,6 +410,7 @@ class GraphedExchangeTail:
             opt.steps_done = sd                         # the capture ran the bookkeeping but no kernel
             for tb, sg in zip(tables, saved):
                 tb.sparse_grad = sg
+        self.plane_keys = opt.plane_keys()              # the weight planes the captured optimizer step re-cuts
 
     def __call__(self, host_s):
         opt = self.trainer.optimizer
@@ -416,7 +422,7 @@ class GraphedExchangeTail:
         host_s[3] += time.perf_counter() - t0
         parallel.all_gather_tables(self.msgs, self.gathered)
         self.merge.replay()
-        opt.steps_done += 1
+        opt.replayed(self.plane_keys)                   # steps_done += 1; plane sets this capture does not know are stale
         for t in opt.tables:
             if t.table.sparse_grad is not None:
                 t.table.sparse_grad = None
