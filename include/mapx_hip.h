@@ -770,6 +770,51 @@ int mapx_fgcnn_conv_bwd(const float* g, const float* z, const float* x, const fl
 int mapx_inner_product_fwd(const float* x, int64_t B, int T, int E, float* out, hipStream_t stream);
 int mapx_inner_product_bwd(const float* g, const float* x, int64_t B, int T, int E, float* dx, hipStream_t stream);
 
+/* ------------------------------------------------------------------ FiGNN backbone
+ * layers.py:300-379 (GraphLayer, FiGNNBlock, AttentionalPrediction), models.py:410-438.  All tensors fp32, dense and
+ * 16-byte aligned; x and every h are [B,F,E], 2 <= F <= 64, E % 4 == 0, E <= 32.  No atomics: bitwise deterministic.
+ *
+ * graph_fwd   s[b,i] = w_attn[:E] . x[b,i], d[b,j] = w_attn[E:] . x[b,j], pre = s_i + d_j, alpha = leaky_relu(pre, 0.01)
+ *             with the diagonal at -inf, g[b,i,:] = softmax_j(alpha): g [B,F,F] (g_ii = 0), s and d [B,F].
+ * layer_fwd   h_out_i = W_out[i] h_i, aggr = g h_out, a_i = W_in[i] aggr_i + bias_p, GRUCell(a, h) (gates r, z, n),
+ *             h_next = (1-z) n + z h (+ x_res_opt).  w_in / w_out [F,E,E], w_ih / w_hh [3E,E], b_ih / b_hh [3E].
+ *             weights_staged(F, E, backward) -> 1 when W_in and W_out sit in LDS next to the tile, 0 when they are
+ *             streamed, -1 for a shape outside the range.
+ * layer_bwd   recomputes the layer from its input h and g, then from dh_next: dh (a buffer other than dh_next),
+ *             dg [B,F,F] (written when dg_init, else added to), dx_acc_opt [B,F,E] (res_conn: = or += dh_next by
+ *             dx_init), and ws [B,F,8,E] = {a, aggr, da, dh_out, dr, dz, dn, dhn} for the weight gradients.
+ * layer_wgrad from ws and h: dW_in[i] = sum_b da_i (x) aggr_i, dW_out[i] = sum_b dh_out_i (x) h_i, dbias_p = sum da,
+ *             dW_ih = sum dgi (x) a, dW_hh = sum dgh (x) h, db_ih, db_hh; partial rows per 64 samples (part_field
+ *             [groups(B,F,0), 2 F E E]) and per 64 (sample, field) rows (part_gru [groups(B,F,1), 6 E E + 7 E]), added in
+ *             order in fp64.  add_layer: dW_in, dW_out, dbias_p are added to, not overwritten (reuse_graph_layer);
+ *             add_gru: likewise the four GRU gradients (the cell is shared by all layers).
+ * graph_bwd   dalpha = g (dg - sum_j g dg) times the slope at pre = s_i + d_j; ds = row sums, dd = column sums;
+ *             dx = dx_base (+ dx_add_opt) + ds w_attn[:E] + dd w_attn[E:] (dx may be dx_base); dw_attn [2E] from the
+ *             partial rows part [graph_bwd_groups(B), 2E].
+ * pred_fwd    logits[b] = sum_f sigmoid(z2[b,f]) score[b,f];  pred_bwd: dscore = g sigmoid(z2),
+ *             dz2 = g score sigmoid'(z2). */
+int mapx_fignn_weights_staged(int F, int E, int backward);
+int mapx_fignn_graph_fwd(const float* x, const float* w_attn, int64_t B, int F, int E, float* g, float* s, float* d,
+                         hipStream_t stream);
+int mapx_fignn_graph_bwd_groups(int64_t B);
+int mapx_fignn_graph_bwd(const float* dg, const float* g, const float* s, const float* d, const float* x,
+                         const float* w_attn, const float* dx_base, const float* dx_add_opt, int64_t B, int F, int E,
+                         float* dx, float* part, float* dw_attn, hipStream_t stream);
+int mapx_fignn_layer_fwd(const float* h, const float* g, const float* x_res_opt, const float* w_in, const float* w_out,
+                         const float* bias_p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         int64_t B, int F, int E, float* h_next, hipStream_t stream);
+int mapx_fignn_layer_bwd(const float* dh_next, const float* h, const float* g, const float* w_in, const float* w_out,
+                         const float* bias_p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         int64_t B, int F, int E, float* dh, float* dg, int dg_init, float* dx_acc_opt, int dx_init,
+                         float* ws, hipStream_t stream);
+int mapx_fignn_wgrad_groups(int64_t B, int F, int gru);
+int mapx_fignn_layer_wgrad(const float* ws, const float* h, int64_t B, int F, int E, float* part_field, float* part_gru,
+                           float* dw_in, float* dw_out, float* dbias_p, float* dw_ih, float* dw_hh, float* db_ih,
+                           float* db_hh, int add_layer, int add_gru, hipStream_t stream);
+int mapx_fignn_pred_fwd(const float* score, const float* z2, int64_t B, int F, float* logits, hipStream_t stream);
+int mapx_fignn_pred_bwd(const float* g_logits, const float* score, const float* z2, int64_t B, int F, float* dscore,
+                        float* dz2, hipStream_t stream);
+
 /* ------------------------------------------------------------------ state fingerprint (replica-consistency check)
  * No reference site: the reference trains unsynchronised replicas and never compares them.  An
  * order-independent 64-bit integer fingerprint of n_words raw 32-bit words (bit patterns: -0.0 != +0.0, NaN payloads

@@ -1387,3 +1387,165 @@ class FGCNNBlock(nn.Module):
                 r = _Act.apply(r, self.act, None)
             new.append(r.reshape(B, -1, self.embedding_dim))
         return torch.cat(new, dim=1)
+
+
+# ----------------------------------------------------------------------------- FiGNN
+class _FiGNNTrunk(Function):
+    """FiGNNBlock.forward (reference layers.py:333-365) as one autograd node over csrc/fignn.hip: the attention graph
+    once, then one launch per layer (GraphLayer + the shared GRUCell + the optional residual).  Saved for backward: x,
+    the graph g with its two projections s and d, and every layer's input h; the layer's intermediates are recomputed.
+    Backward walks the layers in reverse (one recompute-and-backward launch, then the weight gradients from per-chunk
+    partials added in a fixed order), accumulating dg and — res_conn — dx, and ends in the graph's backward.  The
+    shared GRU's gradients, and with reuse_graph_layer the one GraphLayer's, are added up in that (layer) order."""
+
+    @staticmethod
+    def forward(ctx, x, w_attn, w_ih, w_hh, b_ih, b_hh, res_conn, reuse, num_layers, *layer_params):
+        x = x.contiguous()
+        g, s, d = ops.fignn_graph_fwd(x, w_attn)
+        hs = [x]
+        for l in range(num_layers):
+            w_in, w_out, bias_p = layer_params[0:3] if reuse else layer_params[3 * l:3 * l + 3]
+            hs.append(ops.fignn_layer_fwd(hs[-1], g, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh,
+                                          x_res=x if res_conn else None))
+        ctx.cfg = (bool(res_conn), bool(reuse), int(num_layers))
+        ctx.params = (w_attn, w_ih, w_hh, b_ih, b_hh) + tuple(layer_params)
+        ctx.slots = tuple(_grad_slot(p) for p in ctx.params)
+        ctx.save_for_backward(g, s, d, *hs[:-1])
+        return hs[-1]
+
+    @staticmethod
+    def backward(ctx, dh):
+        g, s, d, *hs = ctx.saved_tensors
+        res_conn, reuse, L = ctx.cfg
+        w_attn, w_ih, w_hh, b_ih, b_hh = ctx.params[:5]
+        layer_params = ctx.params[5:]
+        x = hs[0]
+        B, F, E = x.shape
+        # destinations: the optimizer's slots, else fresh tensors handed back to autograd
+        dst = [sl if sl is not None else torch.empty_like(p) for sl, p in zip(ctx.slots, ctx.params)]
+        dg = torch.empty_like(g)
+        dx_acc = torch.empty_like(x) if res_conn else None
+        ws = torch.empty(B, F, ops.FIGNN_WS_VECS, E, dtype=torch.float32, device=x.device)
+        dh = dh.contiguous()
+        for l in reversed(range(L)):
+            first = l == L - 1
+            k = 0 if reuse else 3 * l
+            dh, _ = ops.fignn_layer_bwd(dh, hs[l], g, *layer_params[k:k + 3], w_ih, w_hh, b_ih, b_hh, dg, first,
+                                        dx_acc=dx_acc, dx_init=first, grads=dst[5 + k:5 + k + 3] + dst[1:5],
+                                        add_layer=reuse and not first, add_gru=not first, ws=ws)
+        dx, _ = ops.fignn_graph_bwd(dg, g, s, d, x, w_attn, dh, dx_add=dx_acc, dw_attn=dst[0], inplace=True)
+        grads = [None if sl is not None else t for sl, t in zip(ctx.slots, dst)]
+        return (dx, *grads[:5], None, None, None, *grads[5:])
+
+
+class GraphLayer(nn.Module):
+    """Reference layers.py:300-313: per-field E x E matrices `W_in`, `W_out` [F,E,E] (xavier_normal_) and `bias_p` [E]
+    (zeros).  Read by the FiGNN kernels only (`_mapx_row_resident`: the optimizer keeps no weight planes for them)."""
+
+    def __init__(self, config):
+        super().__init__()
+        F, E = config.num_fields, config.embed_size
+        self.W_in = nn.Parameter(torch.empty(F, E, E))
+        self.W_out = nn.Parameter(torch.empty(F, E, E))
+        nn.init.xavier_normal_(self.W_in)
+        nn.init.xavier_normal_(self.W_out)
+        self.bias_p = nn.Parameter(torch.zeros(E))
+
+
+class _GRUCellWeights(nn.Module):
+    """The parameters of an nn.GRUCell(E, E): `weight_ih`, `weight_hh` [3E,E], `bias_ih`, `bias_hh` [3E], gate order
+    r, z, n, all U(-1/sqrt(E), 1/sqrt(E))."""
+
+    def __init__(self, input_size, hidden_size):
+        super().__init__()
+        self.weight_ih = nn.Parameter(torch.empty(3 * hidden_size, input_size))
+        self.weight_hh = nn.Parameter(torch.empty(3 * hidden_size, hidden_size))
+        self.bias_ih = nn.Parameter(torch.empty(3 * hidden_size))
+        self.bias_hh = nn.Parameter(torch.empty(3 * hidden_size))
+        bound = 1.0 / math.sqrt(hidden_size)
+        with torch.no_grad():
+            for p in self.parameters():
+                p.uniform_(-bound, bound)
+
+
+class FiGNNBlock(nn.Module):
+    """Reference layers.py:316-365: `gnn` (one GraphLayer per layer, or ONE with reuse_graph_layer), `gru`
+    (nn.GRUCell(E, E), shared by all layers) and `W_attn` (Linear(2E, 1, bias=False))."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.num_fields = config.num_fields
+        self.embedding_dim = config.embed_size
+        self.gnn_layers = int(config.num_hidden_layers)
+        self.use_residual = bool(config.res_conn)
+        self.reuse_graph_layer = bool(config.reuse_graph_layer)
+        if self.reuse_graph_layer:
+            self.gnn = GraphLayer(config)
+        else:
+            self.gnn = nn.ModuleList([GraphLayer(config) for _ in range(self.gnn_layers)])
+        self.gru = _GRUCellWeights(config.embed_size, config.embed_size)
+        self.W_attn = _ProjWeight(config.embed_size * 2, 1)
+        for p in self.parameters():
+            p._mapx_row_resident = True
+
+    def forward(self, feat_embed):
+        layers = [self.gnn] if self.reuse_graph_layer else list(self.gnn)
+        flat = [p for gl in layers for p in (gl.W_in, gl.W_out, gl.bias_p)]
+        return _FiGNNTrunk.apply(feat_embed, self.W_attn.weight, self.gru.weight_ih, self.gru.weight_hh,
+                                 self.gru.bias_ih, self.gru.bias_hh, self.use_residual, self.reuse_graph_layer,
+                                 self.gnn_layers, *flat)
+
+
+class _BiasFreeLinear(Function):
+    """y = x W^T on the existing GEMM / streaming kernels (the AutoInt projections' calls), dW into the optimizer's slot."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x = x.contiguous()
+        M, K = x.shape
+        Nn = w.shape[0]
+        ctx.slot = _grad_slot(w)
+        ctx.save_for_backward(x, w)
+        if ops._skinny(Nn, K, x, w):
+            return ops.linear_fwd(x, w, None)
+        return ops.gemm(x, w, True, True, M, Nn, K)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        dw = ops.linear_bwd_weight(gy, x, out=ctx.slot)
+        dx = ops.linear_bwd_input(gy, w) if ctx.needs_input_grad[0] else None
+        return dx, (None if ctx.slot is not None else dw)
+
+
+class _AttnPredict(Function):
+    """logits = sum_f sigmoid(z2) score (reference layers.py:375-379), csrc/fignn.hip."""
+
+    @staticmethod
+    def forward(ctx, score, z2):
+        score, z2 = score.contiguous(), z2.contiguous()
+        ctx.save_for_backward(score, z2)
+        return ops.fignn_pred_fwd(score, z2)
+
+    @staticmethod
+    def backward(ctx, g):
+        score, z2 = ctx.saved_tensors
+        return ops.fignn_pred_bwd(g, score, z2)
+
+
+class AttentionalPrediction(nn.Module):
+    """Reference layers.py:368-379: `linear1` = Linear(E, 1, bias=False), `linear2` = Sequential(Linear(F E, F,
+    bias=False), Sigmoid()) — keys `linear1.weight`, `linear2.0.weight`; the sigmoid is inside the combining kernel."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.linear1 = _ProjWeight(config.embed_size, 1)
+        self.linear2 = nn.ModuleDict({"0": _ProjWeight(config.num_fields * config.embed_size, config.num_fields)})
+
+    def forward(self, h):
+        B, F, E = h.shape
+        h = h.contiguous()
+        score = _BiasFreeLinear.apply(h.view(B * F, E), self.linear1.weight).view(B, F)
+        z2 = _BiasFreeLinear.apply(h.view(B, F * E), self.linear2["0"].weight)
+        return _AttnPredict.apply(score, z2)

@@ -1,7 +1,7 @@
 """BaseModel + DCNV2 (host mirror of reference code/models.py:21-127, 282-322): same factory,
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
 is a gfx950 kernel.  The other backbones the factory builds: DNN, DeepFM, xDeepFM, AutoInt, trans, fgcnn
-(fignn raises)."""
+(from_config still refuses fignn; build_backbone and the FiGNN class build it)."""
 import logging
 
 import torch
@@ -9,8 +9,8 @@ from torch import nn
 
 from . import ops
 from .arguments import Config
-from .layers import (_JoinColumns, CIN, CrossNetV2, Embeddings, FGCNNBlock, HipLinear, MLPBlock,
-                     MultiHeadSelfAttention, RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer,
+from .layers import (_JoinColumns, AttentionalPrediction, CIN, CrossNetV2, Embeddings, FGCNNBlock, FiGNNBlock,
+                     HipLinear, MLPBlock, MultiHeadSelfAttention, RowTable, TableWeight, TransformerEncoder, TransformerEncoderLayer,
                      bce_with_logits, field_pool, fm_product_sum, inner_product, to_bf16)
 from .nce import IndexLinear
 
@@ -745,3 +745,60 @@ class FGCNN(BaseModel):
         if self.dnn is not None:
             dense_input = self.dnn(dense_input)
         return self.get_outputs(self.fc_out(dense_input), labels)
+
+
+class FiGNN(BaseModel):
+    """Field interactions on a per-sample attention graph (reference models.py:410-438): Embeddings -> FiGNNBlock
+    (the graph from W_attn once, then num_hidden_layers steps of GraphLayer + one shared GRUCell, optional residual to
+    the embeddings, optionally ONE GraphLayer for all steps) -> the flattened [B, F*E] state feeds the MFP / RFD heads,
+    or `fc` = AttentionalPrediction.  Only embed_size is used (the reference warns that hidden_size should equal it
+    and goes on).  The trunk is csrc/fignn.hip: fp32, embed_size % 4 == 0 and <= 32, 2 <= num_fields <= 64."""
+    used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
+                   "res_conn", "reuse_graph_layer"]
+    MAX_FIELDS, MAX_EMBED = ops.FIGNN_MAX_FIELDS, ops.FIGNN_MAX_EMBED
+
+    def __init__(self, config: Config):
+        super().__init__(model_name="FiGNN", config=config)
+        from .layers import compute_dtype_of
+        if compute_dtype_of(config) != torch.float32:
+            raise NotImplementedError("compute_dtype=bf16 is not built for fignn: its graph / GRU kernels are fp32")
+        E, F, L = int(config.embed_size), int(config.num_fields), int(config.num_hidden_layers)
+        if E % 4 or E < 4 or E > self.MAX_EMBED:
+            raise NotImplementedError(f"fignn: the graph / GRU kernels take embed_size % 4 == 0 and <= {self.MAX_EMBED} "
+                                      f"(embed_size={E})")
+        if F < 2 or F > self.MAX_FIELDS:
+            raise NotImplementedError(f"fignn: the graph kernels take 2 <= num_fields <= {self.MAX_FIELDS} "
+                                      f"(num_fields={F}; with one field the reference's masked softmax is NaN)")
+        if L < 1:
+            raise NotImplementedError(f"fignn: num_hidden_layers >= 1 graph steps (num_hidden_layers={L})")
+        if int(config.hidden_size) != E:
+            logger.warning("this model requires embed_size == hidden_size, only uses embed_size")
+        self.embed = Embeddings(config)
+        self.embed.defer_plan = True
+        self.fignn = FiGNNBlock(config)
+        if config.pretrain:
+            self.create_pretraining_predictor(F * E)
+        else:
+            self.fc = AttentionalPrediction(config)
+
+    def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
+        x = self.embed(input_ids)
+        nce_idx, early = self._sample_early(labels, masked_index, noise_samples)
+        h = self.fignn(x)
+        self._plans_and_join(nce_idx, early)
+        if self.config.pretrain:
+            return self.get_outputs(h.flatten(start_dim=1), labels, masked_index, noise_samples=noise_samples,
+                                    nce_idx=nce_idx)
+        return self.get_outputs(self.fc(h), labels)
+
+
+def build_backbone(config: Config):
+    """Every model name the reference's factory reaches: FiGNN here, the other seven through BaseModel.from_config
+    (which still refuses fignn, as two tests pin; making it delegate is a one-line follow-up)."""
+    if str(config.model_name).lower() == "fignn":
+        from .layers import compute_dtype_of
+        if compute_dtype_of(config) != torch.float32:
+            raise NotImplementedError("compute_dtype=bf16 is built for DCNv2, DNN, DeepFM and AutoInt, "
+                                      f"not {config.model_name}")
+        return FiGNN(config)
+    return BaseModel.from_config(config)

@@ -152,6 +152,16 @@ SIGNATURES = {
     "mapx_fgcnn_conv_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "mapx_inner_product_fwd": (_i, [_p, _i64, _i, _i, _p, _p]),
     "mapx_inner_product_bwd": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
+    "mapx_fignn_weights_staged": (_i, [_i, _i, _i]),
+    "mapx_fignn_graph_fwd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p, _p]),
+    "mapx_fignn_graph_bwd_groups": (_i, [_i64]),
+    "mapx_fignn_graph_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
+    "mapx_fignn_layer_fwd": (_i, [_p] * 10 + [_i64, _i, _i, _p, _p]),
+    "mapx_fignn_layer_bwd": (_i, [_p] * 10 + [_i64, _i, _i, _p, _p, _i, _p, _i, _p, _p]),
+    "mapx_fignn_wgrad_groups": (_i, [_i64, _i, _i]),
+    "mapx_fignn_layer_wgrad": (_i, [_p, _p, _i64, _i, _i] + [_p] * 9 + [_i, _i, _p]),
+    "mapx_fignn_pred_fwd": (_i, [_p, _p, _i64, _i, _p, _p]),
+    "mapx_fignn_pred_bwd": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p]),
 }
 
 

@@ -848,6 +848,138 @@ def inner_product_bwd(g, x3):
     return dx
 
 
+# --------------------------------------------------------------------------- FiGNN (csrc/fignn.hip)
+FIGNN_MAX_FIELDS, FIGNN_MAX_EMBED = 64, 32          # csrc/fignn.hip kGnMaxF, kGnMaxE
+FIGNN_WS_VECS = 8                                   # workspace vectors per (sample, field) row: kWsVecs
+
+
+def _gn_f32c(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("fignn kernels take contiguous fp32 tensors")
+
+
+def _gn_layer_weights(F, E, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh):
+    want = ((F, E, E), (F, E, E), (E,), (3 * E, E), (3 * E, E), (3 * E,), (3 * E,))
+    got = tuple(tuple(t.shape) for t in (w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh))
+    if got != want:
+        raise ValueError(f"fignn layer: weights {got} do not fit F={F}, E={E} (want {want})")
+
+
+def fignn_weights_staged(F, E, backward=False):
+    """True: the layer kernels keep W_in / W_out in LDS at this shape; False: they stream them through L2."""
+    rc = lib.mapx_fignn_weights_staged(int(F), int(E), int(bool(backward)))
+    if rc < 0:
+        raise ValueError(f"fignn: num_fields={F}, embed_size={E} is outside the kernels' range")
+    return bool(rc)
+
+
+def fignn_graph_fwd(x3, w_attn):
+    """x3 [B,F,E], w_attn [1,2E] -> (g [B,F,F], s [B,F], d [B,F]): the attention graph without self-loops."""
+    require_gpu(x3, w_attn)
+    _gn_f32c(x3, w_attn)
+    B, F, E = x3.shape
+    if w_attn.numel() != 2 * E:
+        raise ValueError(f"fignn_graph_fwd: W_attn {tuple(w_attn.shape)} does not fit embed_size={E}")
+    g = torch.empty(B, F, F, dtype=torch.float32, device=x3.device)
+    s = torch.empty(B, F, dtype=torch.float32, device=x3.device)
+    d = torch.empty(B, F, dtype=torch.float32, device=x3.device)
+    check(lib.mapx_fignn_graph_fwd(ptr(x3), ptr(w_attn), B, F, E, ptr(g), ptr(s), ptr(d), stream()))
+    return g, s, d
+
+
+def fignn_graph_bwd(dg, g, s, d, x3, w_attn, dx_base, dx_add=None, dw_attn=None, inplace=False):
+    """-> (dx = dx_base (+ dx_add) + the graph's input gradient, dW_attn); `inplace`: dx is written over dx_base."""
+    require_gpu(dg, g, s, d, x3, w_attn, dx_base, dx_add, dw_attn)
+    _gn_f32c(dg, g, s, d, x3, w_attn, dx_base, dx_add, dw_attn)
+    B, F, E = x3.shape
+    if tuple(g.shape) != (B, F, F) or dg.shape != g.shape or tuple(s.shape) != (B, F) or d.shape != s.shape \
+            or dx_base.shape != x3.shape or (dx_add is not None and dx_add.shape != x3.shape) \
+            or w_attn.numel() != 2 * E or (dw_attn is not None and dw_attn.numel() != 2 * E):
+        raise ValueError(f"fignn_graph_bwd: operands do not fit x {tuple(x3.shape)}")
+    dx = dx_base if inplace else torch.empty_like(x3)
+    part = torch.empty(lib.mapx_fignn_graph_bwd_groups(B), 2 * E, dtype=torch.float32, device=x3.device)
+    dw_attn = torch.empty_like(w_attn) if dw_attn is None else dw_attn
+    check(lib.mapx_fignn_graph_bwd(ptr(dg), ptr(g), ptr(s), ptr(d), ptr(x3), ptr(w_attn), ptr(dx_base), ptr(dx_add), B, F,
+                                   E, ptr(dx), ptr(part), ptr(dw_attn), stream()))
+    return dx, dw_attn
+
+
+def fignn_layer_fwd(h, g, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh, x_res=None):
+    """One GraphLayer + GRUCell step (+ x_res): h [B,F,E], g [B,F,F] -> h_next [B,F,E]."""
+    require_gpu(h, g, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh, x_res)
+    _gn_f32c(h, g, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh, x_res)
+    B, F, E = h.shape
+    _gn_layer_weights(F, E, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh)
+    if tuple(g.shape) != (B, F, F) or (x_res is not None and x_res.shape != h.shape):
+        raise ValueError(f"fignn_layer_fwd: g {tuple(g.shape)} / x_res do not fit h {tuple(h.shape)}")
+    out = torch.empty_like(h)
+    check(lib.mapx_fignn_layer_fwd(ptr(h), ptr(g), ptr(x_res), ptr(w_in), ptr(w_out), ptr(bias_p), ptr(w_ih), ptr(w_hh),
+                                   ptr(b_ih), ptr(b_hh), B, F, E, ptr(out), stream()))
+    return out
+
+
+def fignn_layer_bwd(dh_next, h, g, w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh, dg, dg_init, dx_acc=None, dx_init=True,
+                    grads=None, add_layer=False, add_gru=False, ws=None):
+    """Backward of fignn_layer_fwd from dh_next: -> (dh, grads).  dg [B,F,F] and dx_acc [B,F,E] (res_conn) are written
+    (`*_init`) or added to; grads = [dW_in, dW_out, dbias_p, dW_ih, dW_hh, db_ih, db_hh] (given: the destinations,
+    overwritten or — add_layer for the first three, add_gru for the GRU's four — added to)."""
+    weights = (w_in, w_out, bias_p, w_ih, w_hh, b_ih, b_hh)
+    require_gpu(dh_next, h, g, dg, dx_acc, ws, *weights)
+    dh_next = dh_next.contiguous()
+    _gn_f32c(dh_next, h, g, dg, dx_acc, ws, *weights)
+    B, F, E = h.shape
+    _gn_layer_weights(F, E, *weights)
+    if tuple(g.shape) != (B, F, F) or tuple(dg.shape) != (B, F, F) or dh_next.shape != h.shape \
+            or (dx_acc is not None and dx_acc.shape != h.shape):
+        raise ValueError(f"fignn_layer_bwd: g / dg / dh_next / dx_acc do not fit h {tuple(h.shape)}")
+    dev = h.device
+    if grads is None:
+        if add_layer or add_gru:
+            raise ValueError("fignn_layer_bwd: adding needs the destinations")
+        grads = [torch.empty_like(w) for w in weights]
+    _gn_f32c(*grads)
+    require_gpu(*grads)
+    if [tuple(t.shape) for t in grads] != [tuple(w.shape) for w in weights]:
+        raise ValueError("fignn_layer_bwd: gradient destinations do not fit the weights")
+    if ws is None:
+        ws = torch.empty(B, F, FIGNN_WS_VECS, E, dtype=torch.float32, device=dev)
+    elif ws.numel() != B * F * FIGNN_WS_VECS * E:
+        raise ValueError("fignn_layer_bwd: workspace of the wrong size")
+    dh = torch.empty_like(h)
+    check(lib.mapx_fignn_layer_bwd(ptr(dh_next), ptr(h), ptr(g), *(ptr(w) for w in weights), B, F, E, ptr(dh), ptr(dg),
+                                   int(bool(dg_init)), ptr(dx_acc), int(bool(dx_init)), ptr(ws), stream()))
+    pf = torch.empty(lib.mapx_fignn_wgrad_groups(B, F, 0), 2 * F * E * E, dtype=torch.float32, device=dev)
+    pg = torch.empty(lib.mapx_fignn_wgrad_groups(B, F, 1), 6 * E * E + 7 * E, dtype=torch.float32, device=dev)
+    check(lib.mapx_fignn_layer_wgrad(ptr(ws), ptr(h), B, F, E, ptr(pf), ptr(pg), *(ptr(t) for t in grads),
+                                     int(bool(add_layer)), int(bool(add_gru)), stream()))
+    return dh, grads
+
+
+def fignn_pred_fwd(score, z2):
+    """score, z2 [B,F] -> logits [B,1] = sum_f sigmoid(z2) score."""
+    require_gpu(score, z2)
+    _gn_f32c(score, z2)
+    B, F = score.shape
+    if z2.shape != score.shape:
+        raise ValueError("fignn_pred_fwd: score and z2 differ in shape")
+    out = torch.empty(B, 1, dtype=torch.float32, device=score.device)
+    check(lib.mapx_fignn_pred_fwd(ptr(score), ptr(z2), B, F, ptr(out), stream()))
+    return out
+
+
+def fignn_pred_bwd(g_logits, score, z2):
+    require_gpu(g_logits, score, z2)
+    g_logits = g_logits.contiguous()
+    _gn_f32c(g_logits, score, z2)
+    B, F = score.shape
+    if g_logits.numel() != B:
+        raise ValueError("fignn_pred_bwd: one logit gradient per sample")
+    dscore, dz2 = torch.empty_like(score), torch.empty_like(z2)
+    check(lib.mapx_fignn_pred_bwd(ptr(g_logits), ptr(score), ptr(z2), B, F, ptr(dscore), ptr(dz2), stream()))
+    return dscore, dz2
+
+
 # --------------------------------------------------------------------------- NCE
 def alias_build(probs_cpu):
     """Host Walker table, bit-identical to the reference's (alias_multinomial.py:39-72)."""

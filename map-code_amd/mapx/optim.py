@@ -215,7 +215,9 @@ class MapxOptimizer:
             offs.append(offs[-1] + sz)
         off = 0
         for i, ((_, p), sz) in enumerate(zip(members, sizes)):
-            if recs is not None:
+            # (FiGNN's graph, GRU and W_attn parameters are read by row-resident kernels only, never as a GEMM operand:
+            # no record is attached to them and no planes are kept; their rows of `recs` are written and never read)
+            if recs is not None and not getattr(p, "_mapx_row_resident", False):
                 p._amax = recs[i]
                 if p.dim() == 2:
                     p._planes = {}           # ops.weight_planes: filled at first use, refreshed behind every update
@@ -239,6 +241,8 @@ class MapxOptimizer:
         for g in self.groups:
             if g.get("amax") is not None:
                 for p, rec in zip(g["params"], g["amax"]):
+                    if getattr(p, "_mapx_row_resident", False):
+                        continue
                     ops.amax(p.data.reshape(1, -1) if p.dim() != 2 else p.data, rec=rec, reset=True)
                     p._amax_ver = p._version
                     ops.refresh_weight_planes(p)

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from mapx.arguments import Config, parse_args_into_dataclasses  # noqa: E402
 from mapx.dataset import BaseDataset  # noqa: E402
-from mapx.models import BaseModel  # noqa: E402
+from mapx.models import build_backbone  # noqa: E402
 from mapx.trainer import Trainer  # noqa: E402
 
 
@@ -66,7 +66,7 @@ def main(argv=None):
                feat_num_per_field=dataset.feat_num_per_field, seed=training_args.seed,
                rank=max(training_args.local_rank, 0))
     config = Config.from_dict(cfg)
-    model = BaseModel.from_config(config)
+    model = build_backbone(config)
     if training_args.finetune:
         model.load_for_finetune(training_args.pretrained_model_path)
 
