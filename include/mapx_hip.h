@@ -78,7 +78,8 @@ int mapx_seg_plan(const int32_t* keys, int64_t n, int64_t V, void* ws, size_t ws
  * from ONE chain of launches (a sort is a dependent chain of small kernels; two sorts one after the
  * other cost two chains): block b of every launch works on the list it belongs to, so a 3-pass
  * sort of both lists is 8 launches (mapx_seg_plan: 8 per list).  All arguments are HOST arrays of `count` entries holding what
- * mapx_seg_plan takes per list; outputs are identical to `count` calls of mapx_seg_plan. */
+ * mapx_seg_plan takes per list; outputs are identical to `count` calls of mapx_seg_plan, which is the one-list case of
+ * the same code: mapx_seg_plan_multi_workspace_bytes(1, &n, &V) == mapx_seg_plan_workspace_bytes(n, V). */
 size_t mapx_seg_plan_multi_workspace_bytes(int count, const int64_t* n, const int64_t* V);
 int mapx_seg_plan_multi(int count, const int32_t* const* keys, const int64_t* n, const int64_t* V, void* ws,
                         size_t ws_bytes, int32_t* const* sorted_keys, int32_t* const* perm,

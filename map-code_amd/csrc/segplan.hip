@@ -4,7 +4,9 @@
 // deterministic gradient reduce-by-key after the backward pass (segreduce.h).
 //
 // The sort is the hand-written LSD radix sort of radixsort.h (8-bit digits: two launches per pass, two more for the
-// runs; 9- and 12-bit digits and a scan launch per pass were measured and lost).
+// runs; 9- and 12-bit digits and a scan launch per pass were measured and lost).  Its kernels take a list of
+// problems; the three plan entries below fill that list (add_prob) and share one launch routine: mapx_seg_plan is
+// the one-problem case of mapx_seg_plan_multi, mapx_seg_plan_merge a ranking launch in place of the sort passes.
 #include <cstdlib>
 #include <cstring>
 
@@ -23,109 +25,111 @@ static int key_bits_for(int64_t V) {
   return b;
 }
 
-struct PlanWs {   // carve-up of the caller's workspace
-  int32_t *tk, *tv, *bh, *off;
-  size_t total;
+// Carve-up of the caller's workspace for one problem, from byte `at` on: two ping-pong arrays, the
+// histogram matrix of the running pass, the tile counts of the run kernels.
+struct ProbWs {
+  size_t tk, tv, bh, cnt, end;
 };
-static PlanWs plan_ws(void* ws, int64_t n) {
-  PlanWs w;
-  const size_t hist = (size_t)(1 << kSortBits) * radix_ld(radix_blocks(n));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes); return at; };
-  char* base = static_cast<char*>(ws);
-  w.tk = reinterpret_cast<int32_t*>(base + take((size_t)n * 4));
-  w.tv = reinterpret_cast<int32_t*>(base + take((size_t)n * 4));
-  w.bh = reinterpret_cast<int32_t*>(base + take(hist * 4));
-  w.off = reinterpret_cast<int32_t*>(base + take(hist * 4));
-  w.total = o;
-  return w;
-}
-}  // namespace mapx
-
-extern "C" size_t mapx_seg_plan_workspace_bytes(int64_t n, int64_t V) {
-  (void)V;
-  if (n <= 0) return 256;
-  return mapx::plan_ws(nullptr, n).total + 256;
-}
-
-extern "C" int mapx_seg_plan(const int32_t* keys, int64_t n, int64_t V, void* ws, size_t ws_bytes,
-                             int32_t* sorted_keys, int32_t* perm, int32_t* rank, int32_t* uniq,
-                             int32_t* seg_start, int32_t* n_uniq, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(n >= 0 && n < (1LL << 31) && V > 0 && V < (1LL << 31), "seg_plan: bad sizes");
-  MAPX_REQUIRE(n_uniq && seg_start, "seg_plan: null output");
-  if (n == 0) {
-    MAPX_HIP(hipMemsetAsync(n_uniq, 0, 2 * sizeof(int32_t), stream));
-    MAPX_HIP(hipMemsetAsync(seg_start, 0, sizeof(int32_t), stream));
-    return MAPX_OK;
-  }
-  MAPX_REQUIRE(keys && sorted_keys && perm && rank && uniq && ws, "seg_plan: null pointer");
-  MAPX_REQUIRE((uintptr_t)ws % 256 == 0, "seg_plan: workspace must be 256-byte aligned");
-  const PlanWs w = plan_ws(ws, n);
-  if (ws_bytes < w.total) {
-    set_error("seg_plan: workspace %zu < %zu bytes", ws_bytes, w.total);
-    return MAPX_EWORKSPACE;
-  }
-  const int bits = key_bits_for(V), passes = radix_passes(bits), nblocks = radix_blocks(n);
-  // ping-pong so that the last pass lands in (sorted_keys, perm)
-  const int32_t* src_k = keys;
-  const int32_t* src_v = nullptr;
-  for (int p = 0; p < passes; ++p) {
-    const int shift = p * kSortBits;
-    const int db = (bits - shift) < kSortBits ? (bits - shift) : kSortBits;
-    const int bins = 1 << db;
-    const bool to_out = ((passes - 1 - p) % 2) == 0;
-    int32_t* dst_k = to_out ? sorted_keys : w.tk;
-    int32_t* dst_v = to_out ? perm : w.tv;
-    hipLaunchKernelGGL(radix_hist_kernel, dim3(nblocks), dim3(256), 0, stream, src_k, n, shift, bins,
-                       nblocks, w.bh);
-    if (p == 0)
-      hipLaunchKernelGGL(radix_scatter_kernel<true>, dim3(nblocks), dim3(256), 0, stream, src_k, src_v,
-                         n, shift, db, nblocks, (const int32_t*)w.bh, dst_k, dst_v);
-    else
-      hipLaunchKernelGGL(radix_scatter_kernel<false>, dim3(nblocks), dim3(256), 0, stream, src_k, src_v,
-                         n, shift, db, nblocks, (const int32_t*)w.bh, dst_k, dst_v);
-    src_k = dst_k;
-    src_v = dst_v;
-  }
-  hipLaunchKernelGGL(seg_count_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys, n,
-                     w.off);
-  hipLaunchKernelGGL(seg_mark_tiles_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys,
-                     n, (const int32_t*)w.off, rank, uniq, seg_start, n_uniq);
-  return check_launch("seg_plan");
-}
-
-// ---------------------------------------------------------------------------------------------
-// The plans of up to kMaxSortProbs key lists (the step's tables) from ONE chain of launches
-// (radixsort.h, multi-problem form).  Workspace per problem: two ping-pong arrays, one histogram
-// matrix per pass, the tile counts.
-namespace mapx {
-struct MultiWs {
-  size_t tk, tv, bh[kMaxPasses], cnt, total;
-};
-static MultiWs multi_ws(int64_t n, int passes, size_t at) {
-  MultiWs w;
+static ProbWs prob_ws(int64_t n, size_t at) {
+  ProbWs w;
   size_t o = at;
   auto take = [&](size_t bytes) { size_t a = o; o = align_up(o + bytes); return a; };
   const size_t hist = (size_t)(1 << kSortBits) * radix_ld(radix_blocks(n));
   w.tk = take((size_t)n * 4);
   w.tv = take((size_t)n * 4);
-  for (int p = 0; p < kMaxPasses; ++p) w.bh[p] = p < 1 ? take(hist * 4) : 0;
-  (void)passes;
+  w.bh = take(hist * 4);
   w.cnt = take((size_t)radix_blocks(n) * 4);
-  w.total = o;
+  w.end = o;
   return w;
 }
-}  // namespace mapx
-
-extern "C" size_t mapx_seg_plan_multi_workspace_bytes(int count, const int64_t* n, const int64_t* V) {
-  using namespace mapx;
+static size_t plan_ws_bytes(int count, const int64_t* n) {
   size_t at = 0;
   for (int q = 0; q < count; ++q)
-    if (n[q] > 0) at = multi_ws(n[q], radix_passes(key_bits_for(V[q])), at).total;
+    if (n[q] > 0) at = prob_ws(n[q], at).end;
   return at + 256;
 }
 
+struct PlanOut {   // the arrays of one plan (include/mapx_hip.h)
+  int32_t *sorted_keys, *perm, *rank, *uniq, *seg_start, *n_uniq;
+};
+
+// Appends the problem {keys[n] of `bits` bits -> o} to ps, its scratch carved from the workspace at byte
+// `at`.  An empty list gets its plan, {0 runs}, here and takes no part in the launches.  `what` names the
+// entry in the error messages.
+static int add_prob(SortProbs& ps, size_t& at, const char* what, const int32_t* keys, int64_t n, int bits,
+                    void* ws, size_t ws_bytes, const PlanOut& o, hipStream_t stream) {
+  MAPX_REQUIRE(o.n_uniq && o.seg_start, "%s: null output", what);
+  if (n == 0) {
+    MAPX_HIP(hipMemsetAsync(o.n_uniq, 0, 2 * sizeof(int32_t), stream));
+    MAPX_HIP(hipMemsetAsync(o.seg_start, 0, sizeof(int32_t), stream));
+    return MAPX_OK;
+  }
+  MAPX_REQUIRE(keys && o.sorted_keys && o.perm && o.rank && o.uniq && ws, "%s: null pointer", what);
+  MAPX_REQUIRE((uintptr_t)ws % 256 == 0, "%s: workspace must be 256-byte aligned", what);
+  SortProb& pr = ps.p[ps.count];
+  pr.keys = keys; pr.n = n;
+  pr.nblocks = radix_blocks(n);
+  pr.block0 = ps.count ? ps.p[ps.count - 1].block0 + ps.p[ps.count - 1].nblocks : 0;
+  pr.bits = bits; pr.passes = radix_passes(bits);
+  MAPX_REQUIRE(pr.passes <= kMaxPasses, "%s: keys wider than %d bits", what, kMaxPasses * kSortBits);
+  const ProbWs w = prob_ws(n, at);
+  if (ws_bytes < w.end) {
+    set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.end);
+    return MAPX_EWORKSPACE;
+  }
+  at = w.end;
+  char* base = static_cast<char*>(ws);
+  pr.tk = reinterpret_cast<int32_t*>(base + w.tk);
+  pr.tv = reinterpret_cast<int32_t*>(base + w.tv);
+  pr.bh = reinterpret_cast<int32_t*>(base + w.bh);
+  pr.cnt = reinterpret_cast<int32_t*>(base + w.cnt);
+  pr.sorted_keys = o.sorted_keys; pr.perm = o.perm; pr.rank = o.rank; pr.uniq = o.uniq;
+  pr.seg_start = o.seg_start; pr.n_uniq = o.n_uniq;
+  ++ps.count;
+  return MAPX_OK;
+}
+
+static int sort_blocks(const SortProbs& ps) { return ps.p[ps.count - 1].block0 + ps.p[ps.count - 1].nblocks; }
+
+// The runs of equal keys in every problem's sorted_keys: rank, uniq, seg_start, n_uniq.
+static int launch_runs(const SortProbs& ps, hipStream_t stream, const char* what) {
+  if (ps.count == 0) return MAPX_OK;
+  const int blocks = sort_blocks(ps);
+  const RunProbs rp = run_probs_of(ps);
+  hipLaunchKernelGGL(seg_count_mp_kernel, dim3(blocks), dim3(256), 0, stream, rp);
+  hipLaunchKernelGGL(seg_mark_mp_kernel, dim3(blocks), dim3(256), 0, stream, rp);
+  return check_launch(what);
+}
+
+// The whole plan of every problem: the sort passes of the widest keys (a problem with narrower keys sits
+// out the passes it does not need), then the runs.
+static int launch_sort_and_runs(const SortProbs& ps, hipStream_t stream, const char* what) {
+  if (ps.count == 0) return MAPX_OK;
+  const int blocks = sort_blocks(ps);
+  int max_passes = 0;
+  for (int q = 0; q < ps.count; ++q)
+    if (ps.p[q].passes > max_passes) max_passes = ps.p[q].passes;
+  for (int p = 0; p < max_passes; ++p) {
+    hipLaunchKernelGGL(radix_hist_mp_kernel, dim3(blocks), dim3(256), 0, stream, ps, p);
+    if (p == 0) hipLaunchKernelGGL(radix_scatter_mp_kernel<true>, dim3(blocks), dim3(256), 0, stream, ps, p);
+    else hipLaunchKernelGGL(radix_scatter_mp_kernel<false>, dim3(blocks), dim3(256), 0, stream, ps, p);
+  }
+  return launch_runs(ps, stream, what);
+}
+}  // namespace mapx
+
+// V does not enter the layout (the merge form passes 0).
+extern "C" size_t mapx_seg_plan_workspace_bytes(int64_t n, int64_t V) {
+  (void)V;
+  return mapx::plan_ws_bytes(1, &n);
+}
+
+extern "C" size_t mapx_seg_plan_multi_workspace_bytes(int count, const int64_t* n, const int64_t* V) {
+  (void)V;
+  return mapx::plan_ws_bytes(count, n);
+}
+
+// The plans of up to kMaxSortProbs key lists (the step's tables) from ONE chain of launches.
 extern "C" int mapx_seg_plan_multi(int count, const int32_t* const* keys, const int64_t* n, const int64_t* V,
                                    void* ws, size_t ws_bytes, int32_t* const* sorted_keys, int32_t* const* perm,
                                    int32_t* const* rank, int32_t* const* uniq, int32_t* const* seg_start,
@@ -135,49 +139,29 @@ extern "C" int mapx_seg_plan_multi(int count, const int32_t* const* keys, const 
   MAPX_REQUIRE(keys && n && V && sorted_keys && perm && rank && uniq && seg_start && n_uniq, "seg_plan_multi: null array");
   SortProbs ps;
   memset(&ps, 0, sizeof(ps));
-  int blocks = 0, max_passes = 0;
   size_t at = 0;
-  char* base = static_cast<char*>(ws);
   for (int q = 0; q < count; ++q) {
     MAPX_REQUIRE(n[q] >= 0 && n[q] < (1LL << 31) && V[q] > 0 && V[q] < (1LL << 31), "seg_plan_multi: bad sizes");
-    MAPX_REQUIRE(n_uniq[q] && seg_start[q], "seg_plan_multi: null output");
-    if (n[q] == 0) {          // an empty list: its plan is {0 runs}; it takes no part in the launches
-      MAPX_HIP(hipMemsetAsync(n_uniq[q], 0, 2 * sizeof(int32_t), stream));
-      MAPX_HIP(hipMemsetAsync(seg_start[q], 0, sizeof(int32_t), stream));
-      continue;
-    }
-    MAPX_REQUIRE(keys[q] && sorted_keys[q] && perm[q] && rank[q] && uniq[q] && ws, "seg_plan_multi: null pointer");
-    MAPX_REQUIRE((uintptr_t)ws % 256 == 0, "seg_plan_multi: workspace must be 256-byte aligned");
-    SortProb& pr = ps.p[ps.count];
-    pr.keys = keys[q]; pr.n = n[q];
-    pr.nblocks = radix_blocks(n[q]); pr.block0 = blocks;
-    pr.bits = key_bits_for(V[q]); pr.passes = radix_passes(pr.bits);
-    MAPX_REQUIRE(pr.passes <= kMaxPasses, "seg_plan_multi: keys wider than %d bits", kMaxPasses * kSortBits);
-    const MultiWs w = multi_ws(n[q], pr.passes, at);
-    if (ws_bytes < w.total) {
-      set_error("seg_plan_multi: workspace %zu < %zu bytes", ws_bytes, w.total);
-      return MAPX_EWORKSPACE;
-    }
-    at = w.total;
-    pr.tk = reinterpret_cast<int32_t*>(base + w.tk);
-    pr.tv = reinterpret_cast<int32_t*>(base + w.tv);
-    pr.bh[0] = reinterpret_cast<int32_t*>(base + w.bh[0]);
-    pr.cnt = reinterpret_cast<int32_t*>(base + w.cnt);
-    pr.sorted_keys = sorted_keys[q]; pr.perm = perm[q]; pr.rank = rank[q]; pr.uniq = uniq[q];
-    pr.seg_start = seg_start[q]; pr.n_uniq = n_uniq[q];
-    blocks += pr.nblocks;
-    if (pr.passes > max_passes) max_passes = pr.passes;
-    ++ps.count;
+    const PlanOut o{sorted_keys[q], perm[q], rank[q], uniq[q], seg_start[q], n_uniq[q]};
+    const int rc = add_prob(ps, at, "seg_plan_multi", keys[q], n[q], key_bits_for(V[q]), ws, ws_bytes, o, stream);
+    if (rc != MAPX_OK) return rc;
   }
-  if (ps.count == 0) return MAPX_OK;
-  for (int p = 0; p < max_passes; ++p) {
-    hipLaunchKernelGGL(radix_hist_mp_kernel, dim3(blocks), dim3(256), 0, stream, ps, p);
-    if (p == 0) hipLaunchKernelGGL(radix_scatter_mp_kernel<true>, dim3(blocks), dim3(256), 0, stream, ps, p);
-    else hipLaunchKernelGGL(radix_scatter_mp_kernel<false>, dim3(blocks), dim3(256), 0, stream, ps, p);
-  }
-  hipLaunchKernelGGL(seg_count_mp_kernel, dim3(blocks), dim3(256), 0, stream, ps);
-  hipLaunchKernelGGL(seg_mark_mp_kernel, dim3(blocks), dim3(256), 0, stream, ps);
-  return check_launch("seg_plan_multi");
+  return launch_sort_and_runs(ps, stream, "seg_plan_multi");
+}
+
+// One key list: the one-problem case of the above.
+extern "C" int mapx_seg_plan(const int32_t* keys, int64_t n, int64_t V, void* ws, size_t ws_bytes,
+                             int32_t* sorted_keys, int32_t* perm, int32_t* rank, int32_t* uniq,
+                             int32_t* seg_start, int32_t* n_uniq, hipStream_t stream) {
+  using namespace mapx;
+  MAPX_REQUIRE(n >= 0 && n < (1LL << 31) && V > 0 && V < (1LL << 31), "seg_plan: bad sizes");
+  SortProbs ps;
+  memset(&ps, 0, sizeof(ps));
+  size_t at = 0;
+  const PlanOut o{sorted_keys, perm, rank, uniq, seg_start, n_uniq};
+  const int rc = add_prob(ps, at, "seg_plan", keys, n, key_bits_for(V), ws, ws_bytes, o, stream);
+  if (rc != MAPX_OK) return rc;
+  return launch_sort_and_runs(ps, stream, "seg_plan");
 }
 
 namespace mapx {
@@ -210,33 +194,22 @@ __global__ void __launch_bounds__(256) merge_rank_kernel(const int32_t* __restri
 }
 }  // namespace mapx
 
+// The order comes from one ranking launch; the runs from the run kernels on a one-problem list.
 extern "C" int mapx_seg_plan_merge(const int32_t* keys, int lists, int64_t len, void* ws, size_t ws_bytes,
                                    int32_t* sorted_keys, int32_t* perm, int32_t* rank, int32_t* uniq,
                                    int32_t* seg_start, int32_t* n_uniq, hipStream_t stream) {
   using namespace mapx;
   MAPX_REQUIRE(lists >= 1 && len >= 0 && (int64_t)lists * len < (1LL << 31), "seg_plan_merge: bad sizes");
-  MAPX_REQUIRE(n_uniq && seg_start, "seg_plan_merge: null output");
   const int64_t n = (int64_t)lists * len;
-  if (n == 0) {
-    MAPX_HIP(hipMemsetAsync(n_uniq, 0, 2 * sizeof(int32_t), stream));
-    MAPX_HIP(hipMemsetAsync(seg_start, 0, sizeof(int32_t), stream));
-    return MAPX_OK;
-  }
-  MAPX_REQUIRE(keys && sorted_keys && perm && rank && uniq && ws, "seg_plan_merge: null pointer");
-  MAPX_REQUIRE((uintptr_t)ws % 256 == 0, "seg_plan_merge: workspace must be 256-byte aligned");
-  const PlanWs w = plan_ws(ws, n);
-  if (ws_bytes < w.total) {
-    set_error("seg_plan_merge: workspace %zu < %zu bytes", ws_bytes, w.total);
-    return MAPX_EWORKSPACE;
-  }
-  const int nblocks = radix_blocks(n);
+  SortProbs ps;
+  memset(&ps, 0, sizeof(ps));
+  size_t at = 0;
+  const PlanOut o{sorted_keys, perm, rank, uniq, seg_start, n_uniq};
+  const int rc = add_prob(ps, at, "seg_plan_merge", keys, n, /*bits=*/0, ws, ws_bytes, o, stream);   // no sort pass
+  if (rc != MAPX_OK || ps.count == 0) return rc;
   hipLaunchKernelGGL(merge_rank_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, keys, lists, len,
                      sorted_keys, perm);
-  hipLaunchKernelGGL(seg_count_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys, n,
-                     w.off);
-  hipLaunchKernelGGL(seg_mark_tiles_kernel, dim3(nblocks), dim3(256), 0, stream, (const int32_t*)sorted_keys,
-                     n, (const int32_t*)w.off, rank, uniq, seg_start, n_uniq);
-  return check_launch("seg_plan_merge");
+  return launch_runs(ps, stream, "seg_plan_merge");
 }
 
 // Generic reduce-by-key of dense rows: out[u, :] = sum over the positions of key uniq[u] of
@@ -246,67 +219,78 @@ extern "C" size_t mapx_seg_reduce_workspace_bytes(int64_t n, int W) {
   return mapx::seg_reduce_partial_bytes(n, W, true) + 256;
 }
 
+namespace mapx {
+// The entries below for T = float (rows read with 16-byte loads) and T = __bf16 (8-byte loads).
+template <class T>
+constexpr unsigned kRowAlign = sizeof(T) * 4;
+template <class T>
+constexpr const char* kRowAlignMsg =
+    sizeof(T) == 4 ? "%s: pointers must be 16-byte aligned" : "%s: pointers must be 8 / 16-byte aligned";
+
+template <class T>
+static int reduce_rows(const char* what, int64_t n, const int32_t* perm, const int32_t* rank,
+                       const int32_t* seg_start, const T* src, const T* src2_opt, int W, float* out, void* ws,
+                       size_t ws_bytes, int32_t* zeroed_counter_opt, hipStream_t stream) {
+  MAPX_REQUIRE(n >= 0, "%s: n < 0", what);
+  if (n == 0) return MAPX_OK;
+  MAPX_REQUIRE(perm && rank && seg_start && src && out, "%s: null pointer", what);
+  MAPX_REQUIRE((uintptr_t)src % kRowAlign<T> == 0 && (uintptr_t)src2_opt % kRowAlign<T> == 0 &&
+                   (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0,
+               kRowAlignMsg<T>, what);
+  SegPlanView pl{n, perm, rank, seg_start};
+  if (src2_opt) {
+    RowsContrib<T, true> c2{{src, src2_opt}, W};
+    return seg_reduce_launch<false>(pl, c2, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream, what);
+  }
+  RowsContrib<T, false> c{{src}, W};
+  return seg_reduce_launch<false>(pl, c, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream, what);
+}
+
+template <class T>
+static int reduce_rows_extra(const char* what, int64_t n, const int32_t* perm, const int32_t* rank,
+                             const int32_t* seg_start, const T* src, int W, int64_t ld_src, const float* extra,
+                             int group, int64_t extra_stride, float* out, float* out_extra, void* ws,
+                             size_t ws_bytes, int32_t* zeroed_counter_opt, hipStream_t stream) {
+  MAPX_REQUIRE(n >= 0 && group >= 1 && ld_src >= W && ld_src % 4 == 0 && extra_stride >= 1, "%s: bad sizes", what);
+  if (n == 0) return MAPX_OK;
+  MAPX_REQUIRE(perm && rank && seg_start && src && extra && out && out_extra, "%s: null pointer", what);
+  MAPX_REQUIRE((uintptr_t)src % kRowAlign<T> == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0,
+               kRowAlignMsg<T>, what);
+  SegPlanView pl{n, perm, rank, seg_start};
+  RowsExtraContrib<T> c{src, W, ld_src, extra, group, extra_stride};
+  return seg_reduce_launch<true>(pl, c, W, out, out_extra, ws, ws_bytes, zeroed_counter_opt, stream, what);
+}
+}  // namespace mapx
+
 extern "C" int mapx_seg_reduce_rows(int64_t n, const int32_t* perm, const int32_t* rank,
                                     const int32_t* seg_start, const float* src, const float* src2_opt, int W,
                                     float* out, void* ws, size_t ws_bytes, int32_t* zeroed_counter_opt,
                                     hipStream_t stream) {
-  MAPX_REQUIRE(n >= 0, "seg_reduce_rows: n < 0");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(perm && rank && seg_start && src && out, "seg_reduce_rows: null pointer");
-  MAPX_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)src2_opt % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                   ((uintptr_t)ws % 16 == 0),
-               "seg_reduce_rows: pointers must be 16-byte aligned");
-  mapx::SegPlanView pl{n, perm, rank, seg_start};
-  if (src2_opt) {
-    mapx::Rows2Contrib c2{src, src2_opt, W};
-    return mapx::seg_reduce_launch<false>(pl, c2, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream,
-                                          "seg_reduce_rows");
-  }
-  mapx::RowsContrib c{src, W};
-  return mapx::seg_reduce_launch<false>(pl, c, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream,
-                                        "seg_reduce_rows");
+  return mapx::reduce_rows("seg_reduce_rows", n, perm, rank, seg_start, src, src2_opt, W, out, ws, ws_bytes,
+                           zeroed_counter_opt, stream);
+}
+
+// mapx_seg_reduce_rows over bf16 gradient rows: fp32 sums and output.
+extern "C" int mapx_seg_reduce_rows_bf16(int64_t n, const int32_t* perm, const int32_t* rank,
+                                         const int32_t* seg_start, const mapx_bf16* src, const mapx_bf16* src2_opt,
+                                         int W, float* out, void* ws, size_t ws_bytes,
+                                         int32_t* zeroed_counter_opt, hipStream_t stream) {
+  return mapx::reduce_rows("seg_reduce_rows_bf16", n, perm, rank, seg_start, reinterpret_cast<const __bf16*>(src),
+                           reinterpret_cast<const __bf16*>(src2_opt), W, out, ws, ws_bytes, zeroed_counter_opt,
+                           stream);
 }
 
 // Same reduction with an extra scalar per run: out_extra[u] = sum over the run of
 // extra[position / group] (DeepFM: the LR weight shares the embedding's ids, its gradient
 // dL/dlr[b] is common to the F positions of batch row b).
-extern "C" int mapx_seg_reduce_rows_bf16(int64_t n, const int32_t* perm, const int32_t* rank,
-                                         const int32_t* seg_start, const mapx_bf16* src, const mapx_bf16* src2_opt,
-                                         int W, float* out, void* ws, size_t ws_bytes,
-                                         int32_t* zeroed_counter_opt, hipStream_t stream) {
-  MAPX_REQUIRE(n >= 0, "seg_reduce_rows_bf16: n < 0");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(perm && rank && seg_start && src && out, "seg_reduce_rows_bf16: null pointer");
-  MAPX_REQUIRE((uintptr_t)src % 8 == 0 && (uintptr_t)src2_opt % 8 == 0 && (uintptr_t)out % 16 == 0 &&
-                   (uintptr_t)ws % 16 == 0,
-               "seg_reduce_rows_bf16: pointers must be 8 / 16-byte aligned");
-  mapx::SegPlanView pl{n, perm, rank, seg_start};
-  if (src2_opt) {
-    mapx::Rows2Bf16Contrib c2{reinterpret_cast<const __bf16*>(src), reinterpret_cast<const __bf16*>(src2_opt), W};
-    return mapx::seg_reduce_launch<false>(pl, c2, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream,
-                                          "seg_reduce_rows_bf16");
-  }
-  mapx::RowsBf16Contrib c{reinterpret_cast<const __bf16*>(src), W};
-  return mapx::seg_reduce_launch<false>(pl, c, W, out, nullptr, ws, ws_bytes, zeroed_counter_opt, stream,
-                                        "seg_reduce_rows_bf16");
-}
-
 extern "C" int mapx_seg_reduce_rows_extra(int64_t n, const int32_t* perm, const int32_t* rank,
                                           const int32_t* seg_start, const float* src, int W, int64_t ld_src,
                                           const float* extra, int group, int64_t extra_stride, float* out,
                                           float* out_extra,
                                           void* ws, size_t ws_bytes, int32_t* zeroed_counter_opt,
                                           hipStream_t stream) {
-  MAPX_REQUIRE(n >= 0 && group >= 1 && ld_src >= W && ld_src % 4 == 0 && extra_stride >= 1,
-               "seg_reduce_rows_extra: bad sizes");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(perm && rank && seg_start && src && extra && out && out_extra, "seg_reduce_rows_extra: null pointer");
-  MAPX_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)ws % 16 == 0),
-               "seg_reduce_rows_extra: pointers must be 16-byte aligned");
-  mapx::SegPlanView pl{n, perm, rank, seg_start};
-  mapx::RowsExtraContrib c{src, W, ld_src, extra, group, extra_stride};
-  return mapx::seg_reduce_launch<true>(pl, c, W, out, out_extra, ws, ws_bytes, zeroed_counter_opt, stream,
-                                       "seg_reduce_rows_extra");
+  return mapx::reduce_rows_extra("seg_reduce_rows_extra", n, perm, rank, seg_start, src, W, ld_src, extra, group,
+                                 extra_stride, out, out_extra, ws, ws_bytes, zeroed_counter_opt, stream);
 }
 
 // mapx_seg_reduce_rows_extra over bf16 rows: the same plan order, fp32 sums and outputs, the scalar fp32.
@@ -315,17 +299,9 @@ extern "C" int mapx_seg_reduce_rows_extra_bf16(int64_t n, const int32_t* perm, c
                                                const float* extra, int group, int64_t extra_stride, float* out,
                                                float* out_extra, void* ws, size_t ws_bytes,
                                                int32_t* zeroed_counter_opt, hipStream_t stream) {
-  MAPX_REQUIRE(n >= 0 && group >= 1 && ld_src >= W && ld_src % 4 == 0 && extra_stride >= 1,
-               "seg_reduce_rows_extra_bf16: bad sizes");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(perm && rank && seg_start && src && extra && out && out_extra,
-               "seg_reduce_rows_extra_bf16: null pointer");
-  MAPX_REQUIRE(((uintptr_t)src % 8 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)ws % 16 == 0),
-               "seg_reduce_rows_extra_bf16: pointers must be 8 / 16-byte aligned");
-  mapx::SegPlanView pl{n, perm, rank, seg_start};
-  mapx::RowsExtraBf16Contrib c{reinterpret_cast<const __bf16*>(src), W, ld_src, extra, group, extra_stride};
-  return mapx::seg_reduce_launch<true>(pl, c, W, out, out_extra, ws, ws_bytes, zeroed_counter_opt, stream,
-                                       "seg_reduce_rows_extra_bf16");
+  return mapx::reduce_rows_extra("seg_reduce_rows_extra_bf16", n, perm, rank, seg_start,
+                                 reinterpret_cast<const __bf16*>(src), W, ld_src, extra, group, extra_stride, out,
+                                 out_extra, ws, ws_bytes, zeroed_counter_opt, stream);
 }
 
 // Data-parallel exchange (mapx/parallel.py): the first n_uniq (id, gradient row) pairs of a rank's

@@ -40,75 +40,48 @@ struct SegPlanView {
   const int32_t* seg_start;  // [U+1] first sorted position of each segment; [U] = n
 };
 
+// Four consecutive elements of a gradient row as fp32.  bf16 rows: bf16 compute mode, dL/dX0 leaves
+// the trunk's backward GEMMs in bf16; the sums are fp32 like everything else here.
+__device__ inline float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ inline float4 load4(const __bf16* p) {
+  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+  const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+// a + b of two gradient tensors, formed here, element by element, instead of by an elementwise launch in
+// front of the reduction.  fp32: the same fp32 additions in the same order, so the result is bit-identical.
+// bf16: the sum is rounded to bf16 first, as the elementwise bf16 addition it replaces would have done.
+__device__ inline float4 load4_sum(const float* pa, const float* pb) {
+  const float4 a = load4(pa), b = load4(pb);
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+__device__ inline float4 load4_sum(const __bf16* pa, const __bf16* pb) {
+  const float4 a = load4(pa), b = load4(pb);
+  return make_float4((float)(__bf16)(a.x + b.x), (float)(__bf16)(a.y + b.y), (float)(__bf16)(a.z + b.z),
+                     (float)(__bf16)(a.w + b.w));
+}
+
 // Contribution functors: value of row `p` (original position), float4 column `sub`.
+// Dense rows of T = float or __bf16.  TWO: the rows reach the table as the SUM of two gradient tensors
+// (DCNv2: dL/dX0 of the deep tower and of the cross tower).
+template <class T, bool TWO>
 struct RowsContrib {
-  const float* src;  // [n, W]
+  const T* src[TWO ? 2 : 1];   // each [n, W]
   int W;
   __device__ inline void prepare() {}
   __device__ inline float4 operator()(int32_t p, int sub, float& extra) const {
     extra = 0.f;
-    return *reinterpret_cast<const float4*>(src + (int64_t)p * W + 4 * sub);
+    if constexpr (TWO) return load4_sum(src[0] + (int64_t)p * W + 4 * sub, src[1] + (int64_t)p * W + 4 * sub);
+    else return load4(src[0] + (int64_t)p * W + 4 * sub);
   }
 };
 
-// Rows that reach the table as the SUM of two gradient tensors (DCNv2: dL/dX0 of the deep tower and of the
-// cross tower): a + b is formed here, element by element, instead of by an elementwise launch in front of
-// the reduction — the same fp32 additions in the same order, so the result is bit-identical.
-struct Rows2Contrib {
-  const float* src;   // [n, W]
-  const float* src2;  // [n, W]
-  int W;
-  __device__ inline void prepare() {}
-  __device__ inline float4 operator()(int32_t p, int sub, float& extra) const {
-    extra = 0.f;
-    const float4 a = *reinterpret_cast<const float4*>(src + (int64_t)p * W + 4 * sub);
-    const float4 b = *reinterpret_cast<const float4*>(src2 + (int64_t)p * W + 4 * sub);
-    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-  }
-};
-
-// bf16 gradient rows (bf16 compute mode: dL/dX0 leaves the trunk's backward GEMMs in bf16);
-// the sums are fp32 like everything else here.
-struct RowsBf16Contrib {
-  const __bf16* src;  // [n, W]
-  int W;
-  __device__ inline void prepare() {}
-  __device__ inline float4 operator()(int32_t p, int sub, float& extra) const {
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    extra = 0.f;
-    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(src + (int64_t)p * W + 4 * sub);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-  }
-};
-
-// Two bf16 gradient tensors summed on the fly; the sum is rounded to bf16 first, as the elementwise
-// bf16 addition it replaces would have done.
-struct Rows2Bf16Contrib {
-  const __bf16* src;
-  const __bf16* src2;
-  int W;
-  __device__ inline void prepare() {}
-  __device__ inline float4 operator()(int32_t p, int sub, float& extra) const {
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    extra = 0.f;
-    const bf16x4_t a = *reinterpret_cast<const bf16x4_t*>(src + (int64_t)p * W + 4 * sub);
-    const bf16x4_t b = *reinterpret_cast<const bf16x4_t*>(src2 + (int64_t)p * W + 4 * sub);
-    float4 r;
-    r.x = (float)(__bf16)((float)a[0] + (float)b[0]);
-    r.y = (float)(__bf16)((float)a[1] + (float)b[1]);
-    r.z = (float)(__bf16)((float)a[2] + (float)b[2]);
-    r.w = (float)(__bf16)((float)a[3] + (float)b[3]);
-    return r;
-  }
-};
-
-// NCE output-table gradient, never materialised per (target, sample) pair:
-// d emb[idx[t,j]] += dlogit[t,j] * h[t,:]   d bias[idx[t,j]] += dlogit[t,j]
-// (backward of reference nce/index_linear.py:99-102; p = t*(K+1)+j)
 // Rows plus one scalar per GROUP of consecutive positions: embedding gradient rows dL/dX[b,f,:]
-// together with the LR gradient dL/dlr[b] that every field of row b shares (group = F).
+// together with the LR gradient dL/dlr[b] that every field of row b shares (group = F).  The scalar
+// is fp32 for bf16 rows too (bf16 compute mode: DeepFM's / AutoInt's dL/dX).
+template <class T>
 struct RowsExtraContrib {
-  const float* src;    // [n, ld]: the first W columns of a row are reduced
+  const T* src;        // [n, ld]: the first W columns of a row are reduced
   int W;
   int64_t ld;          // row stride of src (>= W)
   const float* extra;  // scalar of position p: extra[(p / group) * estride]
@@ -117,27 +90,13 @@ struct RowsExtraContrib {
   __device__ inline void prepare() {}
   __device__ inline float4 operator()(int32_t p, int sub, float& ex) const {
     ex = extra[(int64_t)(p / group) * estride];
-    return *reinterpret_cast<const float4*>(src + (int64_t)p * ld + 4 * sub);
+    return load4(src + (int64_t)p * ld + 4 * sub);
   }
 };
 
-// The same with bf16 rows (bf16 compute mode: DeepFM's / AutoInt's dL/dX); the scalar stays fp32.
-struct RowsExtraBf16Contrib {
-  const __bf16* src;   // [n, ld]
-  int W;
-  int64_t ld;
-  const float* extra;
-  int group;
-  int64_t estride;
-  __device__ inline void prepare() {}
-  __device__ inline float4 operator()(int32_t p, int sub, float& ex) const {
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    ex = extra[(int64_t)(p / group) * estride];
-    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(src + (int64_t)p * ld + 4 * sub);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-  }
-};
-
+// NCE output-table gradient, never materialised per (target, sample) pair:
+// d emb[idx[t,j]] += dlogit[t,j] * h[t,:]   d bias[idx[t,j]] += dlogit[t,j]
+// (backward of reference nce/index_linear.py:99-102; p = t*(K+1)+j)
 struct NceContrib {
   const float* dlogit;  // [T*(K+1)]
   const float* h;       // [T, P]

@@ -404,8 +404,6 @@ class SegPlan:
         import ctypes as C
         plans = [SegPlan(k, V, launch=False) for k, V in zip(key_lists, Vs)]
         cnt = len(plans)
-        if cnt == 1:          # same kernels, one problem
-            pass
         I64, PP = C.c_int64 * cnt, C.c_void_p * cnt
         n_arr, v_arr = I64(*[p.n for p in plans]), I64(*[int(v) for v in Vs])
         dev = key_lists[0].device

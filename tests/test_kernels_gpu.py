@@ -48,26 +48,39 @@ def _skewed_keys(n, V, seed):
     return k[torch.randperm(n, generator=g)]
 
 
+def _check_plan(plan, keys):
+    """Every array of `plan` against torch on the CPU: `keys` [n] int64, the key values as the sort orders them,
+    i.e. as unsigned 32-bit numbers.  A caller whose int32 keys can be negative (the merge plan's -1 padding) passes
+    `keys.long() & 0xFFFFFFFF`, never the signed values: the plan's own arrays are masked the same way here.
+    -> (number of runs, run index of every key)."""
+    n = keys.numel()
+    unsigned = lambda t: _cpu(t).long() & 0xFFFFFFFF
+    U = plan.count()
+    uniq_ref, inv = torch.unique(keys, return_inverse=True)
+    assert U == uniq_ref.numel()
+    assert torch.equal(unsigned(plan.uniq[:U]), uniq_ref)
+    sk = unsigned(plan.sorted_keys[:n])
+    assert torch.equal(sk, keys[_cpu(plan.perm[:n]).long()]) and bool((sk[1:] >= sk[:-1]).all())
+    assert torch.equal(_cpu(plan.perm[:n]).long(), torch.sort(keys, stable=True).indices)
+    starts = _cpu(plan.seg_start[:U + 1]).long()
+    assert int(starts[U]) == n and torch.equal(sk[starts[:U]], uniq_ref)
+    assert torch.equal(_cpu(plan.rank[:n]).long() - 1, inv[_cpu(plan.perm[:n]).long()])
+    return U, inv
+
+
+# single lists beyond the gradient shapes: four passes (26- and 31-bit keys), exactly one tile and two tiles plus one
 @pytest.mark.parametrize("n,V,W", [(1, 50, 16), (31, 50, 16), (32, 50, 16), (33, 7, 16),
                                    (5000, 1000, 16), (94208, 9449445, 16), (70001, 300, 32),
                                    (4097, 5, 64), (2000, 100, 4), (131072, 70000, 4), (131073, 70000, 4),
-                                   (638976, 9449445, 4)])
+                                   (638976, 9449445, 4),
+                                   (5000, 33762577, 4), (4097, 2**31 - 1, 4), (4096, 1000, 4), (8193, 1000, 4)])
 def test_seg_plan_and_reduce_rows(ops, n, V, W):
     """The plan must be THE stable sort of the keys (perm == torch's stable argsort), with runs,
     ranks and unique keys consistent with it."""
     keys = _skewed_keys(n, V, n)
     src = torch.randn(n, W, generator=torch.Generator().manual_seed(1))
     plan = ops.SegPlan(keys.to(torch.int32).to(DEV), V)
-    U = plan.count()
-    uniq_ref, inv = torch.unique(keys, return_inverse=True)
-    assert U == uniq_ref.numel()
-    assert torch.equal(_cpu(plan.uniq[:U]).long(), uniq_ref)
-    sk = _cpu(plan.sorted_keys[:n]).long()
-    assert torch.equal(sk, keys[_cpu(plan.perm[:n]).long()]) and bool((sk[1:] >= sk[:-1]).all())
-    assert torch.equal(_cpu(plan.perm[:n]).long(), torch.sort(keys, stable=True).indices)
-    starts = _cpu(plan.seg_start[:U + 1]).long()
-    assert int(starts[U]) == n and torch.equal(sk[starts[:U]], uniq_ref)
-    assert torch.equal(_cpu(plan.rank[:n]).long() - 1, inv[_cpu(plan.perm[:n]).long()])
+    U, inv = _check_plan(plan, keys)
     out = ops.seg_reduce_rows(plan, src.to(DEV), W)
     ref = torch.zeros(U, W, dtype=torch.float64).index_add_(0, inv, src.double())
     scale = torch.zeros(U, W, dtype=torch.float64).index_add_(0, inv, src.double().abs())
@@ -104,6 +117,7 @@ def test_seg_plan_merge_equals_sort(ops, lists, length, V):
     U = b.count()
     assert a.count() == U
     n = lists * length
+    _check_plan(a, keys.reshape(-1).long() & 0xFFFFFFFF)        # the padding sorts as the largest unsigned key
     for name in ("sorted_keys", "perm", "rank"):
         assert torch.equal(getattr(a, name)[:n], getattr(b, name)[:n]), name
     assert torch.equal(a.uniq[:U], b.uniq[:U]) and torch.equal(a.seg_start[:U + 1], b.seg_start[:U + 1])
@@ -114,11 +128,12 @@ def test_seg_plan_merge_equals_sort(ops, lists, length, V):
 
 @pytest.mark.parametrize("sizes", [((94208, 9449445), (638976, 9449445)), ((159744, 33762577), (1171456, 33762577)),
                                    ((31, 50), (5000, 70000)), ((4097, 5), (1, 9449445)), ((0, 100), (70001, 300)),
-                                   ((131073, 70000),), ((638976, 9449445), (94208, 200))])
+                                   ((131073, 70000),), ((638976, 9449445), (94208, 200)), ((0, 10), (0, 10))])
 def test_seg_plan_build_many_equals_single_plans(ops, sizes):
     """The multi-problem sort (both tables' plans from one chain of launches) must give, array by array, what
     one mapx_seg_plan per list gives — including lists of different key widths (3 and 4 passes in
-    one launch sequence), an empty list, and a list of one key."""
+    one launch sequence), an empty list, two empty lists, and a list of one key.  The single plan is the
+    one-problem case of the same kernels, so every plan, in either position, is also held against torch."""
     keys = [_skewed_keys(n, V, n + q).to(torch.int32).to(DEV) if n else torch.empty(0, dtype=torch.int32, device=DEV)
             for q, (n, V) in enumerate(sizes)]
     many = ops.SegPlan.build_many(keys, [V for _, V in sizes])
@@ -127,6 +142,8 @@ def test_seg_plan_build_many_equals_single_plans(ops, sizes):
         b = ops.SegPlan(k, V)
         U = b.count()
         assert a.count() == U == a2.count()
+        for plan in (a, b):            # a2 is compared with a below
+            _check_plan(plan, k.long().cpu())
         for name in ("sorted_keys", "perm", "rank"):
             assert torch.equal(getattr(a, name)[:n], getattr(b, name)[:n]), (name, n, V)
             assert torch.equal(getattr(a, name)[:n], getattr(a2, name)[:n]), (name, n, V)

@@ -64,6 +64,30 @@ def test_host_only_entry_points_work_without_gpu():
     assert torch.allclose(dist, probs.double())
 
 
+def test_seg_plan_workspace_of_one_list_is_the_one_problem_case():
+    """A single list is the one-problem case of the multi-list plan: one workspace layout, one figure; a second list
+    only ever adds to it."""
+    import ctypes as C
+    from mapx import native
+
+    def multi(sizes):
+        I64 = C.c_int64 * len(sizes)
+        return native.lib.mapx_seg_plan_multi_workspace_bytes(len(sizes), I64(*[n for n, _ in sizes]),
+                                                              I64(*[V for _, V in sizes]))
+
+    V = 9449445
+    sizes = (0, 1, 4096, 4097, 638976)
+    for n in sizes:
+        one = native.lib.mapx_seg_plan_workspace_bytes(n, V)
+        assert one == multi([(n, V)]), n
+        assert one == native.lib.mapx_seg_plan_workspace_bytes(n, 0), n        # the merge form passes V = 0
+        assert one >= 2 * 4 * n + 256
+    for a in sizes:
+        for b in sizes:
+            two = multi([(a, V), (b, 200)])
+            assert two >= multi([(a, V)]) and two >= multi([(b, 200)]), (a, b)
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import pytest
     import torch
