@@ -333,7 +333,7 @@ int seg_reduce_launch(const SegPlanView& pl, const Contrib& contrib, int W, floa
                       float* out_extra, void* ws, size_t ws_bytes, int32_t* zeroed_counter, hipStream_t stream,
                       const char* what) {
   if (pl.n == 0) return MAPX_OK;
-  MAPX_REQUIRE(W % 4 == 0 && W >= 4 && W <= 256, "%s: row width %d must be a multiple of 4", what, W);
+  MAPX_REQUIRE(W % 4 == 0 && W >= 4 && W <= 256, "%s: row width %d must be a multiple of 4 and at most 256", what, W);
   const size_t need = seg_reduce_partial_bytes(pl.n, W, EXTRA);
   if (ws_bytes < need || !ws) {
     set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);

@@ -383,6 +383,9 @@ class HipLayerNorm(nn.Module):
         return _LayerNorm.apply(x, self.weight, self.bias, self.eps)
 
 
+MAX_EMBED_SIZE = 256      # csrc/segreduce.h: seg_reduce_launch refuses wider rows (inside the first backward otherwise)
+
+
 class Embeddings(nn.Module):
     """One shared id space over all fields (reference layers.py:83-102): gather, optional LayerNorm
     over the embedding width (`embed_norm`), optional dropout (`embed_dropout_rate`)."""
@@ -396,6 +399,9 @@ class Embeddings(nn.Module):
         if config.embed_size % 4 != 0:
             raise NotImplementedError("embed_size must be a multiple of 4 (16-byte rows for the gather, "
                                       "segment-reduce and float4 elementwise kernels)")
+        if config.embed_size > MAX_EMBED_SIZE:
+            raise NotImplementedError(f"embed_size {config.embed_size} > {MAX_EMBED_SIZE}: the segment reduction of "
+                                      f"the gradient rows is built for rows of at most {MAX_EMBED_SIZE} floats")
         self.embedding = TableWeight(config.input_size, config.embed_size)
         std = math.sqrt(2.0 / float(config.num_fields + config.embed_size))
         with torch.no_grad():

@@ -404,10 +404,14 @@ class DeepFM(BaseModel):
     compute_dtype=bf16: the gathered rows and the MLP are bf16; the LR sum, the FM term and lr + bias + fm [B,1] stay
     fp32 — rounded once where that column joins the heads' bf16 input, added in fp32 to the CTR logit."""
     used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act"]
+    FM_EMBED_SIZES = (4, 8, 16, 32, 64)
 
     def __init__(self, config: Config):
         super().__init__(model_name="DeepFM", config=config)
         _refuse_bf16_mlp_options(config, "hidden_act", "hidden_dropout_rate")
+        if config.embed_size not in self.FM_EMBED_SIZES:      # (csrc/fm.hip refuses the others inside the first forward)
+            raise NotImplementedError(f"DeepFM: the FM kernels take embed_size in {self.FM_EMBED_SIZES} "
+                                      f"(embed_size={config.embed_size})")
         self.embed = Embeddings(config)
         self.embed.defer_plan = True
         self.lr_layer = LR(config)

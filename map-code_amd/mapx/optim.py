@@ -258,12 +258,15 @@ class MapxOptimizer:
             if t.table.sparse_grad is not None:
                 plan, r0, r1 = t.table.sparse_grad
                 if plan.n_uniq is None:          # gathered list (mapx.parallel): padding rows are zero
-                    live = torch.ones(r0.shape[0], device=r0.device)
+                    live = torch.ones(r0.shape[0], dtype=torch.bool, device=r0.device)
                 else:
-                    live = (torch.arange(r0.shape[0], device=r0.device) < plan.n_uniq[0]).float()
-                sq = sq + ((r0 ** 2).sum(1) * live).sum()
+                    live = torch.arange(r0.shape[0], device=r0.device) < plan.n_uniq[0]
+                # rows at and beyond n_uniq are never written (ops.seg_reduce_rows: torch.empty): selected out, not
+                # multiplied by zero — what the allocator left there may be inf or NaN, and NaN * 0 is NaN
+                zero = torch.zeros((), dtype=r0.dtype, device=r0.device)
+                sq = sq + torch.where(live, (r0 ** 2).sum(1), zero).sum()
                 if r1 is not None:
-                    sq = sq + ((r1 ** 2) * live).sum()
+                    sq = sq + torch.where(live, r1.view(-1) ** 2, zero).sum()
         coef = (self.max_grad_norm / (sq.sqrt() + 1e-6)).clamp(max=1.0)
         for g in self.groups:
             g["g"].mul_(coef)

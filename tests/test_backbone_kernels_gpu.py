@@ -300,6 +300,12 @@ SEG_CASES = [
     pytest.param(70001, 300, 16, 39, 20, 1, id="n70001-group39-ld20:runs-over-many-chunks-ragged-last-group"),
     pytest.param(4097, 5, 64, 1, 68, 68, id="n4097-V5-W64-ld68-stride68:five-long-runs"),
     pytest.param(20000, 9_449_445, 4, 25, 4, 1, id="n20000-W4-group25:wide-keys-narrow-rows"),
+    # one per lane-group form (tests/row_widths_ref.py), a shared scalar (group > 1) at a stride of its own
+    pytest.param(5000, 300, 12, 5, 20, 3, id="n5000-W12-ld20-group5-stride3:4-lanes-one-idle"),
+    pytest.param(5000, 300, 24, 7, 24, 2, id="n5000-W24-group7-stride2:8-lanes-two-idle"),
+    pytest.param(5000, 300, 40, 3, 48, 5, id="n5000-W40-ld48-group3-stride5:16-lanes-six-idle"),
+    pytest.param(5000, 300, 68, 23, 72, 3, id="n5000-W68-ld72-group23-stride3:second-round-of-one-lane"),
+    pytest.param(5000, 300, 128, 4, 128, 2, id="n5000-W128-group4-stride2:two-full-rounds"),
 ]
 
 
@@ -311,8 +317,8 @@ def test_seg_reduce_rows_extra(ops, n, V, W, group, ld, estride):
     g = torch.Generator().manual_seed(n + W)
     src = torch.randn(n, ld, generator=g)
     src_d = src.to(DEV)
-    if estride == 1:
-        extra = torch.randn(-(-n // group), generator=g)       # ceil(n / group) scalars
+    if estride == 1 or group > 1:
+        extra = torch.randn(-(-n // group) * estride, generator=g)       # ceil(n / group) scalars, `estride` apart
         extra_d = extra.to(DEV)
     else:                                                       # the scalar is column W of src itself
         assert estride == ld and ld > W
@@ -361,7 +367,7 @@ def _pack_check(ops, plan, uniq, U, rows0, rows1, maxc, live):
     assert not bool(rows[live:].any())
 
 
-@pytest.mark.parametrize("W0", [16, 32])
+@pytest.mark.parametrize("W0", [16, 32, 4, 12, 64, 128])
 @pytest.mark.parametrize("with_rows1", [True, False], ids=["rows1", "no-rows1"])
 def test_pack_sparse(ops, W0, with_rows1):
     n, V = 3000, 400

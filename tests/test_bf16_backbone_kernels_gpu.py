@@ -235,8 +235,8 @@ def test_seg_reduce_rows_extra_bf16(ops, n, V, W, group, ld, estride):
     g = torch.Generator().manual_seed(n + W)
     src = _rb(torch.randn(n, ld, generator=g))
     src_d = src.to(DEV).to(BF16)
-    if estride == 1:
-        extra = torch.randn(-(-n // group), generator=g)
+    if estride == 1 or group > 1:
+        extra = torch.randn(-(-n // group) * estride, generator=g)
         extra_d = extra.to(DEV)
     else:                                                       # a strided fp32 column: the scalar of position p at p * ld
         assert estride == ld and ld > W

@@ -271,12 +271,22 @@ def test_bf16_full_batch_vs_fp32_oracle(mode, B, F):
     """BASELINE batch (4096 x 23, K = 25, P = 32, H = 1000; and a ragged 777 x 39 Criteo-width batch) in bf16
     mode against the fp32 oracle on the step's own masks / negatives / replacements: loss, logits, every
     gradient within 1e-2."""
+    _bf16_full_batch_vs_fp32_oracle(mode, B, F)
+
+
+def test_bf16_full_batch_vs_fp32_oracle_at_embed_size_24():
+    """The same step and bound at embed_size = 24 (rows on 8 lanes, two of them idle; D = 552) and B = 1024."""
+    _bf16_full_batch_vs_fp32_oracle("MFP", 1024, 23, E=24)
+
+
+def _bf16_full_batch_vs_fp32_oracle(mode, B, F, E=16):
     from mapx import ops
     from mapx.dataset import synth_table
     from mapx.models import BaseModel
     from oracle import ref_model as R
     from util import make_config
-    cfg = dict(F=F, V=60000, E=16, H=1000, NL=3, NC=3, P=32, K=25)
+    cfg = dict(F=F, V=60000, E=E, H=1000, NL=3, NC=3, P=32, K=25)
+    tag = "B=4096" if E == 16 else f"B={B} E={E}"
     ids_np, y_np, _, _ = synth_table(B, F, cfg["V"], seed=1)
     cnt = np.bincount(ids_np.reshape(-1), minlength=cfg["V"]).astype(np.float32)
     torch.manual_seed(0)
@@ -314,14 +324,14 @@ def test_bf16_full_batch_vs_fp32_oracle(mode, B, F):
     loss.backward()
     with torch.no_grad():
         head(preacts=pre)
-    flips = _check_pattern(masks, pre, f"B=4096 {mode}")
+    flips = _check_pattern(masks, pre, f"{tag} {mode}")
     loss_r, out_r = head(relu_masks=masks)           # the fp32 oracle on the step's own ReLU pattern
     loss_r.backward()
     assert abs(float(loss.detach()) - float(loss_r)) <= 1e-2 * abs(float(loss_r))
     assert _rel(out.detach().float().cpu().numpy().reshape(out_r.shape), out_r.detach().numpy()) <= 1e-2
     worst = _grads_vs(model, {k: v.grad.numpy() for k, v in P.items() if torch.is_tensor(v) and v.requires_grad},
-                      1e-2, f"B=4096 {mode}")
-    print(f"[bf16 B=4096 {mode}] loss {float(loss.detach()):.6f} vs fp32 oracle {float(loss_r):.6f}; {flips} of "
+                      1e-2, f"{tag} {mode}")
+    print(f"[bf16 {tag} {mode}] loss {float(loss.detach()):.6f} vs fp32 oracle {float(loss_r):.6f}; {flips} of "
           f"{sum(v.numel() for v in pre.values())} ReLU units on the other side of the kink; "
           f"worst gradient {worst[1]:.2e} of scale at {worst[0]}")
 

@@ -268,3 +268,88 @@ def test_vocab_hex_path_needs_every_string_to_be_fixed_width_lower_case_hex():
     late = ["0a1f"] * 70 + ["0A1F", " a1f", "1_0f", "+a1f"]            # the odd ones come after the first 64
     codes, dec = encode_column(np.array(late))
     assert len(set(codes.tolist())) == 5 and [dec(c) for c in codes[-4:]] == late[-4:]
+
+
+@pytest.mark.parametrize("mode", ["MFP", "CTR"])
+def test_embed_size_above_256_is_refused_at_construction(mode):
+    """The segment reduction of the gradient rows refuses rows wider than 256 floats (csrc/segreduce.h); the model must
+    say so when it is built, not inside the first backward (under capture when the step is graphed).  256 builds."""
+    import copy
+    from mapx.models import BaseModel
+    cfg = copy.deepcopy(pg.CASES["A_f23_b7"])
+    cfg["E"] = 260
+    with pytest.raises(NotImplementedError, match="embed_size 260 > 256"):
+        BaseModel.from_config(make_config(cfg, mode, np.ones(cfg["V"], dtype=np.float32)))
+    cfg["E"] = 256
+    model = BaseModel.from_config(make_config(cfg, mode, np.ones(cfg["V"], dtype=np.float32)))
+    assert model.embed.embedding.weight.shape == (cfg["V"], 256)
+
+
+def test_width_test_sizes_reach_the_deep_loop_of_the_run_combine():
+    """tests/row_widths_ref.py, checked on the CPU: at every size of the reduction cases with n >= 20 000 the hot key's
+    run spans the 16 G + 1 chunks that pass B's 16-deep loop needs at every lane-group width (LG 4: 257 chunks), and
+    the list holds every form the row kernels take."""
+    import row_widths_ref as RW
+    assert {RW.form(W) for W in RW.ROW_WIDTHS} == {(4, "partial"), (8, "partial"), (16, "partial"), (16, "full"),
+                                                   (16, "rounds")}
+    assert RW.form(16) == (4, "full") and RW.form(32) == (8, "full") and max(RW.ROW_WIDTHS) == RW.MAX_ROW_WIDTH
+    assert {n for _, n, _ in RW.seg_sizes()} == {33, 20000, 2 ** 18 + 1}
+    assert RW.seg_chunk(2 ** 18) == 16 and RW.seg_chunk(2 ** 18 + 1) == 32
+    for W, n, V in RW.seg_sizes():
+        if n < 20000:
+            continue
+        assert V <= n // 50
+        keys = RW.skewed_keys(n, V, n + W)
+        run = int((keys == RW.HOT_KEY).sum())
+        assert run // RW.seg_chunk(n) >= RW.deep_loop_chunks(W), (W, n, run)
+
+
+@pytest.mark.parametrize("mode", ["MFP", "CTR"])
+def test_deepfm_refuses_an_embed_size_its_fm_kernels_do_not_take(mode):
+    """csrc/fm.hip takes embed_size 4, 8, 16, 32 and 64; DeepFM says so when it is built (embed_size = 12 used to build
+    and fail inside the first forward).  8 builds."""
+    import copy
+    from mapx.models import BaseModel
+    cfg = copy.deepcopy(pg.CASES["B_f25_b64"])
+    cnt = np.ones(cfg["V"], dtype=np.float32)
+    cfg["E"] = 12
+    with pytest.raises(NotImplementedError, match=r"embed_size in \(4, 8, 16, 32, 64\) \(embed_size=12\)"):
+        BaseModel.from_config(make_config(cfg, mode, cnt, backbone="DeepFM"))
+    cfg["E"] = 8
+    model = BaseModel.from_config(make_config(cfg, mode, cnt, backbone="DeepFM"))
+    assert model.embed.embedding.weight.shape == (cfg["V"], 8)
+
+
+def test_clipping_norm_ignores_the_unwritten_rows_of_a_sparse_gradient():
+    """The reduced gradient rows of a table have the capacity of the key list; rows at and beyond the number of unique
+    keys are never written.  Whatever the allocator left there (here NaN and inf) must not reach the clipping norm:
+    NaN * 0 is NaN, and one NaN coefficient turns every parameter into NaN (seen as a graph == eager failure after
+    tests that freed large buffers)."""
+    from types import SimpleNamespace
+    try:
+        from mapx.optim import MapxOptimizer
+    except ImportError as e:          # the HIP library is not built here
+        pytest.skip(str(e))
+    g = torch.Generator().manual_seed(0)
+    dense = torch.randn(40, generator=g)
+    r0, r1 = torch.randn(10, 8, generator=g), torch.randn(10, generator=g)
+    r0[6:], r1[6:] = float("nan"), float("inf")
+    want = float((dense.double() ** 2).sum() + (r0[:6].double() ** 2).sum() + (r1[:6].double() ** 2).sum()) ** 0.5
+    opt = object.__new__(MapxOptimizer)
+    opt.max_grad_norm = 0.5
+    opt.groups = [dict(g=dense.clone())]
+    plan = SimpleNamespace(n_uniq=torch.tensor([6, 0], dtype=torch.int32))
+    table = SimpleNamespace(sparse_grad=(plan, r0.clone(), r1.clone()))
+    opt.tables = [SimpleNamespace(table=table)]
+    opt.clip_grad_norm_()
+    coef = 0.5 / (want + 1e-6)
+    assert coef < 1.0
+    np.testing.assert_allclose(opt.groups[0]["g"].numpy(), (dense * coef).numpy(), rtol=1e-6)
+    np.testing.assert_allclose(table.sparse_grad[1][:6].numpy(), (r0[:6] * coef).numpy(), rtol=1e-6)
+    np.testing.assert_allclose(table.sparse_grad[2][:6].numpy(), (r1[:6] * coef).numpy(), rtol=1e-6)
+    # a gathered list (data-parallel merge, n_uniq None): every row counts
+    r0[6:], r1[6:] = 0.0, 0.0
+    opt.groups = [dict(g=dense.clone())]
+    table.sparse_grad = (SimpleNamespace(n_uniq=None), r0.clone(), r1.clone())
+    opt.clip_grad_norm_()
+    np.testing.assert_allclose(opt.groups[0]["g"].numpy(), (dense * coef).numpy(), rtol=1e-6)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import row_widths_ref as RW
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -22,7 +24,8 @@ def _cpu(x):
 
 
 # --------------------------------------------------------------------------- gather
-@pytest.mark.parametrize("n,E", [(0, 16), (1, 16), (7 * 23, 16), (4096 * 23, 16), (33, 8), (5, 6)])
+@pytest.mark.parametrize("n,E", [(0, 16), (1, 16), (7 * 23, 16), (4096 * 23, 16), (33, 8), (5, 6)] +
+                         [(4099, E) for E in RW.ROW_WIDTHS])
 def test_emb_gather_bit_exact(ops, n, E):
     g = torch.Generator().manual_seed(n + E)
     V = 1000
@@ -540,7 +543,8 @@ def test_colsum(ops, M, N):
                                rtol=0, atol=2e-6 * float(x.abs().sum(0).max()) + 1e-6)
 
 
-@pytest.mark.parametrize("B,D,NC", [(7, 368, 3), (64, 400, 3), (4096, 368, 3), (33, 624, 2), (100, 368, 3), (4, 368, 1)])
+@pytest.mark.parametrize("B,D,NC", [(7, 368, 3), (64, 400, 3), (4096, 368, 3), (33, 624, 2), (100, 368, 3), (4, 368, 1),
+                                    (96, 276, 3), (1024, 184, 3)])
 def test_cross_network_fwd_bwd_vs_oracle(ops, B, D, NC):
     """CrossNetV2 forward + hand-written backward chain vs autograd on the oracle.  B = 100, 33, 4:
     row counts whose last 32-row band ends 1-4 rows in, where the upper half-wave of the GEMM
@@ -673,10 +677,16 @@ def test_adamw_dense_trajectory_vs_oracle(ops, wd):
     np.testing.assert_allclose(_cpu(v).numpy(), v_ref.numpy(), rtol=2e-6, atol=1e-10)
 
 
-@pytest.mark.parametrize("W,with_bias", [(16, False), (32, True)])
+@pytest.mark.parametrize("W,with_bias", [(16, False), (32, True)] + [(W, b) for W in RW.ROW_WIDTHS for b in (False, True)])
 def test_lazy_table_adam_equals_dense_reference(ops, W, with_bias):
     """Row-sparse lazy AdamW == the reference's dense every-row-every-step AdamW (rows that
-    receive no gradient still decay and move by momentum), after a final flush."""
+    receive no gradient still decay and move by momentum), after a final flush; m and v as arrays of their own and as
+    the two halves of one record per row (row stride 2 W, the layout the optimizer uses)."""
+    for side_by_side in (False, True):
+        _lazy_table_adam_vs_dense(ops, W, with_bias, side_by_side)
+
+
+def _lazy_table_adam_vs_dense(ops, W, with_bias, side_by_side):
     from oracle import ref_model as R
     T, V = 40, 257
     sched, lambdas = _sched(ops, T, kind="cosine")
@@ -687,6 +697,9 @@ def test_lazy_table_adam_equals_dense_reference(ops, W, with_bias):
     br, bmr, bvr = b0.clone(), torch.zeros(V), torch.zeros(V)
     p, m, v = p0.to(DEV).clone(), torch.zeros(V, W, device=DEV), torch.zeros(V, W, device=DEV)
     b, bm, bv = b0.to(DEV).clone(), torch.zeros(V, device=DEV), torch.zeros(V, device=DEV)
+    if side_by_side:
+        mv, bmv = torch.zeros(V, 2 * W, device=DEV), torch.zeros(V, 2, device=DEV)
+        m, v, bm, bv = mv[:, :W], mv[:, W:], bmv[:, 0], bmv[:, 1]
     last = torch.zeros(V, dtype=torch.int32, device=DEV)
     done = torch.zeros(1, dtype=torch.int32, device=DEV)
     kw = dict(p1=b, m1=bm, v1=bv, wd1=0.0) if with_bias else {}
@@ -828,13 +841,14 @@ def test_nce_forward_reads_rows_through_their_pending_updates(ops, grouped):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("half", [False, True])
-def test_gather_reads_rows_through_their_pending_updates(ops, half):
+@pytest.mark.parametrize("half,E", [pytest.param(False, 16, id="False"), pytest.param(True, 16, id="True")] +
+                         [(False, E) for E in RW.ROW_WIDTHS] + [(True, E) for E in RW.BF16_ROW_WIDTHS])
+def test_gather_reads_rows_through_their_pending_updates(ops, half, E):
     """mapx_emb_gather_fwd(lazy=) / _bf16: the gather of a training step replays a stale row's missing zero-gradient
     updates in registers and writes nothing; bit-identical to the catch-up pass followed by the plain gather (fp32
     rows, and the bf16 rows of the bf16 compute mode), hot ids current, repeats in the id list."""
     from mapx import native as N
-    V, E, n, T_done = 5000, 16, 4096 * 3, 41
+    V, n, T_done = 5000, 4096 * 3 if E == 16 else 4096, 41
     sched, lambdas = _sched(ops, 120, kind="cosine", warm=10)
     aux = ops.make_replay_aux(1e-3, lambdas, 0.9, 0.999, 0.05).to(DEV)
     g = torch.Generator().manual_seed(4)
@@ -1015,6 +1029,28 @@ def test_grouped_feat_encoder_matches_dense(ops, arith, B, F, D):
                                atol=4e-6 * float((denc.view(B, -1).abs().t() @ final.abs().double()).max()) + 1e-6)
     if F > 30:
         assert float(_cpu(dw)[5 * P:6 * P].abs().max()) == 0.0       # unmasked field: exact zeros
+
+
+def test_grouped_feat_encoder_refuses_a_width_that_is_4_mod_8(ops):
+    """embed_size = 12 gives the encoder D + H = 23 * 12 + 1000 = 1276 input columns, 4 mod 8: the grouped kernels read
+    16-byte chunks of 8 bf16 / fp16 values and refuse it, naming the dense GEMM; the model must then take that one
+    (tests/test_model_gpu.py runs the step at this width against the oracle)."""
+    from mapx.models import BaseModel
+    from mapx.native import MapxError
+    from util import make_config
+    B, F, D, P = 96, 23, 1276, 32
+    g = torch.Generator().manual_seed(D)
+    mi = torch.randint(0, F, (B, 6), generator=g).to(DEV)
+    groups = ops.EncGroups(mi, F)
+    with pytest.raises(MapxError, match=r"enc_grouped_fwd: K % 8 != 0 .*use the dense encoder GEMM"):
+        ops.enc_grouped_fwd(torch.randn(B, D, generator=g).to(DEV), torch.randn(F * P, D, generator=g).to(DEV),
+                            torch.randn(F * P, generator=g).to(DEV), groups)
+    cfg = dict(F=F, V=500, E=12, H=1000, NL=1, NC=1, P=P, K=25)
+    model = BaseModel.from_config(make_config(cfg, "MFP", np.ones(cfg["V"], dtype=np.float32)))
+    assert model.feat_encoder.in_features == D and not model._grouped_head(mi)
+    cfg["E"] = 16
+    model = BaseModel.from_config(make_config(cfg, "MFP", np.ones(cfg["V"], dtype=np.float32)))
+    assert model.feat_encoder.in_features % 8 == 0 and model._grouped_head(mi)
 
 
 # ----------------------------------------------------------------------------- eval metrics (SURVEY §8 f2)

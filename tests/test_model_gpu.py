@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import paramgen as pg
+import row_widths_ref as RW
 from util import assert_digest, build_model, load_case, t
 
 pytestmark = pytest.mark.gpu
@@ -212,11 +213,36 @@ def test_full_batch_vs_fp64_oracle(mode, B, F, arith):
     twice — in fp64 (the exact answer) and in fp32 (the reference's CPU arithmetic).  Loss, logits
     and EVERY gradient (dense and table rows) must be within 1e-5 of the exact value at the tensor's
     scale (north star: 1e-5 fp32) and not noisier than the CPU fp32 path."""
+    _full_batch_vs_fp64_oracle(mode, B, F)
+
+
+# (E, B): the widths whose rows take another lane-group form than 16 (tests/row_widths_ref.py) and whose dense side has
+# D = 23 E = 184, 276, 552, 1472 instead of 368; B = 1024 x H = 1000 is 8 x 16 tiles, the threshold of ops.planes_wanted
+WIDTH_STEPS = [(8, 1024), (12, 1024), (24, 1024), (64, 1024), (12, 96)]
+
+
+@pytest.mark.parametrize("E,B", WIDTH_STEPS)
+@pytest.mark.parametrize("mode", ["MFP", "RFD", "CTR"])
+def test_full_batch_vs_fp64_oracle_at_other_embed_sizes(mode, E, B, arith):
+    """The step of test_full_batch_vs_fp64_oracle, same assertions, at embed_size 8, 12, 24 and 64 (F = 23, H = 1000).
+    At E = 12 the first layers have K = 276 (K % 8 == 4: no weight planes) and the hidden ones K = 1000 (planes at
+    B = 1024, none at B = 96); the encoder and head widths D + H are 4 mod 8 too."""
+    from mapx import ops
+    assert E in RW.ROW_WIDTHS
+    if B == 1024:
+        assert ops.planes_wanted(1024, 1000, 1000) and not ops.planes_wanted(1024, 1000, 23 * 12)
+    else:
+        assert not ops.planes_wanted(B, 1000, 1000) and not ops.planes_wanted(B, 1000, 23 * E)
+    _full_batch_vs_fp64_oracle(mode, B, 23, E=E)
+
+
+def _full_batch_vs_fp64_oracle(mode, B, F, E=16, H=1000):
     from mapx import ops
     from mapx.dataset import synth_table
     from util import make_config
     from mapx.models import BaseModel
-    cfg = dict(F=F, V=60000, E=16, H=1000, NL=3, NC=3, P=32, K=25)
+    cfg = dict(F=F, V=60000, E=E, H=H, NL=3, NC=3, P=32, K=25)
+    tag = f"{mode} B={B} F={F}" + ("" if E == 16 else f" E={E}")
     ids_np, y_np, _, _ = synth_table(B, F, cfg["V"], seed=1)
     cnt = np.bincount(ids_np.reshape(-1), minlength=cfg["V"]).astype(np.float32)
     torch.manual_seed(0)
@@ -271,7 +297,7 @@ def test_full_batch_vs_fp64_oracle(mode, B, F, arith):
     pre32 = {}
     loss32, out32, _, g32 = _oracle_pass(mode, P, inputs, cfg, cnt, torch.float32, preacts=pre32)
     flips32 = sum(int(((z > 0) != hip_masks[k]).sum()) for k, z in pre32.items())
-    print(f"[{mode} B={B} F={F}] ReLU units decided differently from fp64: hip {flips}, hip vs cpu fp32 {flips32} "
+    print(f"[{tag}] ReLU units decided differently from fp64: hip {flips}, hip vs cpu fp32 {flips32} "
           f"of {sum(z.numel() for z in pre64.values())}")
     assert abs(float(loss.detach()) - float(loss64)) <= 2e-6 * abs(float(loss64)), (float(loss.detach()), float(loss64))
     # logits: 1e-5 of max(1, |logit|) element by element
@@ -293,7 +319,7 @@ def test_full_batch_vs_fp64_oracle(mode, B, F, arith):
             n1 = names[id(table.p1)]
             report[n1] = _three_way(n1, g1, g32[n1], g64[n1])
     worst = max(report, key=lambda k: report[k][0])
-    print(f"[{mode} B={B} F={F}] worst gradient error vs fp64 / scale: hip {report[worst][0]:.2e} at {worst}; "
+    print(f"[{tag}] worst gradient error vs fp64 / scale: hip {report[worst][0]:.2e} at {worst}; "
           f"cpu fp32 oracle on its own pattern: {max(v[1] for v in report.values()):.2e}")
 
 
@@ -350,6 +376,66 @@ def test_cross_tower_depths_vs_oracle(E, NC):
         else:
             got = p.grad.cpu()
         np.testing.assert_allclose(got.numpy(), params[name].grad.numpy(), rtol=2e-5, atol=2e-6, err_msg=name)
+
+
+@pytest.mark.parametrize("backbone,mode,E", [("DeepFM", "MFP", 8), ("AutoInt", "CTR", 12)])
+def test_other_backbones_at_narrow_embed_sizes_vs_float64(backbone, mode, E):
+    """Rows on four lanes of which two (E = 8) or one (E = 12) idle, at B = 96, in the manner of
+    test_cross_tower_depths_vs_oracle, same tolerances, the reference in float64 on the step's own ReLU pattern
+    (bf16_backbones_ref.step).  DeepFM MFP: the LR weight is the scalar table p1 of the embedding's rows, so its
+    gradient comes out of the reduction with the extra scalar and the heads read H + 1 columns; E = 8 because the FM
+    kernels take 4, 8, 16, 32 and 64 (DeepFM refuses 12 when it is built: tests/test_host_surface.py).  AutoInt CTR:
+    2 layers x 2 heads x 12, the first with W_res (12 -> 24)."""
+    import bf16_backbones_ref as BR
+    from mapx import ops
+    from mapx.layers import MultiHeadSelfAttention
+    from mapx.models import BaseModel
+    from oracle import ref_model as R
+    from util import check_pattern, hook_relu_pattern, make_config
+    B, cfg = 96, dict(F=23, V=2000, E=E, H=64, NL=2, NC=0, P=32, K=25)
+    F, L = cfg["F"], int(cfg["F"] * 0.3)
+    g = torch.Generator().manual_seed(12)
+    cnt = (1.0 + 50.0 * torch.rand(cfg["V"], generator=g) ** 4).numpy().astype(np.float32)
+    torch.manual_seed(12)
+    model = BaseModel.from_config(make_config(cfg, mode, cnt if mode == "MFP" else None, backbone=backbone)).to(DEV)
+    ai = pg.extras_of(backbone) or None
+    masks, logits = hook_relu_pattern(model), {}
+    for name, mod in model.named_modules():
+        if isinstance(mod, MultiHeadSelfAttention):
+            def attn_hook(m, i, o, name=name):
+                masks[name] = (o.detach() > 0).cpu()
+            mod.register_forward_hook(attn_hook)
+    ids = torch.randint(10, cfg["V"], (B, F), generator=g)
+    model.train()
+    if mode == "MFP":
+        mi = torch.stack([torch.randperm(F, generator=g)[:L] for _ in range(B)])
+        noise = torch.randint(0, cfg["V"], (B, L, cfg["K"]), generator=g)
+        masked, labels, _ = ops.dynamic_mask_mfp(ids.to(DEV), L, masked_index=mi.to(DEV))
+        model.mfp_criterion.return_logits = True
+        model.mfp_criterion.register_forward_hook(lambda m, i, o: logits.__setitem__("out", o[1].detach()))
+        loss = model(input_ids=masked, labels=labels, masked_index=mi.to(DEV), noise_samples=noise.to(DEV))[0]
+        batch = dict(ids=masked.cpu(), labels=labels.cpu(), masked_index=mi, noise=noise,
+                     logq=R.nce_buffers(cnt)[0], dims=(F, cfg["P"], cfg["K"]))
+    else:
+        y = torch.randint(0, 2, (B,), generator=g)
+        loss, out = model(input_ids=ids.to(DEV), labels=y.to(DEV))
+        logits["out"] = out.detach()
+        batch = dict(ids=ids, y=y)
+    loss.backward()
+    params = {n: p.detach().cpu().numpy() for n, p in model.named_parameters()}
+    pre = {}
+    BR.step(backbone, mode, params, batch, num_hidden=cfg["NL"], ai=ai, preacts=pre)
+    flips = check_pattern(masks, pre, f"{backbone} {mode} E={E}", tol=2e-6)
+    loss_ref, logits_ref, ref = BR.step(backbone, mode, params, batch, num_hidden=cfg["NL"], ai=ai, relu_masks=masks)
+    np.testing.assert_allclose(float(loss.detach()), loss_ref, rtol=1e-5)
+    np.testing.assert_allclose(logits["out"].cpu().numpy().ravel(), logits_ref.ravel(), rtol=1e-5, atol=1e-6)
+    grads = _all_grads(model)
+    assert set(grads) == set(ref), (sorted(grads), sorted(ref))
+    worst = max((BR.rel(grads[n].cpu().numpy(), ref[n]), n) for n in grads)
+    print(f"[{backbone} {mode} B={B} F={F} E={E}] {flips} ReLU units on the other side of the kink; worst gradient error "
+          f"vs fp64 / scale: hip {worst[0]:.2e} at {worst[1]}")
+    for n, got in grads.items():
+        np.testing.assert_allclose(got.cpu().numpy(), ref[n].reshape(got.shape), rtol=2e-5, atol=2e-6, err_msg=n)
 
 
 # ----------------------------------------------------------------------------- other backbones (§8 f4)

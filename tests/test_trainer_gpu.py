@@ -42,26 +42,59 @@ def _step_inputs(case, cfg, step):
                 y=(r.random(B) < 0.3).astype(np.int64), feat_count=inp["feat_count"])
 
 
-def _oracle_loop(mode, cfg, params, steps, case, total, warmup, kind, lr0, wd, backbone="DCNv2"):
+def _synth_step_inputs(cfg, step):
+    """_step_inputs without a fixture case: ids of a skewed per-field vocabulary (cfg carries B and mask_ratio), fresh
+    masks / negatives / labels per step."""
+    r = np.random.default_rng(7000 + step)
+    B, F, K, V = cfg["B"], cfg["F"], cfg["K"], cfg["V"]
+    L = int(F * cfg["mask_ratio"])
+    lo, hi = pg.field_ranges(F, V)
+    ids = lo[None, :] + np.floor(r.random((B, F)) ** 3 * (hi - lo)[None, :]).astype(np.int64)
+    cnt = (1.0 + np.random.default_rng(7).integers(0, 50, V)).astype(np.float32)
+    return dict(ids=ids.astype(np.int64), mi=r.integers(0, F, (B, L)).astype(np.int64),
+                noise=r.integers(0, V, (B, L, K)).astype(np.int64),
+                repl=ids[r.integers(0, B, (B, L)), r.integers(0, F, (B, L))].astype(np.int64),
+                y=(r.random(B) < 0.3).astype(np.int64), feat_count=cnt)
+
+
+def _oracle_loop(mode, cfg, params, steps, case, total, warmup, kind, lr0, wd, backbone="DCNv2", step_inputs=None,
+                 relu_masks=None):
+    """`params`: the arrays of a fixture case, or a model's state_dict() (its trainable tensors are taken: the sampler's
+    and the noise distribution's buffers are not parameters).  `step_inputs(s)`: the batch of step s, default the
+    fixture case's (_step_inputs).  `relu_masks[s]` (DCNv2, MFP / CTR): the ReLU pattern of the step under test at step
+    s, imposed on the oracle after checking that the two patterns differ only at units whose pre-activation is zero to
+    fp32 rounding (util.check_pattern, 2e-6 of the layer's scale): one such unit on the other side of the kink changes
+    a whole row of the first layer's weight gradient, and AdamW turns any change of a gradient into a step of ~lr."""
     from oracle import ref_model as R
-    P = {k: t(v).clone().requires_grad_(True) for k, v in params.items()}
+    from util import check_pattern
+    inputs_of = step_inputs or (lambda s: _step_inputs(case, cfg, s))
+    params = {k: (v.detach().cpu() if torch.is_tensor(v) else t(v)) for k, v in params.items()}
+    P = {k: v.clone().requires_grad_(True) for k, v in params.items()
+         if v.dtype.is_floating_point and "alias" not in k and "logprob" not in k}
     m = {k: torch.zeros_like(p) for k, p in P.items()}
     v = {k: torch.zeros_like(p) for k, p in P.items()}
     losses = []
     for s in range(steps):
-        si = _step_inputs(case, cfg, s)
+        si = inputs_of(s)
         ids = t(si["ids"])
+        pre = {}
+        trunk = lambda x: R.trunk(P, x, cfg["NC"], cfg["NL"], relu_masks=relu_masks[s], preacts=pre)
         if mode == "MFP":
             logq, _, _ = R.nce_buffers(si["feat_count"])
             masked, labels = R.dynamic_mask_mfp(ids, t(si["mi"]))
-            fin = R.final_of(backbone, P, masked, cfg["NC"], cfg["NL"], pg.extras_of(backbone))
+            fin = trunk(masked) if relu_masks is not None else \
+                R.final_of(backbone, P, masked, cfg["NC"], cfg["NL"], pg.extras_of(backbone))
             loss, _, _ = R.mfp_head(P, fin, labels, t(si["mi"]), t(si["noise"]), logq, cfg["F"], cfg["P"], cfg["K"])
         elif mode == "RFD":
             rep, labels = R.dynamic_mask_rfd(ids, t(si["mi"]), t(si["repl"]))
             loss = R.rfd_head(P, R.final_of(backbone, P, rep, cfg["NC"], cfg["NL"], pg.extras_of(backbone)), labels)[0]
         else:
-            logits = R.ctr_logits_of(backbone, P, ids, cfg["NC"], cfg["NL"], pg.extras_of(backbone))
+            logits = R.ctr_head(P, trunk(ids))[0] if relu_masks is not None else \
+                R.ctr_logits_of(backbone, P, ids, cfg["NC"], cfg["NL"], pg.extras_of(backbone))
             loss = torch.nn.functional.binary_cross_entropy_with_logits(logits.view(-1), t(si["y"]).float())
+        if relu_masks is not None:
+            assert backbone == "DCNv2" and mode != "RFD"
+            check_pattern(relu_masks[s], pre, f"{mode} step {s}", tol=2e-6)
         loss.backward()
         losses.append(float(loss.detach()))
         lr = lr0 * R.lr_lambda(kind, s, total, warmup)
@@ -135,6 +168,61 @@ def test_training_trajectory_matches_reference_semantics(mode, kind, warm, backb
         got = sd[k].cpu()
         # 8 AdamW steps move parameters by ~8e-3; fp32 parity of the whole trajectory
         np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=1e-4, atol=2e-6, err_msg=k)
+
+
+@pytest.mark.parametrize("E", [12, 64])
+@pytest.mark.parametrize("mode,kind", [("MFP", "cosine"), ("CTR", "const")])
+def test_training_trajectory_at_other_embed_sizes(mode, kind, E):
+    """Eight optimizer steps of DCNv2 at embed_size 12 (rows on four lanes, one idle) and 64 (sixteen lanes) with the
+    assertions of test_training_trajectory_matches_reference_semantics: batches of 64 over 3000 ids leave most rows
+    without a gradient for several steps, so the replay of the lazy AdamW runs at these widths (max_gap = 3).
+
+    The oracle runs on each step's own ReLU pattern (_oracle_loop): at E = 12 in CTR mode unit 18 of the first deep layer
+    sits on the kink for one batch row of the second step; compared on the oracle's own pattern that one unit's row
+    of the weight gradient differs, AdamW makes ~lr of it, and after eight steps 178 of 36 000 embedding elements were
+    off by up to 2.9e-3 with every kernel right (each gradient within 2e-7 of float64 from the step's own
+    parameters)."""
+    from mapx import ops
+    from mapx.models import BaseModel
+    from mapx.optim import MapxOptimizer
+    from util import make_config
+    cfg = dict(F=23, V=3000, E=E, H=64, NL=3, NC=3, P=32, K=25, B=64, mask_ratio=0.3)
+    steps, total, warmup, lr0, wd = 8, 10, 0, 1e-3, 5e-2
+    inputs = lambda s: _synth_step_inputs(cfg, s)
+    torch.manual_seed(E)
+    model = BaseModel.from_config(make_config(cfg, mode, inputs(0)["feat_count"] if mode == "MFP" else None)).to(DEV)
+    start = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    from util import hook_relu_pattern
+    masks, patterns = hook_relu_pattern(model), []
+    opt = MapxOptimizer(model, _targs(lr_sched=kind, learning_rate=lr0, weight_decay=wd), num_training_steps=total,
+                        num_warmup_steps=warmup, max_gap=3)
+    model.train()
+    L = int(cfg["F"] * cfg["mask_ratio"])
+    losses = []
+    for s in range(steps):
+        si = inputs(s)
+        ids = t(si["ids"], DEV)
+        if mode == "MFP":
+            masked, labels, mi = ops.dynamic_mask_mfp(ids, L, masked_index=t(si["mi"], DEV))
+            loss = model(input_ids=masked, labels=labels, masked_index=mi, noise_samples=t(si["noise"], DEV))[0]
+        else:
+            loss = model(input_ids=ids, labels=t(si["y"], DEV))[0]
+        patterns.append(dict(masks))
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+    ref_losses, ref_params = _oracle_loop(mode, cfg, start, steps, None, total, warmup, kind, lr0, wd,
+                                          step_inputs=inputs, relu_masks=patterns)
+    np.testing.assert_allclose(losses, ref_losses, rtol=2e-5)
+    opt.flush()
+    sd = model.state_dict()
+    assert set(ref_params) == {n for n, _ in model.named_parameters()}
+    off = {}
+    for k, ref in ref_params.items():                 # every tensor, so that a failure names all that moved wrongly
+        bad = ~torch.isclose(sd[k].cpu(), ref, rtol=1e-4, atol=2e-6)
+        if bool(bad.any()):
+            off[k] = (int(bad.sum()), ref.numel(), float((sd[k].cpu() - ref).abs().max()))
+    assert not off, f"(elements off, of, max |difference|) per tensor: {off}"
 
 
 def test_untouched_rows_still_decay_like_the_reference():
@@ -282,18 +370,24 @@ def test_two_ranks_graphed_exchange_equals_eager(tmp_path):
         assert torch.equal(outs["graph"][0][k], outs["eager"][0][k]), f"graphed exchange != eager exchange on {k}"
 
 
-@pytest.mark.parametrize("max_grad_norm,backbone,full,epochs",
-                         [(0.0, "DCNv2", 9, 2), (0.5, "DCNv2", 9, 2), (0.0, "DeepFM", 9, 2),
+@pytest.mark.parametrize("max_grad_norm,backbone,full,epochs,E",
+                         [pytest.param(0.0, "DCNv2", 9, 2, 16, id="0.0-DCNv2-9-2"),
+                          pytest.param(0.5, "DCNv2", 9, 2, 16, id="0.5-DCNv2-9-2"),
+                          pytest.param(0.0, "DeepFM", 9, 2, 16, id="0.0-DeepFM-9-2"),
                           # GRAPH_AFTER full batches per epoch: the step is captured right after the
                           # epoch-end flush (no stale row at trace time) — the lazy catch-up must be
                           # in the graph all the same
-                          (0.0, "DCNv2", 3, 4), (0.5, "DCNv2", 3, 4)])
-def test_graph_replay_equals_eager_bitwise(max_grad_norm, backbone, full, epochs):
+                          pytest.param(0.0, "DCNv2", 3, 4, 16, id="0.0-DCNv2-3-4"),
+                          pytest.param(0.5, "DCNv2", 3, 4, 16, id="0.5-DCNv2-3-4"),
+                          # the row kernels' other lane-group forms (tests/row_widths_ref.py)
+                          pytest.param(0.0, "DCNv2", 9, 2, 12, id="0.0-DCNv2-9-2-E12"),
+                          pytest.param(0.0, "DCNv2", 9, 2, 64, id="0.0-DCNv2-9-2-E64")])
+def test_graph_replay_equals_eager_bitwise(max_grad_norm, backbone, full, epochs, E):
     """The captured-hipGraph step and the eager step draw the same Philox streams (device-side
     counter) and run the same kernels: identical parameters after two epochs, bit for bit.
     With gradient clipping (as with N > 1) only mask + forward + backward are captured and the
     rest of the step runs eagerly after each replay (trainer.GraphedBackward)."""
-    _graph_equals_eager(max_grad_norm, backbone, full, epochs)
+    _graph_equals_eager(max_grad_norm, backbone, full, epochs, E=E)
 
 
 @pytest.mark.gpu
@@ -311,22 +405,23 @@ def test_graph_replay_equals_eager_bitwise_with_streaming_hidden_layers(monkeypa
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("use_graph", [True, False])
-def test_rows_read_through_pending_updates_train_like_the_catch_up_pass(use_graph):
+@pytest.mark.parametrize("use_graph,E", [pytest.param(True, 16, id="True"), pytest.param(False, 16, id="False"),
+                                         (True, 12), (False, 12), (True, 64), (False, 64)])
+def test_rows_read_through_pending_updates_train_like_the_catch_up_pass(use_graph, E):
     """nce.LAZY_FOLD and layers.EMB_LAZY_FOLD (opt-in, MAPX_LAZY_FOLD=1 / MAPX_EMB_LAZY_FOLD=1): a training step without
     the tables' catch-up passes — the loss kernel and the embedding gather replay stale rows in registers, the gradient
     updates write them once — leaves, after two epochs with a ragged last batch, the parameters of the step with the
     catch-up passes, bit for bit (graphed and eager)."""
-    _graph_equals_eager(0.0, "DCNv2", 9, 2, arms=((use_graph, True), (use_graph, False)))
+    _graph_equals_eager(0.0, "DCNv2", 9, 2, arms=((use_graph, True), (use_graph, False)), E=E)
 
 
-def _graph_equals_eager(max_grad_norm, backbone, full, epochs, tail=100, arms=((True, None), (False, None))):
+def _graph_equals_eager(max_grad_norm, backbone, full, epochs, tail=100, arms=((True, None), (False, None)), E=16):
     from mapx.arguments import TrainingArguments
     from mapx.dataset import OurDataset, synth_table
     from mapx.models import BaseModel
     from mapx.trainer import Trainer
     from util import make_config
-    cfg = dict(F=23, V=3000, E=16, H=64, NL=3, NC=3, P=32, K=25)
+    cfg = dict(F=23, V=3000, E=E, H=64, NL=3, NC=3, P=32, K=25)
     ids, labels, _, _ = synth_table(512 * full + tail, 23, cfg["V"], seed=3)    # ragged last batch
     cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
     out = []
