@@ -693,6 +693,37 @@ int mapx_act_fwd(int kind, const float* z, int64_t M, int N, float* y, int64_t l
 int mapx_act_bwd(int kind, const float* dy, int64_t ld_dy, const float* z, int64_t M, int N, float* dz,
                  hipStream_t stream);
 
+/* ------------------------------------------------------------------ the Transformer trunk in bf16 compute mode
+ * The bf16 I/O forms of the kernels above: bf16 tensors are widened on load, every sum is fp32,
+ * a store rounds to nearest even once.  mapx_mha_*_bf16: qkv, o, d_o, d_qkv bf16, probs fp32, the same keep mask
+ * (mapx_mha_dropout_mask serves both).  mapx_field_pool_*_bf16: x, out, g, dx bf16; scores, weights, d_scores fp32.
+ * mapx_dropout_bf16 / mapx_act_*_bf16: x * scale, f(z) and dy f'(z) in fp32, the saved pre-activation z is bf16; the
+ * Philox mask does not depend on the element type. */
+int mapx_mha_fwd_bf16(const mapx_bf16* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed, uint64_t offset,
+                      const int32_t* offset_dev_opt, mapx_bf16* o, float* probs, hipStream_t stream);
+int mapx_mha_bwd_bf16(const mapx_bf16* qkv, const float* probs, const mapx_bf16* d_o, int64_t B, int F, int E, int H,
+                      float p, uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt, mapx_bf16* d_qkv,
+                      hipStream_t stream);
+int mapx_field_pool_fwd_bf16(const mapx_bf16* x, const float* scores_opt, int64_t B, int F, int E, int mode,
+                             mapx_bf16* out, float* weights_opt, hipStream_t stream);
+int mapx_field_pool_bwd_bf16(const mapx_bf16* g, const mapx_bf16* x, const float* weights_opt, int64_t B, int F, int E,
+                             int mode, mapx_bf16* dx, float* d_scores_opt, hipStream_t stream);
+int mapx_dropout_bf16(const mapx_bf16* x, int64_t n, float p, uint64_t seed, uint64_t offset,
+                      const int32_t* offset_dev_opt, mapx_bf16* out, hipStream_t stream);
+int mapx_act_fwd_bf16(int kind, const mapx_bf16* z, int64_t M, int N, mapx_bf16* y, int64_t ldy, hipStream_t stream);
+int mapx_act_bwd_bf16(int kind, const mapx_bf16* dy, int64_t ld_dy, const mapx_bf16* z, int64_t M, int N, mapx_bf16* dz,
+                      hipStream_t stream);
+/* Residual add + LayerNorm over rows [R, E] of bf16 (E % 4 == 0, E <= 64): y = LN(x + s_opt) (s_opt NULL: LN(x)).
+ * The sum is formed in fp32 from the two bf16 addends and is NOT rounded before it is normalised; stats [R,2] =
+ * {mean, rstd} fp32.  Backward recomputes the sum from x and s_opt and writes dsum [R,E] bf16 — the gradient of both
+ * addends — and part [mapx_add_layernorm_bwd_groups(R, E), 2E] fp32: one row (dL/dw | dL/db) per workgroup, to be
+ * summed over the rows (mapx_sum_tasks).  No atomics: bitwise deterministic. */
+int mapx_add_layernorm_fwd_bf16(const mapx_bf16* x, const mapx_bf16* s_opt, int64_t R, int E, const float* w,
+                                const float* b, float eps, mapx_bf16* y, float* stats, hipStream_t stream);
+int mapx_add_layernorm_bwd_groups(int64_t R, int E);
+int mapx_add_layernorm_bwd_bf16(const mapx_bf16* dy, const mapx_bf16* x, const mapx_bf16* s_opt, const float* w,
+                                const float* stats, int64_t R, int E, mapx_bf16* dsum, float* part, hipStream_t stream);
+
 /* ------------------------------------------------------------------ vocabulary builders (f4)
  * One categorical field of data_preprocess/proc_avazu.py:237-262 / proc_criteo.py:147-163:
  *   for k, v in Counter(feat).most_common(): if v >= n_core: feat_map[name-k] = len(feat_map)

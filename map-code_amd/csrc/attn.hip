@@ -19,10 +19,8 @@ constexpr int kAttnMaxF = 64, kAttnMaxA = 64;   // one lane per field; LDS budge
 
 // Element type T of q, k, v, o, dO, dq, dk, dv: float, or bf16_t (bf16 compute mode).  Only the global
 // loads and stores differ: a load widens to fp32 into the LDS staging (which stays fp32: the same LDS budget), all
-// arithmetic is the fp32 code below, a store rounds to nearest even once.  P is fp32 for both.
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+// arithmetic is the fp32 code below, a store rounds to nearest even once.  P is fp32 for both.  (bf16_t and its
+// vector types: common.h.)
 
 // Elements per staging load.  A group starts at element g*F*A, which is only 2-byte aligned when F*A is odd: 8-byte
 // loads when F*A % 4 == 0, 4-byte ones when it is even, single elements otherwise (A = 7, A = 1 with odd F).
@@ -39,8 +37,8 @@ __device__ inline int attn_vec(int FA, const void* a, const void* b, const void*
 template <int V, class T>
 __device__ inline void attn_load(const T* __restrict__ p, float (&f)[V]) {
   if constexpr (V == 4) {
-    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
-    f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2]; f[3] = (float)v[3];
+    const float4 v = load4(p);
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
   } else if constexpr (V == 2) {
     const bf16x2_t v = *reinterpret_cast<const bf16x2_t*>(p);
     f[0] = (float)v[0]; f[1] = (float)v[1];

@@ -93,4 +93,24 @@ __device__ inline float group_sum(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- bf16 I/O (bf16 compute mode)
+// Kernels templated on an element type T = float | bf16_t differ only here: a load widens to fp32 (exact), all
+// arithmetic is fp32, a store rounds to nearest even once (v_cvt_pk_bf16_f32).
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+// Four consecutive elements (16-byte aligned floats / 8-byte aligned bf16) as fp32, and back.
+__device__ inline float4 load4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }
+__device__ inline float4 load4(const bf16_t* __restrict__ p) {
+  const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ inline void store4(float* __restrict__ p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ inline void store4(bf16_t* __restrict__ p, const float4& v) {
+  bf16x4_t o;
+  o[0] = (bf16_t)v.x; o[1] = (bf16_t)v.y; o[2] = (bf16_t)v.z; o[3] = (bf16_t)v.w;
+  *reinterpret_cast<bf16x4_t*>(p) = o;
+}
+
 }  // namespace mapx

@@ -10,6 +10,12 @@
 // Layout (attn.hip's): one wave per group, Q/K/V rows in LDS (16-byte rows, float4 loads along dh), one lane per
 // query row, two groups per wave when F <= 32.  The F x F probabilities live in LDS at a row pitch of F+1 floats
 // (lane i walks row i: conflict-free).  The work is tiny and HBM-bound: qkv in, O and P out.
+//
+// Element type T of qkv, o, d_o and d_qkv (and of the pooling's x, out, g, dx): float, or bf16_t in bf16 compute mode
+// (DESIGN §4.6).  Only the global loads and stores differ (common.h load4 / store4): a load widens into the same fp32
+// LDS rows, the arithmetic is the fp32 code, a store rounds once.  P, the pooling weights and d_scores are fp32 for
+// both.  A head's row section starts at a multiple of 4 elements and is a multiple of 4 wide, so the four-element
+// accesses are 8-byte aligned in bf16 as they are 16-byte aligned in fp32.
 #include "../../include/mapx_hip.h"
 #include "common.h"
 
@@ -46,23 +52,24 @@ __device__ inline float dot4(const float4& a, const float4& b, float s) {
 }
 
 // Cooperative 16-byte loads of `nsec` row sections of width dh (each starting at column col0 + s*E of the rows
-// b*F .. b*F+F-1, row pitch ld floats) into LDS at [s][r][LD].
-__device__ inline void load_sections(const float* __restrict__ src, int64_t ld, int64_t row0, int col0, int E,
+// b*F .. b*F+F-1, row pitch ld elements) into LDS at [s][r][LD].
+template <class T>
+__device__ inline void load_sections(const T* __restrict__ src, int64_t ld, int64_t row0, int col0, int E,
                                      int nsec, int F, int dh, int LD, float* dst, int li, int LW) {
   const int dh4 = dh / 4;
   const int n = nsec * F * dh4;
   for (int t = li; t < n; t += LW) {
     const int c = t % dh4, rs = t / dh4, r = rs % F, s = rs / F;
-    const float4 v = *reinterpret_cast<const float4*>(src + (row0 + r) * ld + col0 + s * E + 4 * c);
+    const float4 v = load4(src + (row0 + r) * ld + col0 + s * E + 4 * c);
     *reinterpret_cast<float4*>(dst + (s * F + r) * LD + 4 * c) = v;
   }
 }
 
 // DHB: dh rounded up to a bucket (registers hold one row of dh floats); GPW groups per wave.
-template <int GPW, int DHB>
-__global__ void __launch_bounds__(64) mha_fwd_kernel(const float* __restrict__ qkv, int64_t G, int H, int F, int E,
+template <int GPW, int DHB, class T>
+__global__ void __launch_bounds__(64) mha_fwd_kernel(const T* __restrict__ qkv, int64_t G, int H, int F, int E,
                                                      float scale, float p, uint64_t seed, uint64_t offset,
-                                                     const int32_t* __restrict__ offset_dev, float* __restrict__ o,
+                                                     const int32_t* __restrict__ offset_dev, T* __restrict__ o,
                                                      float* __restrict__ probs) {
   extern __shared__ float4 sm4[];
   float* sm = reinterpret_cast<float*>(sm4);
@@ -121,10 +128,10 @@ __global__ void __launch_bounds__(64) mha_fwd_kernel(const float* __restrict__ q
       for (int c = 0; c < C4; ++c)
         if (c < dh4) fma4(acc[c], pd, *reinterpret_cast<const float4*>(Vs + j * LD + 4 * c));
     }
-    float* orow = o + (row0 + i) * E + h * dh;
+    T* orow = o + (row0 + i) * E + h * dh;
 #pragma unroll
     for (int c = 0; c < C4; ++c)
-      if (c < dh4) *reinterpret_cast<float4*>(orow + 4 * c) = acc[c];
+      if (c < dh4) store4(orow + 4 * c, acc[c]);
   }
   __syncthreads();
   for (int t = li; have && t < F * F; t += LW) {       // coalesced copy of the probabilities for backward
@@ -134,12 +141,12 @@ __global__ void __launch_bounds__(64) mha_fwd_kernel(const float* __restrict__ q
 }
 
 // dV = P~^T dO;  dP = (dO V^T) m / (1-p);  dS = P (dP - rowsum(P dP)) scale;  dQ = dS K;  dK = dS^T Q
-template <int GPW, int DHB>
-__global__ void __launch_bounds__(64) mha_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ probs,
-                                                     const float* __restrict__ d_o, int64_t G, int H, int F, int E,
+template <int GPW, int DHB, class T>
+__global__ void __launch_bounds__(64) mha_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ probs,
+                                                     const T* __restrict__ d_o, int64_t G, int H, int F, int E,
                                                      float scale, float p, uint64_t seed, uint64_t offset,
                                                      const int32_t* __restrict__ offset_dev,
-                                                     float* __restrict__ d_qkv) {
+                                                     T* __restrict__ d_qkv) {
   extern __shared__ float4 sm4[];
   float* sm = reinterpret_cast<float*>(sm4);
   constexpr int LW = 64 / GPW, C4 = DHB / 4;
@@ -207,10 +214,10 @@ __global__ void __launch_bounds__(64) mha_bwd_kernel(const float* __restrict__ q
       for (int c = 0; c < C4; ++c)
         if (c < dh4) fma4(acc[c], ds, *reinterpret_cast<const float4*>(Ks + j * LD + 4 * c));
     }
-    float* dq = d_qkv + (row0 + i) * ldq + h * dh;
+    T* dq = d_qkv + (row0 + i) * ldq + h * dh;
 #pragma unroll
     for (int c = 0; c < C4; ++c)
-      if (c < dh4) *reinterpret_cast<float4*>(dq + 4 * c) = acc[c];
+      if (c < dh4) store4(dq + 4 * c, acc[c]);
   }
   __syncthreads();
   if (have && i < F) {                           // lane i now owns key / value row i: sums over the query rows
@@ -226,13 +233,13 @@ __global__ void __launch_bounds__(64) mha_bwd_kernel(const float* __restrict__ q
           fma4(av[c], pd, *reinterpret_cast<const float4*>(Ds + r * LD + 4 * c));
         }
     }
-    float* dk = d_qkv + (row0 + i) * ldq + E + h * dh;
-    float* dv = dk + E;
+    T* dk = d_qkv + (row0 + i) * ldq + E + h * dh;
+    T* dv = dk + E;
 #pragma unroll
     for (int c = 0; c < C4; ++c)
       if (c < dh4) {
-        *reinterpret_cast<float4*>(dk + 4 * c) = ak[c];
-        *reinterpret_cast<float4*>(dv + 4 * c) = av[c];
+        store4(dk + 4 * c, ak[c]);
+        store4(dv + 4 * c, av[c]);
       }
   }
 }
@@ -267,9 +274,10 @@ __device__ inline void pool_softmax_stats(const float* __restrict__ s, int F, fl
   for (int f = 0; f < F; ++f) den += expf(s[f] - mx);
 }
 
-__global__ void __launch_bounds__(256) field_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ scores,
+template <class T>
+__global__ void __launch_bounds__(256) field_pool_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scores,
                                                              int64_t B, int F, int E, int mode,
-                                                             float* __restrict__ out, float* __restrict__ w) {
+                                                             T* __restrict__ out, float* __restrict__ w) {
   const int lane = threadIdx.x % kPoolLanes;
   const int E4 = E / 4;
   for (int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kPoolLanes; b < B;
@@ -282,20 +290,21 @@ __global__ void __launch_bounds__(256) field_pool_fwd_kernel(const float* __rest
     for (int c = lane; c < E4; c += kPoolLanes) {
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int f = 0; f < F; ++f) {
-        const float4 v = *reinterpret_cast<const float4*>(x + (b * F + f) * E + 4 * c);
+        const float4 v = load4(x + (b * F + f) * E + 4 * c);
         if (mode == 2) fma4(acc, expf(scores[b * F + f] - mx) / den, v);
         else { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
       }
       if (mode == 1) acc = make_float4(acc.x / F, acc.y / F, acc.z / F, acc.w / F);
-      *reinterpret_cast<float4*>(out + b * E + 4 * c) = acc;
+      store4(out + b * E + 4 * c, acc);
     }
   }
 }
 
 // dx[b,f,:] = w_f g[b,:] (sum: w_f = 1, mean: 1/F);  attn: d_scores[b,f] = w_f (g.x_f - sum_k w_k g.x_k)
-__global__ void __launch_bounds__(256) field_pool_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
+template <class T>
+__global__ void __launch_bounds__(256) field_pool_bwd_kernel(const T* __restrict__ g, const T* __restrict__ x,
                                                              const float* __restrict__ w, int64_t B, int F, int E,
-                                                             int mode, float* __restrict__ dx,
+                                                             int mode, T* __restrict__ dx,
                                                              float* __restrict__ d_scores) {
   const int lane = threadIdx.x % kPoolLanes;
   const int E4 = E / 4;
@@ -306,11 +315,10 @@ __global__ void __launch_bounds__(256) field_pool_bwd_kernel(const float* __rest
       const float wf = mode == 2 ? w[b * F + f] : (mode == 1 ? 1.f / F : 1.f);
       float gx = 0.f;
       for (int c = lane; c < E4; c += kPoolLanes) {
-        const float4 gv = *reinterpret_cast<const float4*>(g + b * E + 4 * c);
-        if (mode == 2) gx = dot4(gv, *reinterpret_cast<const float4*>(x + (b * F + f) * E + 4 * c), gx);
-        if (mode == 1) *reinterpret_cast<float4*>(dx + (b * F + f) * E + 4 * c) = make_float4(gv.x / F, gv.y / F, gv.z / F, gv.w / F);
-        else *reinterpret_cast<float4*>(dx + (b * F + f) * E + 4 * c) =
-            make_float4(wf * gv.x, wf * gv.y, wf * gv.z, wf * gv.w);
+        const float4 gv = load4(g + b * E + 4 * c);
+        if (mode == 2) gx = dot4(gv, load4(x + (b * F + f) * E + 4 * c), gx);
+        if (mode == 1) store4(dx + (b * F + f) * E + 4 * c, make_float4(gv.x / F, gv.y / F, gv.z / F, gv.w / F));
+        else store4(dx + (b * F + f) * E + 4 * c, make_float4(wf * gv.x, wf * gv.y, wf * gv.z, wf * gv.w));
       }
       if (mode == 2) {
         gx = group_sum<kPoolLanes>(gx);
@@ -321,8 +329,7 @@ __global__ void __launch_bounds__(256) field_pool_bwd_kernel(const float* __rest
       for (int f = lane; f < F; f += kPoolLanes) {
         float gx = 0.f;
         for (int c = 0; c < E4; ++c)
-          gx = dot4(*reinterpret_cast<const float4*>(g + b * E + 4 * c),
-                    *reinterpret_cast<const float4*>(x + (b * F + f) * E + 4 * c), gx);
+          gx = dot4(load4(g + b * E + 4 * c), load4(x + (b * F + f) * E + 4 * c), gx);
         d_scores[b * F + f] = w[b * F + f] * (gx - tot);
       }
     }
@@ -339,8 +346,10 @@ static hipError_t raise_mha_lds_limit() {
   static hipError_t done = [] {
     hipError_t e = hipSuccess;
 #define MAPX_MHA_ALLOW(GPW, DHB)                                                     \
-  if (e == hipSuccess) e = allow_lds(&mha_fwd_kernel<GPW, DHB>);                     \
-  if (e == hipSuccess) e = allow_lds(&mha_bwd_kernel<GPW, DHB>);
+  if (e == hipSuccess) e = allow_lds(&mha_fwd_kernel<GPW, DHB, float>);              \
+  if (e == hipSuccess) e = allow_lds(&mha_bwd_kernel<GPW, DHB, float>);              \
+  if (e == hipSuccess) e = allow_lds(&mha_fwd_kernel<GPW, DHB, bf16_t>);             \
+  if (e == hipSuccess) e = allow_lds(&mha_bwd_kernel<GPW, DHB, bf16_t>);
     MAPX_MHA_ALLOW(1, 8) MAPX_MHA_ALLOW(1, 16) MAPX_MHA_ALLOW(1, 32) MAPX_MHA_ALLOW(1, 64)
     MAPX_MHA_ALLOW(2, 8) MAPX_MHA_ALLOW(2, 16) MAPX_MHA_ALLOW(2, 32) MAPX_MHA_ALLOW(2, 64)
 #undef MAPX_MHA_ALLOW
@@ -364,23 +373,21 @@ static int mha_check(const char* what, int64_t B, int F, int E, int H, float p) 
 
 static int dh_bucket(int dh) { return dh <= 8 ? 8 : (dh <= 16 ? 16 : (dh <= 32 ? 32 : 64)); }
 
-}  // namespace mapx
-
 #define MAPX_MHA_DISPATCH(KERNEL, GPW, GRID, LDS, ...)                                                     \
   switch (dh_bucket(E / H)) {                                                                              \
-    case 8: hipLaunchKernelGGL((KERNEL<GPW, 8>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;         \
-    case 16: hipLaunchKernelGGL((KERNEL<GPW, 16>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;       \
-    case 32: hipLaunchKernelGGL((KERNEL<GPW, 32>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;       \
-    default: hipLaunchKernelGGL((KERNEL<GPW, 64>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;       \
+    case 8: hipLaunchKernelGGL((KERNEL<GPW, 8, T>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;      \
+    case 16: hipLaunchKernelGGL((KERNEL<GPW, 16, T>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;    \
+    case 32: hipLaunchKernelGGL((KERNEL<GPW, 32, T>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;    \
+    default: hipLaunchKernelGGL((KERNEL<GPW, 64, T>), GRID, dim3(64), LDS, stream, __VA_ARGS__); break;    \
   }
 
-extern "C" int mapx_mha_fwd(const float* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed, uint64_t offset,
-                            const int32_t* offset_dev_opt, float* o, float* probs, hipStream_t stream) {
-  using namespace mapx;
-  if (int st = mha_check("mha_fwd", B, F, E, H, p)) return st;
+template <class T>
+static int mha_fwd_launch(const char* what, const T* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed,
+                          uint64_t offset, const int32_t* offset_dev_opt, T* o, float* probs, hipStream_t stream) {
+  if (int st = mha_check(what, B, F, E, H, p)) return st;
   if (B == 0) return MAPX_OK;
-  MAPX_REQUIRE(qkv && o && probs, "mha_fwd: null pointer");
-  MAPX_REQUIRE(((uintptr_t)qkv | (uintptr_t)o) % 16 == 0, "mha_fwd: qkv and o must be 16-byte aligned");
+  MAPX_REQUIRE(qkv && o && probs, "%s: null pointer", what);
+  MAPX_REQUIRE(((uintptr_t)qkv | (uintptr_t)o) % 16 == 0, "%s: qkv and o must be 16-byte aligned", what);
   const int64_t G = B * H;
   const float scale = 1.0f / sqrtf((float)(E / H));
   const size_t lds = mha_lds_bytes(F, E / H, false);
@@ -392,18 +399,18 @@ extern "C" int mapx_mha_fwd(const float* qkv, int64_t B, int F, int E, int H, fl
     MAPX_MHA_DISPATCH(mha_fwd_kernel, 1, dim3((unsigned)G), lds, qkv, G, H, F, E, scale, p, seed, offset, offset_dev_opt,
                       o, probs)
   }
-  return check_launch("mha_fwd");
+  return check_launch(what);
 }
 
-extern "C" int mapx_mha_bwd(const float* qkv, const float* probs, const float* d_o, int64_t B, int F, int E, int H,
-                            float p, uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt, float* d_qkv,
-                            hipStream_t stream) {
-  using namespace mapx;
-  if (int st = mha_check("mha_bwd", B, F, E, H, p)) return st;
+template <class T>
+static int mha_bwd_launch(const char* what, const T* qkv, const float* probs, const T* d_o, int64_t B, int F, int E,
+                          int H, float p, uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt, T* d_qkv,
+                          hipStream_t stream) {
+  if (int st = mha_check(what, B, F, E, H, p)) return st;
   if (B == 0) return MAPX_OK;
-  MAPX_REQUIRE(qkv && probs && d_o && d_qkv, "mha_bwd: null pointer");
+  MAPX_REQUIRE(qkv && probs && d_o && d_qkv, "%s: null pointer", what);
   MAPX_REQUIRE(((uintptr_t)qkv | (uintptr_t)d_o | (uintptr_t)d_qkv) % 16 == 0,
-               "mha_bwd: qkv, d_o and d_qkv must be 16-byte aligned");
+               "%s: qkv, d_o and d_qkv must be 16-byte aligned", what);
   const int64_t G = B * H;
   const float scale = 1.0f / sqrtf((float)(E / H));
   const size_t lds = mha_lds_bytes(F, E / H, true);
@@ -415,7 +422,68 @@ extern "C" int mapx_mha_bwd(const float* qkv, const float* probs, const float* d
     MAPX_MHA_DISPATCH(mha_bwd_kernel, 1, dim3((unsigned)G), lds, qkv, probs, d_o, G, H, F, E, scale, p, seed, offset,
                       offset_dev_opt, d_qkv)
   }
-  return check_launch("mha_bwd");
+  return check_launch(what);
+}
+#undef MAPX_MHA_DISPATCH
+
+template <class T>
+static int field_pool_fwd_launch(const char* what, const T* x, const float* scores_opt, int64_t B, int F, int E,
+                                 int mode, T* out, float* weights_opt, hipStream_t stream) {
+  MAPX_REQUIRE(B >= 0 && F >= 1 && E >= 4 && E % 4 == 0 && mode >= 0 && mode <= 2,
+               "%s: E a multiple of 4, mode 0 (sum) / 1 (mean) / 2 (softmax-weighted)", what);
+  if (B == 0) return MAPX_OK;
+  MAPX_REQUIRE(x && out && (mode != 2 || (scores_opt && weights_opt)), "%s: null pointer", what);
+  MAPX_REQUIRE(sizeof(T) == 4 || ((uintptr_t)x | (uintptr_t)out) % 8 == 0, "%s: x and out must be 8-byte aligned", what);
+  hipLaunchKernelGGL(field_pool_fwd_kernel<T>, dim3(grid_for(B * kPoolLanes, 256)), dim3(256), 0, stream, x, scores_opt,
+                     B, F, E, mode, out, weights_opt);
+  return check_launch(what);
+}
+
+template <class T>
+static int field_pool_bwd_launch(const char* what, const T* g, const T* x, const float* weights_opt, int64_t B, int F,
+                                 int E, int mode, T* dx, float* d_scores_opt, hipStream_t stream) {
+  MAPX_REQUIRE(B >= 0 && F >= 1 && E >= 4 && E % 4 == 0 && mode >= 0 && mode <= 2, "%s: bad arguments", what);
+  if (B == 0) return MAPX_OK;
+  MAPX_REQUIRE(g && dx && (mode != 2 || (x && weights_opt && d_scores_opt)), "%s: null pointer", what);
+  MAPX_REQUIRE(sizeof(T) == 4 || ((uintptr_t)g | (uintptr_t)x | (uintptr_t)dx) % 8 == 0,
+               "%s: g, x and dx must be 8-byte aligned", what);
+  hipLaunchKernelGGL(field_pool_bwd_kernel<T>, dim3(grid_for(B * kPoolLanes, 256)), dim3(256), 0, stream, g, x,
+                     weights_opt, B, F, E, mode, dx, d_scores_opt);
+  return check_launch(what);
+}
+
+static inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
+static inline bf16_t* hm(mapx_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
+
+}  // namespace mapx
+
+extern "C" int mapx_mha_fwd(const float* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed, uint64_t offset,
+                            const int32_t* offset_dev_opt, float* o, float* probs, hipStream_t stream) {
+  return mapx::mha_fwd_launch<float>("mha_fwd", qkv, B, F, E, H, p, seed, offset, offset_dev_opt, o, probs, stream);
+}
+
+extern "C" int mapx_mha_bwd(const float* qkv, const float* probs, const float* d_o, int64_t B, int F, int E, int H,
+                            float p, uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt, float* d_qkv,
+                            hipStream_t stream) {
+  return mapx::mha_bwd_launch<float>("mha_bwd", qkv, probs, d_o, B, F, E, H, p, seed, offset, offset_dev_opt, d_qkv,
+                                     stream);
+}
+
+// bf16 I/O forms: the same kernel templates on bf16 elements (qkv, d_o in; o, d_qkv out); probs stays fp32.
+extern "C" int mapx_mha_fwd_bf16(const mapx_bf16* qkv, int64_t B, int F, int E, int H, float p, uint64_t seed,
+                                 uint64_t offset, const int32_t* offset_dev_opt, mapx_bf16* o, float* probs,
+                                 hipStream_t stream) {
+  using namespace mapx;
+  return mha_fwd_launch<bf16_t>("mha_fwd_bf16", hc(qkv), B, F, E, H, p, seed, offset, offset_dev_opt, hm(o), probs,
+                                stream);
+}
+
+extern "C" int mapx_mha_bwd_bf16(const mapx_bf16* qkv, const float* probs, const mapx_bf16* d_o, int64_t B, int F, int E,
+                                 int H, float p, uint64_t seed, uint64_t offset, const int32_t* offset_dev_opt,
+                                 mapx_bf16* d_qkv, hipStream_t stream) {
+  using namespace mapx;
+  return mha_bwd_launch<bf16_t>("mha_bwd_bf16", hc(qkv), probs, hc(d_o), B, F, E, H, p, seed, offset, offset_dev_opt,
+                                hm(d_qkv), stream);
 }
 
 extern "C" int mapx_mha_dropout_mask(int64_t B, int F, int H, float p, uint64_t seed, uint64_t offset,
@@ -432,23 +500,26 @@ extern "C" int mapx_mha_dropout_mask(int64_t B, int F, int H, float p, uint64_t 
 
 extern "C" int mapx_field_pool_fwd(const float* x, const float* scores_opt, int64_t B, int F, int E, int mode,
                                    float* out, float* weights_opt, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(B >= 0 && F >= 1 && E >= 4 && E % 4 == 0 && mode >= 0 && mode <= 2,
-               "field_pool_fwd: E a multiple of 4, mode 0 (sum) / 1 (mean) / 2 (softmax-weighted)");
-  if (B == 0) return MAPX_OK;
-  MAPX_REQUIRE(x && out && (mode != 2 || (scores_opt && weights_opt)), "field_pool_fwd: null pointer");
-  hipLaunchKernelGGL(field_pool_fwd_kernel, dim3(grid_for(B * kPoolLanes, 256)), dim3(256), 0, stream, x, scores_opt, B,
-                     F, E, mode, out, weights_opt);
-  return check_launch("field_pool_fwd");
+  return mapx::field_pool_fwd_launch<float>("field_pool_fwd", x, scores_opt, B, F, E, mode, out, weights_opt, stream);
 }
 
 extern "C" int mapx_field_pool_bwd(const float* g, const float* x, const float* weights_opt, int64_t B, int F, int E,
                                    int mode, float* dx, float* d_scores_opt, hipStream_t stream) {
+  return mapx::field_pool_bwd_launch<float>("field_pool_bwd", g, x, weights_opt, B, F, E, mode, dx, d_scores_opt,
+                                            stream);
+}
+
+extern "C" int mapx_field_pool_fwd_bf16(const mapx_bf16* x, const float* scores_opt, int64_t B, int F, int E, int mode,
+                                        mapx_bf16* out, float* weights_opt, hipStream_t stream) {
   using namespace mapx;
-  MAPX_REQUIRE(B >= 0 && F >= 1 && E >= 4 && E % 4 == 0 && mode >= 0 && mode <= 2, "field_pool_bwd: bad arguments");
-  if (B == 0) return MAPX_OK;
-  MAPX_REQUIRE(g && dx && (mode != 2 || (x && weights_opt && d_scores_opt)), "field_pool_bwd: null pointer");
-  hipLaunchKernelGGL(field_pool_bwd_kernel, dim3(grid_for(B * kPoolLanes, 256)), dim3(256), 0, stream, g, x, weights_opt,
-                     B, F, E, mode, dx, d_scores_opt);
-  return check_launch("field_pool_bwd");
+  return field_pool_fwd_launch<bf16_t>("field_pool_fwd_bf16", hc(x), scores_opt, B, F, E, mode, hm(out), weights_opt,
+                                       stream);
+}
+
+extern "C" int mapx_field_pool_bwd_bf16(const mapx_bf16* g, const mapx_bf16* x, const float* weights_opt, int64_t B,
+                                        int F, int E, int mode, mapx_bf16* dx, float* d_scores_opt,
+                                        hipStream_t stream) {
+  using namespace mapx;
+  return field_pool_bwd_launch<bf16_t>("field_pool_bwd_bf16", hc(g), hc(x), weights_opt, B, F, E, mode, hm(dx),
+                                       d_scores_opt, stream);
 }

@@ -40,14 +40,8 @@ struct SegPlanView {
   const int32_t* seg_start;  // [U+1] first sorted position of each segment; [U] = n
 };
 
-// Four consecutive elements of a gradient row as fp32.  bf16 rows: bf16 compute mode, dL/dX0 leaves
+// Four consecutive elements of a gradient row as fp32: common.h load4.  bf16 rows: bf16 compute mode, dL/dX0 leaves
 // the trunk's backward GEMMs in bf16; the sums are fp32 like everything else here.
-__device__ inline float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ inline float4 load4(const __bf16* p) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-  const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
-  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
 // a + b of two gradient tensors, formed here, element by element, instead of by an elementwise launch in
 // front of the reduction.  fp32: the same fp32 additions in the same order, so the result is bit-identical.
 // bf16: the sum is rounded to bf16 first, as the elementwise bf16 addition it replaces would have done.

@@ -370,8 +370,39 @@ class _LayerNorm(Function):
         return dx.view(g.shape), (None if sw is not None else dw), (None if sb is not None else db), None
 
 
+class _AddLayerNorm(Function):
+    """bf16 compute mode: y = LN(x + s) (s None: LN(x)) on bf16 rows in one kernel.  The fp32 sum is normalised without
+    being stored, so it is not rounded; backward recomputes it from the two saved addends and returns ONE bf16 tensor
+    as the gradient of both.  dL/dw and dL/db leave the backward kernel as fp32 partial rows, summed with the step's
+    other deferred sums (ops.flush_deferred) when the optimizer owns the parameters."""
+
+    @staticmethod
+    def forward(ctx, x, s, w, b, eps):
+        shape = x.shape
+        x2 = x.contiguous().view(-1, shape[-1])
+        s2 = s.contiguous().view(-1, shape[-1]) if s is not None else None
+        y, stats = ops.add_layernorm_fwd(x2, s2, w, b, eps)
+        ctx.slots = (_grad_slot(w), _grad_slot(b))
+        ctx.has_s = s is not None
+        ctx.save_for_backward(x2, s2, w, stats)
+        return y.view(shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, s2, w, stats = ctx.saved_tensors
+        sw, sb = ctx.slots
+        g2 = g.contiguous().view(-1, x2.shape[1])
+        if not ops.is_bf16(g2):
+            g2 = ops.cast_bf16(g2)
+        dsum, dw, db = ops.add_layernorm_bwd(g2, x2, s2, w, stats, dw=sw, db=sb, defer=sw is not None and sb is not None)
+        dsum = dsum.view(g.shape)
+        return (dsum, dsum if ctx.has_s else None, (None if sw is not None else dw), (None if sb is not None else db),
+                None)
+
+
 class HipLayerNorm(nn.Module):
-    """nn.LayerNorm(E, eps): `weight`, `bias` [E] (ones / zeros), normalisation over the last dimension."""
+    """nn.LayerNorm(E, eps): `weight`, `bias` [E] (ones / zeros), normalisation over the last dimension.
+    bf16 input (the Transformer in bf16 compute mode): the bf16 kernel pair, which also takes the residual addend."""
 
     def __init__(self, width, eps):
         super().__init__()
@@ -379,7 +410,12 @@ class HipLayerNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(width))
         self.bias = nn.Parameter(torch.zeros(width))
 
-    def forward(self, x):
+    def forward(self, x, add=None):
+        """`add` (bf16 mode only): LN(x + add), the sum formed inside the kernel."""
+        if ops.is_bf16(x):
+            return _AddLayerNorm.apply(x, add, self.weight, self.bias, self.eps)
+        if add is not None:
+            raise NotImplementedError("the fused residual add + LayerNorm is the bf16 kernel pair")
         return _LayerNorm.apply(x, self.weight, self.bias, self.eps)
 
 
@@ -1183,7 +1219,9 @@ class TransformerEncoderLayer(nn.Module):
     layer_norm_eps, batch_first=True, norm_first) with torch's parameter names:
       post-norm: x = norm1(x + dropout1(SA(x)));  x = norm2(x + dropout2(linear2(dropout(act(linear1(x))))))
       pre-norm:  x = x + dropout1(SA(norm1(x)));  x = x + dropout2(FF(norm2(x)))
-    relu is fused into linear1's GEMM epilogue, gelu (erf form) is one elementwise pass behind it."""
+    relu is fused into linear1's GEMM epilogue, gelu (erf form) is one elementwise pass behind it.
+    bf16 input (compute_dtype=bf16): every tensor between the kernels is bf16; post-norm layers form both residual sums
+    inside the add + LayerNorm kernels (_AddLayerNorm), pre-norm layers keep their elementwise adds."""
 
     def __init__(self, d_model, nhead, dim_feedforward, dropout=0.0, activation="relu", layer_norm_eps=1e-5,
                  norm_first=False):
@@ -1218,6 +1256,11 @@ class TransformerEncoderLayer(nn.Module):
         if self.norm_first:
             x = x + self._sa(self.norm1(x), B, F)
             x = x + self._ff(self.norm2(x))
+        elif ops.is_bf16(x):
+            # bf16 compute mode: the residual add happens inside the LayerNorm kernels (the sum is never stored, so it
+            # is not rounded; one backward output is the gradient of both addends)
+            x = self.norm1(x, add=self._sa(x, B, F))
+            x = self.norm2(x, add=self._ff(x))
         else:
             x = self.norm1(x + self._sa(x, B, F))
             x = self.norm2(x + self._ff(x))

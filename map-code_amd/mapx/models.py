@@ -1,7 +1,7 @@
 """BaseModel + DCNV2 (host mirror of reference code/models.py:21-127, 282-322): same factory,
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
 is a gfx950 kernel.  The other backbones the factory builds: DNN, DeepFM, xDeepFM, AutoInt, trans, fgcnn
-(from_config still refuses fignn; build_backbone and the FiGNN class build it)."""
+(from_config still refuses fignn, and trans with compute_dtype=bf16; build_backbone builds both)."""
 import logging
 
 import torch
@@ -559,7 +559,12 @@ class Transformer(BaseModel):
     Linear(E,E), ReLU, Linear(E,1)) and adds the LR term (use_lr: its weight is the secondary parameter of the
     embedding's RowTable, as in DeepFM) and an MLP tower over the flattened embeddings (num_dnn_layers > 0: `mlp` +
     `mlp_out`).  The attention core is csrc/mha.hip: F <= 64 fields, head size hidden_size / num_attn_heads a
-    multiple of 4 and <= 64; LayerNorm over hidden_size <= 64."""
+    multiple of 4 and <= 64; LayerNorm over hidden_size <= 64.
+    compute_dtype=bf16 (through build_backbone): the gathered rows, qkv, the attention output, every projection's and
+    LayerNorm's output, the saved gelu pre-activation and the pooled vectors are bf16 — the bf16 I/O forms of
+    csrc/mha.hip, the residual add + LayerNorm pair and the bf16 gelu / dropout of csrc/extras.hip, bf16 GEMMs on the
+    weights' shadows; the attention probabilities, LayerNorm statistics, pooling weights, the scores of
+    field_reduction_attn, the LR term and every logit stay fp32.  hidden_dropout_rate > 0 works as in fp32 mode."""
     used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
                    "num_attn_heads", "intermediate_size", "output_reduction",
                    "norm_first", "layer_norm_eps", "use_lr",
@@ -591,16 +596,18 @@ class Transformer(BaseModel):
             return
         red = config.output_reduction
         if red == "attn,fc":
-            self.field_reduction_attn = nn.ModuleDict({"0": HipLinear(Ee, Ee, relu=True), "2": HipLinear(Ee, 1)})
-        self.trans_out = HipLinear(config.num_fields * Ee if red == "fc" else Ee, 1)
+            self.field_reduction_attn = nn.ModuleDict({"0": HipLinear(Ee, Ee, relu=True),
+                                                       "2": HipLinear(Ee, 1, out_fp32=True)})
+        self.trans_out = HipLinear(config.num_fields * Ee if red == "fc" else Ee, 1, out_fp32=True)   # (bf16 mode: fp32 logits)
         self.lr_layer = LR(config) if config.use_lr else None
         if self.lr_layer is not None:          # one row table for both [V, *] parameters read with input_ids
             self.embed.table = RowTable("embed.embedding", self.embed.embedding.weight, self.lr_layer.embed_w.weight)
         if config.num_dnn_layers > 0:
+            _refuse_bf16_mlp_options(config, "dnn_act", "dnn_drop")
             self.mlp = MLPBlock(input_dim=config.num_fields * Ee, hidden_size=config.dnn_size,
                                 num_hidden_layers=config.num_dnn_layers, hidden_dropout_rate=config.dnn_drop,
                                 hidden_act=config.dnn_act)
-            self.mlp_out = HipLinear(config.dnn_size, 1)
+            self.mlp_out = HipLinear(config.dnn_size, 1, out_fp32=True)
         else:
             self.mlp = None
 
@@ -797,10 +804,14 @@ class FiGNN(BaseModel):
 
 
 def build_backbone(config: Config):
-    """Every model name the reference's factory reaches: FiGNN here, the other seven through BaseModel.from_config
-    (which still refuses fignn, as two tests pin; making it delegate is a one-line follow-up)."""
-    if str(config.model_name).lower() == "fignn":
-        from .layers import compute_dtype_of
+    """Every model name the reference's factory reaches: FiGNN and the Transformer in compute_dtype=bf16 here, the
+    rest through BaseModel.from_config (which still refuses fignn, and trans with bf16, as existing tests pin; making it
+    delegate is a one-line follow-up)."""
+    from .layers import compute_dtype_of
+    name = str(config.model_name).lower()
+    if name == "trans" and compute_dtype_of(config) != torch.float32:
+        return Transformer(config)
+    if name == "fignn":
         if compute_dtype_of(config) != torch.float32:
             raise NotImplementedError("compute_dtype=bf16 is built for DCNv2, DNN, DeepFM and AutoInt, "
                                       f"not {config.model_name}")

@@ -132,6 +132,16 @@ SIGNATURES = {
     "mapx_take_rows_i64": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _p, _p, _p]),
     "mapx_act_fwd": (_i, [_i, _p, _i64, _i, _p, _i64, _p]),
     "mapx_act_bwd": (_i, [_i, _p, _i64, _p, _i64, _i, _p, _p]),
+    "mapx_mha_fwd_bf16": (_i, [_p, _i64, _i, _i, _i, _f, _u64, _u64, _p, _p, _p, _p]),
+    "mapx_mha_bwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _i, _f, _u64, _u64, _p, _p, _p]),
+    "mapx_field_pool_fwd_bf16": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p]),
+    "mapx_field_pool_bwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p]),
+    "mapx_dropout_bf16": (_i, [_p, _i64, _f, _u64, _u64, _p, _p, _p]),
+    "mapx_act_fwd_bf16": (_i, [_i, _p, _i64, _i, _p, _i64, _p]),
+    "mapx_act_bwd_bf16": (_i, [_i, _p, _i64, _p, _i64, _i, _p, _p]),
+    "mapx_add_layernorm_fwd_bf16": (_i, [_p, _p, _i64, _i, _p, _p, _f, _p, _p, _p]),
+    "mapx_add_layernorm_bwd_groups": (_i, [_i64, _i]),
+    "mapx_add_layernorm_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _p, _p]),
     "mapx_vocab_table_init": (_i, [_p, _p, _p, _i64, _p]),
     "mapx_vocab_count": (_i, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p]),
     "mapx_vocab_compact": (_i, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),

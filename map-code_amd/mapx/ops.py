@@ -682,23 +682,35 @@ def attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev=None, de
 
 
 # --------------------------------------------------------------------------- Transformer attention core
+def _one_dtype(what, names, *ts):
+    """True: the bf16 I/O forms (every tensor bf16); False: the fp32 entries.  Mixed element types are an error, as in
+    _attn_half."""
+    half = is_bf16(ts[0])
+    for t in ts:
+        if t.dtype != (BF16 if half else torch.float32):
+            raise TypeError(f"{what}: {names} have one element type, fp32 or bf16 (got {[str(x.dtype) for x in ts]})")
+    return half
+
+
 def mha_fwd(qkv, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
     """qkv [B*F, 3E] (the in-projection's output, read in place) -> (o [B*F, E] heads concatenated,
     probs [B*H, F, F] undropped).  p > 0: O = (P * m / (1-p)) V with m = mha_dropout_mask(B, F, H, p, seed, offset)."""
     require_gpu(qkv)
-    o = torch.empty(B * F, E, dtype=torch.float32, device=qkv.device)
+    fn = lib.mapx_mha_fwd_bf16 if _one_dtype("mha_fwd", "qkv", qkv) else lib.mapx_mha_fwd
+    o = torch.empty(B * F, E, dtype=qkv.dtype, device=qkv.device)
     probs = torch.empty(B * H, F, F, dtype=torch.float32, device=qkv.device)
-    check(lib.mapx_mha_fwd(ptr(qkv), B, F, E, H, float(p), int(seed), int(offset), ptr(offset_dev), ptr(o), ptr(probs),
-                           stream()))
+    check(fn(ptr(qkv), B, F, E, H, float(p), int(seed), int(offset), ptr(offset_dev), ptr(o), ptr(probs), stream()))
     return o, probs
 
 
 def mha_bwd(qkv, probs, d_o, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
     """-> d_qkv [B*F, 3E] (dQ, dK, dV in qkv's layout); the dropout mask is regenerated from (seed, offset)."""
     require_gpu(qkv, probs, d_o)
+    d_o = d_o.contiguous()
+    fn = lib.mapx_mha_bwd_bf16 if _one_dtype("mha_bwd", "qkv and d_o", qkv, d_o) else lib.mapx_mha_bwd
     d_qkv = torch.empty_like(qkv)
-    check(lib.mapx_mha_bwd(ptr(qkv), ptr(probs), ptr(d_o.contiguous()), B, F, E, H, float(p), int(seed), int(offset),
-                           ptr(offset_dev), ptr(d_qkv), stream()))
+    check(fn(ptr(qkv), ptr(_f32(probs, "mha_bwd: probs")), ptr(d_o), B, F, E, H, float(p), int(seed), int(offset),
+             ptr(offset_dev), ptr(d_qkv), stream()))
     return d_qkv
 
 
@@ -719,10 +731,12 @@ def field_pool_fwd(x3, mode, scores=None):
     x3 = x3.contiguous()
     B, F, E = x3.shape
     m = POOL_MODES[mode]
-    out = torch.empty(B, E, dtype=torch.float32, device=x3.device)
+    fn = lib.mapx_field_pool_fwd_bf16 if _one_dtype("field_pool_fwd", "x", x3) else lib.mapx_field_pool_fwd
+    if scores is not None:
+        scores = _f32(scores, "field_pool_fwd: scores").contiguous()
+    out = torch.empty(B, E, dtype=x3.dtype, device=x3.device)
     w = torch.empty(B, F, dtype=torch.float32, device=x3.device) if m == 2 else None
-    check(lib.mapx_field_pool_fwd(ptr(x3), ptr(scores.contiguous() if scores is not None else None), B, F, E, m,
-                                  ptr(out), ptr(w), stream()))
+    check(fn(ptr(x3), ptr(scores), B, F, E, m, ptr(out), ptr(w), stream()))
     return out, w
 
 
@@ -731,10 +745,10 @@ def field_pool_bwd(g, x3, mode, weights=None):
     require_gpu(g, x3)
     B, F, E = x3.shape
     m = POOL_MODES[mode]
-    dx = torch.empty(B, F, E, dtype=torch.float32, device=g.device)
+    fn = lib.mapx_field_pool_bwd_bf16 if _one_dtype("field_pool_bwd", "g and x", g, x3) else lib.mapx_field_pool_bwd
+    dx = torch.empty(B, F, E, dtype=x3.dtype, device=g.device)
     ds = torch.empty(B, F, dtype=torch.float32, device=g.device) if m == 2 else None
-    check(lib.mapx_field_pool_bwd(ptr(g.contiguous()), ptr(x3.contiguous()), ptr(weights), B, F, E, m, ptr(dx), ptr(ds),
-                                  stream()))
+    check(fn(ptr(g.contiguous()), ptr(x3.contiguous()), ptr(weights), B, F, E, m, ptr(dx), ptr(ds), stream()))
     return dx, ds
 
 
@@ -2020,17 +2034,19 @@ ACT_KINDS = {"tanh": 1, "sigmoid": 2, "none": 3, "elu": 4, "leu": 5, "gelu": 6, 
 
 
 def act_fwd(kind, z, out=None):
-    """y = f(z) for the reference's activations other than relu (layers.py:55-80); z [M,N] contiguous fp32,
-    `out`: optional destination with unit column stride (a column slice of a wider buffer)."""
+    """y = f(z) for the reference's activations other than relu (layers.py:55-80); z [M,N] contiguous fp32 or bf16
+    (f in fp32, y of z's type), `out`: optional destination with unit column stride (a column slice of a wider
+    buffer)."""
     require_gpu(z)
-    if z.dtype != torch.float32 or z.dim() != 2 or not z.is_contiguous():
-        raise TypeError("act_fwd: z must be a contiguous fp32 matrix")
+    if z.dtype not in (torch.float32, BF16) or z.dim() != 2 or not z.is_contiguous():
+        raise TypeError("act_fwd: z must be a contiguous fp32 or bf16 matrix")
     M, Nn = z.shape
     if out is None:
         out = torch.empty_like(z)
-    if out.shape != z.shape or out.stride(1) != 1:
-        raise ValueError("act_fwd: `out` must have z's shape and unit column stride")
-    check(lib.mapx_act_fwd(ACT_KINDS[kind], ptr(z), M, Nn, out.data_ptr(), out.stride(0), stream()))
+    if out.shape != z.shape or out.stride(1) != 1 or out.dtype != z.dtype:
+        raise ValueError("act_fwd: `out` must have z's shape and element type and unit column stride")
+    fn = lib.mapx_act_fwd_bf16 if is_bf16(z) else lib.mapx_act_fwd
+    check(fn(ACT_KINDS[kind], ptr(z), M, Nn, out.data_ptr(), out.stride(0), stream()))
     return out
 
 
@@ -2040,23 +2056,26 @@ def act_bwd(kind, dy, z):
     if dy.stride(1) != 1:
         dy = dy.contiguous()
     M, Nn = z.shape
+    fn = lib.mapx_act_bwd_bf16 if _one_dtype("act_bwd", "dy and z", dy, z) else lib.mapx_act_bwd
     dz = torch.empty_like(z)
-    check(lib.mapx_act_bwd(ACT_KINDS[kind], dy.data_ptr(), dy.stride(0), ptr(z), M, Nn, ptr(dz), stream()))
+    check(fn(ACT_KINDS[kind], dy.data_ptr(), dy.stride(0), ptr(z), M, Nn, ptr(dz), stream()))
     return dz
 
 
 def dropout(x, p, seed, offset, offset_dev=None, out=None):
     """out = keep ? x / (1 - p) : 0, keep mask = Philox(seed, offset + *offset_dev) (never stored: the
-    backward pass calls this again on the gradient with the same seed / offset).  fp32."""
+    backward pass calls this again on the gradient with the same seed / offset).  fp32, or bf16 (x / (1 - p) in
+    fp32, rounded once; the same mask)."""
     require_gpu(x)
-    if x.dtype != torch.float32:
-        raise NotImplementedError("dropout is built for the fp32 path")
+    if x.dtype not in (torch.float32, BF16):
+        raise NotImplementedError("dropout is built for fp32 and bf16 tensors")
     x = x.contiguous()
     if out is None:
         out = torch.empty_like(x)
-    if not out.is_contiguous():
-        raise ValueError("dropout writes a contiguous tensor")
-    check(lib.mapx_dropout(ptr(x), x.numel(), float(p), int(seed), int(offset), ptr(offset_dev), ptr(out), stream()))
+    if not out.is_contiguous() or out.dtype != x.dtype:
+        raise ValueError("dropout writes a contiguous tensor of x's element type")
+    fn = lib.mapx_dropout_bf16 if is_bf16(x) else lib.mapx_dropout
+    check(fn(ptr(x), x.numel(), float(p), int(seed), int(offset), ptr(offset_dev), ptr(out), stream()))
     return out
 
 
@@ -2079,6 +2098,52 @@ def layernorm_bwd(dy2, x2, w, stats):
     dx, dyx = torch.empty_like(x2), torch.empty_like(x2)
     check(lib.mapx_layernorm_bwd(ptr(dy2), ptr(x2), ptr(w), ptr(stats), R, E, ptr(dx), ptr(dyx), stream()))
     return dx, dyx
+
+
+def add_layernorm_fwd(x2, s2, w, b, eps):
+    """bf16 x2 [R,E], s2 [R,E] or None -> (y = LN(x2 + s2) bf16, stats [R,2] fp32 = {mean, rstd}).  The sum is formed
+    in fp32 inside the kernel and normalised unrounded (the Transformer's residual add + LayerNorm in bf16 mode)."""
+    require_gpu(x2, s2, w, b)
+    ts = (x2,) if s2 is None else (x2, s2)
+    if not _one_dtype("add_layernorm_fwd", "x and s", *ts) or any(not t.is_contiguous() or t.shape != x2.shape
+                                                                  for t in ts):
+        raise TypeError("add_layernorm_fwd: x (and s) are contiguous bf16 matrices of one shape")
+    R, E = x2.shape
+    y = torch.empty_like(x2)
+    stats = torch.empty(R, 2, dtype=torch.float32, device=x2.device)
+    check(lib.mapx_add_layernorm_fwd_bf16(ptr(x2), ptr(s2), R, E, ptr(_f32(w, "add_layernorm_fwd: w")),
+                                          ptr(_f32(b, "add_layernorm_fwd: b")), float(eps), ptr(y), ptr(stats), stream()))
+    return y, stats
+
+
+def add_layernorm_bwd(dy2, x2, s2, w, stats, dw=None, db=None, defer=False):
+    """-> (dsum [R,E] bf16: the gradient of BOTH addends, dL/dw [E], dL/db [E] fp32).  The kernel leaves one fp32
+    partial row (dw | db) per workgroup; they are summed at once, or (defer, with `dw` and `db` given) by
+    flush_deferred() with the step's other partial sums."""
+    require_gpu(dy2, x2, s2, w, stats)
+    dy2 = dy2.contiguous()
+    ts = (dy2, x2) if s2 is None else (dy2, x2, s2)
+    if not _one_dtype("add_layernorm_bwd", "dy, x and s", *ts) or any(t.shape != x2.shape for t in ts):
+        raise TypeError("add_layernorm_bwd: dy, x (and s) are bf16 matrices of one shape")
+    R, E = x2.shape
+    dsum = torch.empty_like(x2)
+    dw = dw if dw is not None else torch.empty(E, dtype=torch.float32, device=x2.device)
+    db = db if db is not None else torch.empty(E, dtype=torch.float32, device=x2.device)
+    if R == 0:
+        dw.zero_()
+        db.zero_()
+        return dsum, dw, db
+    groups = lib.mapx_add_layernorm_bwd_groups(R, E)
+    part = torch.empty(groups, 2 * E, dtype=torch.float32, device=x2.device)
+    check(lib.mapx_add_layernorm_bwd_bf16(ptr(dy2), ptr(x2), ptr(s2), ptr(_f32(w, "add_layernorm_bwd: w")),
+                                          ptr(_f32(stats, "add_layernorm_bwd: stats")), R, E, ptr(dsum), ptr(part),
+                                          stream()))
+    for dst, col0 in ((dw, 0), (db, E)):
+        if defer:
+            defer_sum(dst, part[:, col0:], 2 * E, groups, E)
+        else:
+            _sum_now(dst, part[:, col0:], 2 * E, groups, E)
+    return dsum, dw, db
 
 
 # --------------------------------------------------------------------------- heads / masks

@@ -1,9 +1,10 @@
 """Step time of the Transformer backbone (model_name=trans) on one GPU: Avazu-shaped synthetic data, batch 4096,
 E = hidden = 16, 3 layers, intermediate 128, 1 and 2 heads; MFP, RFD and finetune (CTR, output_reduction attn,fc)
 steps through Trainer.run_step (the captured step replayed after the first few).  One JSON line per arm.
+--dtype fp32 bf16 runs every step arm in both compute modes, alternated arm by arm in the one process.
 --torch-trunk adds, per head count, forward + backward of the trunk alone: the mapx encoder against
 torch.nn.TransformerEncoder (fp32, same weights, same GPU).
-    python tools/trans_bench.py [--heads 1 2] [--pt MFP RFD CTR] [--steps 100] [--torch-trunk]"""
+    python tools/trans_bench.py [--heads 1 2] [--pt MFP RFD CTR] [--dtype fp32 bf16] [--steps 100] [--torch-trunk]"""
 import argparse
 import json
 import os
@@ -19,7 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "map-code_amd"))
 F_AVAZU, V_AVAZU = 23, 9449445
 
 
-def make_config(a, heads, pt, feat_count):
+def make_config(a, heads, pt, feat_count, dtype="fp32"):
     from mapx.arguments import Config
     return Config(model_name="trans", data_dir=None, input_size=a.vocab, num_fields=F_AVAZU, embed_size=16,
                   embed_dropout_rate=0.0, embed_norm=False, hidden_size=16, num_hidden_layers=3, hidden_act="relu",
@@ -27,17 +28,17 @@ def make_config(a, heads, pt, feat_count):
                   layer_norm_eps=1e-12, output_reduction="attn,fc", use_lr=False, dnn_size=1000, num_dnn_layers=0,
                   dnn_act="relu", dnn_drop=0.0, num_cross_layers=0, pt_neg_num=25, proj_size=32, pretrain=pt != "CTR",
                   pt_type="MFP" if pt == "CTR" else pt, RFD_replace="Unigram", feat_count=feat_count, seed=42, rank=0,
-                  compute_dtype="fp32")
+                  compute_dtype=dtype)
 
 
-def step_arm(a, heads, pt, ids, labels, feat_count, device):
+def step_arm(a, heads, pt, dtype, ids, labels, feat_count, device):
     from mapx.arguments import TrainingArguments
     from mapx.dataset import OurDataset
-    from mapx.models import BaseModel
+    from mapx.models import build_backbone
     from mapx.trainer import Trainer
     torch.manual_seed(42)
-    cfg = make_config(a, heads, pt, feat_count)
-    model = BaseModel.from_config(cfg)
+    cfg = make_config(a, heads, pt, feat_count, dtype)
+    model = build_backbone(cfg)
     targs = TrainingArguments(output_dir="/tmp/mapx_trans_bench", per_gpu_train_batch_size=a.batch,
                               per_gpu_eval_batch_size=a.batch, learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2,
                               num_train_epochs=1000, pretrain=pt != "CTR", pt_type="MFP" if pt == "CTR" else pt,
@@ -66,7 +67,7 @@ def step_arm(a, heads, pt, ids, labels, feat_count, device):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     live = [g for g in tr._graphs.values() if not isinstance(g, int)]
-    return {"arm": f"trans {pt}", "heads": heads, "batch": a.batch, "ms_per_step": 1e3 * dt / a.steps,
+    return {"arm": f"trans {pt}", "dtype": dtype, "heads": heads, "batch": a.batch, "ms_per_step": 1e3 * dt / a.steps,
             "samples_per_s": a.batch * a.steps / dt, "graphed": bool(live), "loss": float(out[0].detach())}
 
 
@@ -111,6 +112,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--pt", nargs="+", default=["MFP", "RFD", "CTR"], choices=["MFP", "RFD", "CTR"])
+    ap.add_argument("--dtype", nargs="+", default=["fp32"], choices=["fp32", "bf16"], help="compute_dtype of the step arms")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--vocab", type=int, default=V_AVAZU)
@@ -128,7 +130,8 @@ def main():
     for heads in a.heads:
         if not a.no_steps:
             for pt in a.pt:
-                print(json.dumps(step_arm(a, heads, pt, ids, labels, feat_count, device)), flush=True)
+                for dtype in a.dtype:
+                    print(json.dumps(step_arm(a, heads, pt, dtype, ids, labels, feat_count, device)), flush=True)
         if a.torch_trunk:
             print(json.dumps(trunk_arm(a, heads, feat_count, device)), flush=True)
 
