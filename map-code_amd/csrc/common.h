@@ -1,9 +1,12 @@
-// Shared helpers for the mapx gfx950 kernels: status codes, launch checks, Philox RNG.
+// Shared helpers for the mapx gfx950 kernels: status codes, launch checks, the dynamic-LDS opt-in, Philox RNG and the
+// dropout draw, lane-group reductions, float4 helpers, bf16 I/O.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include "../../include/mapx_hip.h"
 
 #define MAPX_OK 0
 #define MAPX_EINVAL (-1)
@@ -39,6 +42,17 @@ inline int check_launch(const char* what) {
       return MAPX_EHIP;                                                  \
     }                                                                    \
   } while (0)
+
+// Lets `kernels` ask for up to `bytes` of dynamic LDS (the default limit is 64 KB, the CU has 160 KB); the first
+// error.  A call site keeps the result in a function-local static, so the attribute is set once.
+template <class... K>
+inline hipError_t allow_dynamic_lds(size_t bytes, K*... kernels) {
+  for (const void* fn : {reinterpret_cast<const void*>(kernels)...}) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 constexpr int kWave = 64;
 
@@ -85,13 +99,51 @@ __device__ inline uint32_t bounded(uint32_t r, uint32_t n) {
 // u32 -> uniform float in [0, 1) with 24 random bits.
 __device__ inline float unit_float(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 
-// Wave64 butterfly sum over `width` lanes (width a power of two <= 64).
-template <int WIDTH>
-__device__ inline float group_sum(float v) {
+// THE dropout draw: an inverted-dropout mask is never stored, every user regenerates it from
+// Philox(seed, counter, drop_offset(offset, offset_dev)), one draw per four consecutive elements of its own counter
+// layout (dropout_kernel: flat i / 4; attn.hip, mha.hip: row * ceil(width / 4) + c).  Element e of the draw is kept
+// iff its word >= p * 2^32, so P(keep) = 1 - p.
+__device__ inline uint32_t drop_threshold(float p) { return (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f); }
+
+// The device word is what a replayed hipGraph bumps between steps.
+__device__ inline uint64_t drop_offset(uint64_t offset, const int32_t* offset_dev) {
+  return offset + (offset_dev ? (uint64_t)(uint32_t)*offset_dev : 0ull);
+}
+
+// Bit e set = element e of the draw is kept.
+__device__ inline uint32_t keep_bits4(const Philox4& r, uint32_t thr) {
+  return (uint32_t)(r.x >= thr) | ((uint32_t)(r.y >= thr) << 1) | ((uint32_t)(r.z >= thr) << 2) |
+         ((uint32_t)(r.w >= thr) << 3);
+}
+
+// Wave64 butterfly sum / max over `width` lanes (width a power of two <= 64).
+template <int WIDTH, class V = float>
+__device__ inline V group_sum(V v) {
 #pragma unroll
   for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
   return v;
 }
+template <int WIDTH>
+__device__ inline float group_max(float v) {
+#pragma unroll
+  for (int o = WIDTH / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+
+// acc += s * v and s + a . b, one fmaf per term in x, y, z, w order.
+__device__ inline void fma4(float4& acc, float s, const float4& v) {
+  acc.x = fmaf(s, v.x, acc.x);
+  acc.y = fmaf(s, v.y, acc.y);
+  acc.z = fmaf(s, v.z, acc.z);
+  acc.w = fmaf(s, v.w, acc.w);
+}
+__device__ inline float dot4(const float4& a, const float4& b, float s) {
+  s = fmaf(a.x, b.x, s);
+  s = fmaf(a.y, b.y, s);
+  s = fmaf(a.z, b.z, s);
+  return fmaf(a.w, b.w, s);
+}
+// (fignn.hip keeps gn_dot4, hand-written v_fmac_f32, for dot products that run side by side: see its comment.)
 
 // ---------------------------------------------------------------- bf16 I/O (bf16 compute mode)
 // Kernels templated on an element type T = float | bf16_t differ only here: a load widens to fp32 (exact), all
@@ -99,6 +151,10 @@ __device__ inline float group_sum(float v) {
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+// The C ABI's mapx_bf16 (a uint16_t) as the device element type.
+inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
+inline bf16_t* hm(mapx_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
 
 // Four consecutive elements (16-byte aligned floats / 8-byte aligned bf16) as fp32, and back.
 __device__ inline float4 load4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }

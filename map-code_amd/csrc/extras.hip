@@ -6,8 +6,8 @@
 
 namespace mapx {
 
-// Inverted dropout, mask never stored: element i keeps its value iff Philox(seed, offset (+ *offset_dev),
-// i / 4)[i % 4] >= p * 2^32, scaled by 1 / (1 - p).  Forward and backward call the same kernel with the
+// Inverted dropout, mask never stored: element i keeps its value iff bit i % 4 of the dropout draw (common.h) at
+// counter i / 4 is set, scaled by 1 / (1 - p).  Forward and backward call the same kernel with the
 // same (seed, offset): the mask is regenerated, not saved (0 bytes of activation memory, graph-replay
 // safe through the device-side offset).
 // T: float, or bf16_t (bf16 compute mode: x * scale in fp32, rounded once; the mask does not depend on T).  `vec`
@@ -17,34 +17,36 @@ __global__ void __launch_bounds__(256) dropout_kernel(const T* __restrict__ x, i
                                                       uint64_t seed, uint64_t offset,
                                                       const int32_t* __restrict__ offset_dev,
                                                       T* __restrict__ out, int vec) {
-  const uint64_t off = offset + (offset_dev ? (uint64_t)(uint32_t)*offset_dev : 0ull);
-  const uint32_t thr = (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f);
+  const uint64_t off = drop_offset(offset, offset_dev);
+  const uint32_t thr = drop_threshold(p);
   const int64_t n4 = (n + 3) / 4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const Philox4 r = philox4x32_10(seed, (uint64_t)i, off);
+    const uint32_t keep = keep_bits4(philox4x32_10(seed, (uint64_t)i, off), thr);
     if constexpr (sizeof(T) == 2) {
       if (vec && 4 * i + 4 <= n) {
         const float4 v = load4(x + 4 * i);
-        store4(out + 4 * i, make_float4(r.x >= thr ? v.x * scale : 0.f, r.y >= thr ? v.y * scale : 0.f,
-                                        r.z >= thr ? v.z * scale : 0.f, r.w >= thr ? v.w * scale : 0.f));
+        store4(out + 4 * i, make_float4((keep & 1u) ? v.x * scale : 0.f, (keep & 2u) ? v.y * scale : 0.f,
+                                        (keep & 4u) ? v.z * scale : 0.f, (keep & 8u) ? v.w * scale : 0.f));
         continue;
       }
     }
-    const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int64_t j = 4 * i + e;
-      if (j < n) out[j] = (T)(rr[e] >= thr ? (float)x[j] * scale : 0.f);
+      if (j < n) out[j] = (T)(((keep >> e) & 1u) ? (float)x[j] * scale : 0.f);
     }
   }
 }
 
 // LayerNorm over the last dimension E (<= 64, E % 4 == 0) of [R, E]: one lane group of E/4 lanes per row.
-//   y = (x - mean) * rstd * w + b,  rstd = 1 / sqrt(var + eps)  (biased variance, as nn.LayerNorm)
-template <int LG>
-__global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restrict__ x, int64_t R, int E,
-                                                            const float* __restrict__ w, const float* __restrict__ b,
-                                                            float eps, float* __restrict__ y,
+//   y = (v - mean) * rstd * w + b,  rstd = 1 / sqrt(var + eps)  (biased variance, as nn.LayerNorm),  v = x + s
+// T = float: the embeddings' LayerNorm (s = null).  T = bf16_t: residual add + LayerNorm of the Transformer's bf16
+// trunk (s = null: LN(x)); the sum is formed in fp32 from the two bf16 addends and normalised as it stands — it is
+// never stored, so it is never rounded; y is rounded once.
+template <int LG, class T>
+__global__ void __launch_bounds__(256) layernorm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ s, int64_t R,
+                                                            int E, const float* __restrict__ w,
+                                                            const float* __restrict__ b, float eps, T* __restrict__ y,
                                                             float* __restrict__ stats /* [R,2] mean, rstd */) {
   const int lig = threadIdx.x % LG;
   const bool live = lig * 4 < E;
@@ -52,14 +54,18 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
   const float4 bv = live ? *reinterpret_cast<const float4*>(b + 4 * lig) : make_float4(0, 0, 0, 0);
   for (int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG; row < R;
        row += ((int64_t)gridDim.x * blockDim.x) / LG) {
-    const float4 v = live ? *reinterpret_cast<const float4*>(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
+    float4 v = live ? load4(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
+    if (s && live) {
+      const float4 a = load4(s + row * E + 4 * lig);
+      v = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
+    }
     const float mean = group_sum<LG>(v.x + v.y + v.z + v.w) / E;
     const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
     const float var = group_sum<LG>(live ? d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w : 0.f) / E;
     const float rstd = rsqrtf(var + eps);
     if (live)
-      *reinterpret_cast<float4*>(y + row * E + 4 * lig) =
-          make_float4(d.x * rstd * wv.x + bv.x, d.y * rstd * wv.y + bv.y, d.z * rstd * wv.z + bv.z, d.w * rstd * wv.w + bv.w);
+      store4(y + row * E + 4 * lig, make_float4(d.x * rstd * wv.x + bv.x, d.y * rstd * wv.y + bv.y,
+                                                d.z * rstd * wv.z + bv.z, d.w * rstd * wv.w + bv.w));
     if (lig == 0) {
       stats[2 * row] = mean;
       stats[2 * row + 1] = rstd;
@@ -67,7 +73,31 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* __restr
   }
 }
 
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w;  also writes dy * xhat (its column sum is dw)
+// A lane's four columns of one row in backward: v = x + s (s = null: x) and dy in, then
+//   xhat = (v - mean) * rstd,  g = dy * w,  dv = rstd * (g - mean(g) - xhat * mean(g * xhat))  stored to dx.
+// Every lane of a wave calls it (the group_sum shuffles need all 64); `have` = this lane has a live column of a row
+// < R.  Returns dy and xhat, from which the callers form dw and db in their own ways.
+template <int LG, class T>
+__device__ inline void layernorm_bwd_row(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ s,
+                                         const float4& wv, float mean, float rstd, int64_t row, int E, int lig,
+                                         bool have, T* __restrict__ dx, float4& gy, float4& xh) {
+  float4 v = have ? load4(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
+  if (s && have) {
+    const float4 a = load4(s + row * E + 4 * lig);
+    v = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
+  }
+  gy = have ? load4(dy + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
+  xh = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
+  const float4 g = make_float4(gy.x * wv.x, gy.y * wv.y, gy.z * wv.z, gy.w * wv.w);
+  const float mg = group_sum<LG>(have ? g.x + g.y + g.z + g.w : 0.f) / E;
+  const float mgx = group_sum<LG>(have ? g.x * xh.x + g.y * xh.y + g.z * xh.z + g.w * xh.w : 0.f) / E;
+  if (have)
+    store4(dx + row * E + 4 * lig,
+           make_float4(rstd * (g.x - mg - xh.x * mgx), rstd * (g.y - mg - xh.y * mgx), rstd * (g.z - mg - xh.z * mgx),
+                       rstd * (g.w - mg - xh.w * mgx)));
+}
+
+// fp32 backward: dx as above; also writes dy * xhat (its column sum is dw)
 template <int LG>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ w, const float* __restrict__ stats,
@@ -78,19 +108,9 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* __restr
   const float4 wv = live ? *reinterpret_cast<const float4*>(w + 4 * lig) : make_float4(0, 0, 0, 0);
   for (int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG; row < R;
        row += ((int64_t)gridDim.x * blockDim.x) / LG) {
-    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    const float4 v = live ? *reinterpret_cast<const float4*>(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
-    const float4 gy = live ? *reinterpret_cast<const float4*>(dy + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
-    const float4 xh = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
-    const float4 g = make_float4(gy.x * wv.x, gy.y * wv.y, gy.z * wv.z, gy.w * wv.w);
-    const float mg = group_sum<LG>(live ? g.x + g.y + g.z + g.w : 0.f) / E;
-    const float mgx = group_sum<LG>(live ? g.x * xh.x + g.y * xh.y + g.z * xh.z + g.w * xh.w : 0.f) / E;
-    if (live) {
-      *reinterpret_cast<float4*>(dx + row * E + 4 * lig) =
-          make_float4(rstd * (g.x - mg - xh.x * mgx), rstd * (g.y - mg - xh.y * mgx), rstd * (g.z - mg - xh.z * mgx),
-                      rstd * (g.w - mg - xh.w * mgx));
-      *reinterpret_cast<float4*>(dyxhat + row * E + 4 * lig) = make_float4(gy.x * xh.x, gy.y * xh.y, gy.z * xh.z, gy.w * xh.w);
-    }
+    float4 gy, xh;
+    layernorm_bwd_row<LG, float>(dy, x, nullptr, wv, stats[2 * row], stats[2 * row + 1], row, E, lig, live, dx, gy, xh);
+    if (live) store4(dyxhat + row * E + 4 * lig, make_float4(gy.x * xh.x, gy.y * xh.y, gy.z * xh.z, gy.w * xh.w));
   }
 }
 
@@ -187,43 +207,8 @@ __global__ void __launch_bounds__(256) act_bwd_kernel(int kind, const T* __restr
   }
 }
 
-// Residual add + LayerNorm of the Transformer's bf16 trunk: y = LN(x + s) (s = null: LN(x)) over rows [R, E] of bf16,
-// the layout of layernorm_fwd_kernel (E/4 lanes of a lane group per row).  The sum is formed in fp32 from the two
-// bf16 addends and normalised as it stands — it is never stored, so it is never rounded; y is rounded once.
-template <int LG>
-__global__ void __launch_bounds__(256) add_layernorm_fwd_bf16_kernel(const bf16_t* __restrict__ x,
-                                                                     const bf16_t* __restrict__ s, int64_t R, int E,
-                                                                     const float* __restrict__ w,
-                                                                     const float* __restrict__ b, float eps,
-                                                                     bf16_t* __restrict__ y,
-                                                                     float* __restrict__ stats /* [R,2] mean, rstd */) {
-  const int lig = threadIdx.x % LG;
-  const bool live = lig * 4 < E;
-  const float4 wv = live ? *reinterpret_cast<const float4*>(w + 4 * lig) : make_float4(0, 0, 0, 0);
-  const float4 bv = live ? *reinterpret_cast<const float4*>(b + 4 * lig) : make_float4(0, 0, 0, 0);
-  for (int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG; row < R;
-       row += ((int64_t)gridDim.x * blockDim.x) / LG) {
-    float4 v = live ? load4(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
-    if (s && live) {
-      const float4 a = load4(s + row * E + 4 * lig);
-      v = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
-    }
-    const float mean = group_sum<LG>(v.x + v.y + v.z + v.w) / E;
-    const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
-    const float var = group_sum<LG>(live ? d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w : 0.f) / E;
-    const float rstd = rsqrtf(var + eps);
-    if (live)
-      store4(y + row * E + 4 * lig, make_float4(d.x * rstd * wv.x + bv.x, d.y * rstd * wv.y + bv.y,
-                                                d.z * rstd * wv.z + bv.z, d.w * rstd * wv.w + bv.w));
-    if (lig == 0) {
-      stats[2 * row] = mean;
-      stats[2 * row + 1] = rstd;
-    }
-  }
-}
-
-// Backward of the above: the sum is recomputed from x and s; dsum = rstd * (g - mean(g) - xhat * mean(g * xhat)),
-// g = dy * w, is the gradient of BOTH addends (bf16, rounded once).  dL/dw = sum_rows dy * xhat and dL/db =
+// Backward of the bf16 add + LayerNorm: the sum is recomputed from x and s; dsum (layernorm_bwd_row's dv) is the
+// gradient of BOTH addends (bf16, rounded once).  dL/dw = sum_rows dy * xhat and dL/db =
 // sum_rows dy leave as ONE fp32 partial row per workgroup, part [gridDim.x, 2E] = (dw | db): a lane adds its rows'
 // terms in row order, the wave's lanes of one column group are added by a fixed butterfly, the four waves in wave
 // order — no [R, E] dy * xhat tensor, no atomics, bitwise deterministic.  The caller sums the rows (mapx_sum_tasks).
@@ -248,20 +233,9 @@ __global__ void __launch_bounds__(256) add_layernorm_bwd_bf16_kernel(const bf16_
     const int64_t row = r0 + (threadIdx.x & (kWave - 1)) / LG;
     const bool have = live && row < R;
     const float mean = row < R ? stats[2 * row] : 0.f, rstd = row < R ? stats[2 * row + 1] : 0.f;
-    float4 v = have ? load4(x + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
-    if (s && have) {
-      const float4 a = load4(s + row * E + 4 * lig);
-      v = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
-    }
-    const float4 gy = have ? load4(dy + row * E + 4 * lig) : make_float4(0, 0, 0, 0);
-    const float4 xh = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
-    const float4 g = make_float4(gy.x * wv.x, gy.y * wv.y, gy.z * wv.z, gy.w * wv.w);
-    const float mg = group_sum<LG>(have ? g.x + g.y + g.z + g.w : 0.f) / E;
-    const float mgx = group_sum<LG>(have ? g.x * xh.x + g.y * xh.y + g.z * xh.z + g.w * xh.w : 0.f) / E;
+    float4 gy, xh;
+    layernorm_bwd_row<LG>(dy, x, s, wv, mean, rstd, row, E, lig, have, dsum, gy, xh);
     if (have) {
-      store4(dsum + row * E + 4 * lig,
-             make_float4(rstd * (g.x - mg - xh.x * mgx), rstd * (g.y - mg - xh.y * mgx), rstd * (g.z - mg - xh.z * mgx),
-                         rstd * (g.w - mg - xh.w * mgx)));
       aw.x = fmaf(gy.x, xh.x, aw.x); aw.y = fmaf(gy.y, xh.y, aw.y);
       aw.z = fmaf(gy.z, xh.z, aw.z); aw.w = fmaf(gy.w, xh.w, aw.w);
       ab.x += gy.x; ab.y += gy.y; ab.z += gy.z; ab.w += gy.w;
@@ -294,11 +268,22 @@ __global__ void __launch_bounds__(256) add_layernorm_bwd_bf16_kernel(const bf16_
   }
 }
 
-static int add_ln_lanes(int E) { return E <= 16 ? 4 : (E <= 32 ? 8 : 16); }
-static int add_ln_bwd_groups(int64_t R, int E) { return grid_for(R * add_ln_lanes(E), 256, kAddLnBwdMaxGroups); }
+static int ln_lanes(int E) { return E <= 16 ? 4 : (E <= 32 ? 8 : 16); }
+static int add_ln_bwd_groups(int64_t R, int E) { return grid_for(R * ln_lanes(E), 256, kAddLnBwdMaxGroups); }
 
-static inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
-static inline bf16_t* hm(mapx_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
+template <class T>
+static int layernorm_fwd_launch(const char* what, const T* x, const T* s_opt, int64_t R, int E, const float* w,
+                                const float* b, float eps, T* y, float* stats, hipStream_t stream) {
+  const int lg = ln_lanes(E);
+  const int grid = grid_for(R * lg, 256);
+  if (lg == 4)
+    hipLaunchKernelGGL((layernorm_fwd_kernel<4, T>), dim3(grid), dim3(256), 0, stream, x, s_opt, R, E, w, b, eps, y, stats);
+  else if (lg == 8)
+    hipLaunchKernelGGL((layernorm_fwd_kernel<8, T>), dim3(grid), dim3(256), 0, stream, x, s_opt, R, E, w, b, eps, y, stats);
+  else
+    hipLaunchKernelGGL((layernorm_fwd_kernel<16, T>), dim3(grid), dim3(256), 0, stream, x, s_opt, R, E, w, b, eps, y, stats);
+  return check_launch(what);
+}
 
 }  // namespace mapx
 
@@ -333,16 +318,7 @@ extern "C" int mapx_add_layernorm_fwd_bf16(const mapx_bf16* x, const mapx_bf16* 
   MAPX_REQUIRE(x && w && b && y && stats, "add_layernorm_fwd_bf16: null pointer");
   MAPX_REQUIRE(((uintptr_t)x | (uintptr_t)s_opt | (uintptr_t)y) % 8 == 0 && ((uintptr_t)w | (uintptr_t)b) % 16 == 0,
                "add_layernorm_fwd_bf16: x, s, y must be 8-byte aligned, w and b 16-byte aligned");
-  const int lg = add_ln_lanes(E);
-  const int grid = grid_for(R * lg, 256);
-#define MAPX_ADD_LN_FWD(LG)                                                                                        \
-  hipLaunchKernelGGL(add_layernorm_fwd_bf16_kernel<LG>, dim3(grid), dim3(256), 0, stream, hc(x), hc(s_opt), R, E, w, b, \
-                     eps, hm(y), stats)
-  if (lg == 4) MAPX_ADD_LN_FWD(4);
-  else if (lg == 8) MAPX_ADD_LN_FWD(8);
-  else MAPX_ADD_LN_FWD(16);
-#undef MAPX_ADD_LN_FWD
-  return check_launch("add_layernorm_fwd_bf16");
+  return layernorm_fwd_launch("add_layernorm_fwd_bf16", hc(x), hc(s_opt), R, E, w, b, eps, hm(y), stats, stream);
 }
 
 extern "C" int mapx_add_layernorm_bwd_groups(int64_t R, int E) {
@@ -359,7 +335,7 @@ extern "C" int mapx_add_layernorm_bwd_bf16(const mapx_bf16* dy, const mapx_bf16*
   MAPX_REQUIRE(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)s_opt | (uintptr_t)dsum) % 8 == 0 &&
                    ((uintptr_t)w | (uintptr_t)part) % 16 == 0,
                "add_layernorm_bwd_bf16: dy, x, s, dsum must be 8-byte aligned, w and part 16-byte aligned");
-  const int lg = add_ln_lanes(E);
+  const int lg = ln_lanes(E);
   const int grid = add_ln_bwd_groups(R, E);
 #define MAPX_ADD_LN_BWD(LG)                                                                                        \
   hipLaunchKernelGGL(add_layernorm_bwd_bf16_kernel<LG>, dim3(grid), dim3(256), 0, stream, hc(dy), hc(x), hc(s_opt), w, \
@@ -377,12 +353,7 @@ extern "C" int mapx_layernorm_fwd(const float* x, int64_t R, int E, const float*
   MAPX_REQUIRE(R >= 0 && E >= 4 && E <= 64 && E % 4 == 0, "layernorm_fwd: E must be a multiple of 4 in [4, 64]");
   if (R == 0) return MAPX_OK;
   MAPX_REQUIRE(x && w && b && y && stats, "layernorm_fwd: null pointer");
-  const int lg = E <= 16 ? 4 : (E <= 32 ? 8 : 16);
-  const int grid = grid_for(R * lg, 256);
-  if (lg == 4) hipLaunchKernelGGL(layernorm_fwd_kernel<4>, dim3(grid), dim3(256), 0, stream, x, R, E, w, b, eps, y, stats);
-  else if (lg == 8) hipLaunchKernelGGL(layernorm_fwd_kernel<8>, dim3(grid), dim3(256), 0, stream, x, R, E, w, b, eps, y, stats);
-  else hipLaunchKernelGGL(layernorm_fwd_kernel<16>, dim3(grid), dim3(256), 0, stream, x, R, E, w, b, eps, y, stats);
-  return check_launch("layernorm_fwd");
+  return layernorm_fwd_launch<float>("layernorm_fwd", x, nullptr, R, E, w, b, eps, y, stats, stream);
 }
 
 extern "C" int mapx_layernorm_bwd(const float* dy, const float* x, const float* w, const float* stats, int64_t R, int E,
@@ -391,7 +362,7 @@ extern "C" int mapx_layernorm_bwd(const float* dy, const float* x, const float* 
   MAPX_REQUIRE(R >= 0 && E >= 4 && E <= 64 && E % 4 == 0, "layernorm_bwd: E must be a multiple of 4 in [4, 64]");
   if (R == 0) return MAPX_OK;
   MAPX_REQUIRE(dy && x && w && stats && dx && dy_xhat, "layernorm_bwd: null pointer");
-  const int lg = E <= 16 ? 4 : (E <= 32 ? 8 : 16);
+  const int lg = ln_lanes(E);
   const int grid = grid_for(R * lg, 256);
   if (lg == 4) hipLaunchKernelGGL(layernorm_bwd_kernel<4>, dim3(grid), dim3(256), 0, stream, dy, x, w, stats, R, E, dx, dy_xhat);
   else if (lg == 8) hipLaunchKernelGGL(layernorm_bwd_kernel<8>, dim3(grid), dim3(256), 0, stream, dy, x, w, stats, R, E, dx, dy_xhat);

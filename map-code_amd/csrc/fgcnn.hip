@@ -35,26 +35,6 @@ constexpr int kIpMaxT = 192, kIpMaxE = 64;
 constexpr size_t kFgLdsLimit = 128 * 1024;     // dynamic LDS the kernels may ask for (the CU has 160 KB)
 enum { kActTanh = 0, kActRelu = 1 };
 
-__device__ inline void fma4(float4& acc, float s, const float4& v) {
-  acc.x = fmaf(s, v.x, acc.x);
-  acc.y = fmaf(s, v.y, acc.y);
-  acc.z = fmaf(s, v.z, acc.z);
-  acc.w = fmaf(s, v.w, acc.w);
-}
-
-__device__ inline float dot4(const float4& a, const float4& b, float s) {
-  s = fmaf(a.x, b.x, s);
-  s = fmaf(a.y, b.y, s);
-  s = fmaf(a.z, b.z, s);
-  return fmaf(a.w, b.w, s);
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 // THE normalised value and pre-activation of an element: forward and backward call these, so a relu unit sits on
 // the same side of the kink in both.
 __device__ inline float bn_xhat(float z, float mean, float rstd) { return __fmul_rn(__fsub_rn(z, mean), rstd); }
@@ -100,8 +80,8 @@ __global__ void __launch_bounds__(kFgBlock) fgcnn_conv_fwd_kernel(
       ss += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
     }
     if (part) {
-      s = wave_sum(s);
-      ss = wave_sum(ss);
+      s = group_sum<kWave>(s);
+      ss = group_sum<kWave>(ss);
       if (lane == 0) {
         part[(b * Cout + co) * 2 + 0] = s;
         part[(b * Cout + co) * 2 + 1] = ss;
@@ -237,8 +217,8 @@ __global__ void __launch_bounds__(kFgBlock) fgcnn_pool_bwd_kernel(
       s += (g0 + g1) + (g2 + g3);
       sx += (g0 * x0 + g1 * x1) + (g2 * x2 + g3 * x3);
     }
-    s = wave_sum(s);
-    sx = wave_sum(sx);
+    s = group_sum<kWave>(s);
+    sx = group_sum<kWave>(sx);
     if (lane == 0) {
       part[bc * 2 + 0] = s;
       part[bc * 2 + 1] = sx;
@@ -421,16 +401,8 @@ __global__ void __launch_bounds__(kFgBlock) inner_product_bwd_kernel(const float
 }
 
 static hipError_t raise_lds_limit() {
-  static hipError_t done = [] {
-    for (const void* fn : {reinterpret_cast<const void*>(&fgcnn_conv_fwd_kernel),
-                           reinterpret_cast<const void*>(&fgcnn_conv_bwd_kernel),
-                           reinterpret_cast<const void*>(&inner_product_fwd_kernel),
-                           reinterpret_cast<const void*>(&inner_product_bwd_kernel)}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFgLdsLimit);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }();
+  static const hipError_t done = allow_dynamic_lds(kFgLdsLimit, &fgcnn_conv_fwd_kernel, &fgcnn_conv_bwd_kernel,
+                                                   &inner_product_fwd_kernel, &inner_product_bwd_kernel);
   return done;
 }
 

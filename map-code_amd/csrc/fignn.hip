@@ -42,13 +42,6 @@ constexpr int kGnMaxTile = 32;                 // samples a workgroup of a layer
 // workspace vectors per (sample, field) row, E floats each
 enum { kWsA = 0, kWsAggr = 1, kWsDa = 2, kWsDho = 3, kWsDr = 4, kWsDz = 5, kWsDn = 6, kWsDhn = 7, kWsVecs = 8 };
 
-static __device__ inline void gn_fma4(float4& acc, float s, const float4& v) {
-  acc.x = fmaf(s, v.x, acc.x);
-  acc.y = fmaf(s, v.y, acc.y);
-  acc.z = fmaf(s, v.z, acc.z);
-  acc.w = fmaf(s, v.w, acc.w);
-}
-
 // One v_fmac_f32 per term, by hand, as in skinny.hip: several dot products that run side by side over LDS operands
 // (s and d of the graph, the GRU's six gates) are otherwise paired into v_pk_fma_f32 whose low lane takes the high
 // half of a ds_read result — the form tools/isa_guard.py keeps out of every kernel that ships.
@@ -58,12 +51,6 @@ static __device__ inline float gn_dot4(const float4& a, const float4& b, float s
   asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(s) : "v"(a.z), "v"(b.z));
   asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(s) : "v"(a.w), "v"(b.w));
   return s;
-}
-
-static __device__ inline float gn_wave_max(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
 }
 
 static __device__ inline float gn_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
@@ -107,7 +94,7 @@ __global__ void __launch_bounds__(kGnBlock) fignn_graph_fwd_kernel(const float* 
       const float pre = __shfl(si, i, kWave) + di;
       const float al = pre > 0.f ? pre : kGnLeaky * pre;
       const bool on = lane < F && lane != i;
-      const float m = gn_wave_max(on ? al : -__builtin_huge_valf());
+      const float m = group_max<kWave>(on ? al : -__builtin_huge_valf());
       const float p = on ? expf(al - m) : 0.f;
       const float sum = group_sum<kWave>(p);
       if (lane < F) g[(b * F + i) * F + lane] = p / sum;
@@ -174,8 +161,8 @@ __global__ void __launch_bounds__(kGnBlock) fignn_graph_bwd_kernel(
         v.z += a.z;
         v.w += a.w;
       }
-      gn_fma4(v, sds[i], wsrc[c]);
-      gn_fma4(v, sdd[i], wdst[c]);
+      fma4(v, sds[i], wsrc[c]);
+      fma4(v, sdd[i], wdst[c]);
       dxs[t] = v;
     }
     if (lane < 2 * E) {
@@ -594,16 +581,9 @@ __global__ void __launch_bounds__(kGnBlock) fignn_pred_bwd_kernel(const float* _
 
 // ------------------------------------------------------------------------------------------------ host
 static hipError_t gn_raise_lds_limit() {
-  static hipError_t done = [] {
-    for (const void* fn : {reinterpret_cast<const void*>(&fignn_layer_fwd_kernel<true>),
-                           reinterpret_cast<const void*>(&fignn_layer_fwd_kernel<false>),
-                           reinterpret_cast<const void*>(&fignn_layer_bwd_kernel<true>),
-                           reinterpret_cast<const void*>(&fignn_layer_bwd_kernel<false>)}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGnLdsLimit);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }();
+  static const hipError_t done =
+      allow_dynamic_lds(kGnLdsLimit, &fignn_layer_fwd_kernel<true>, &fignn_layer_fwd_kernel<false>,
+                        &fignn_layer_bwd_kernel<true>, &fignn_layer_bwd_kernel<false>);
   return done;
 }
 

@@ -30,9 +30,6 @@ __global__ void __launch_bounds__(256) lr_sum_kernel(const int64_t* __restrict__
   }
 }
 
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
 // One lane per (row, e): walks the F fields (the E lanes of a row read E consecutive elements).
 // s[b,e] = sum_f x is kept for backward.  E <= 64 and a power of two (host-checked).
 // T: the element type of x, float or bf16_t (bf16 compute mode: widened on load, sums and outputs fp32).
@@ -55,20 +52,8 @@ __global__ void __launch_bounds__(256) fm_fwd_kernel(const T* __restrict__ x, in
   }
 }
 
-// Four consecutive elements of x / dx: one 16-byte (fp32) or 8-byte (bf16) access
-__device__ inline float4 fm_load4(const float* p, int64_t i) { return reinterpret_cast<const float4*>(p)[i]; }
-__device__ inline float4 fm_load4(const bf16_t* p, int64_t i) {
-  const bf16x4_t v = reinterpret_cast<const bf16x4_t*>(p)[i];
-  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-__device__ inline void fm_store4(float* p, int64_t i, const float4& v) { reinterpret_cast<float4*>(p)[i] = v; }
-__device__ inline void fm_store4(bf16_t* p, int64_t i, const float4& v) {      // round to nearest even, once
-  bf16x4_t o;
-  o[0] = (bf16_t)v.x; o[1] = (bf16_t)v.y; o[2] = (bf16_t)v.z; o[3] = (bf16_t)v.w;
-  reinterpret_cast<bf16x4_t*>(p)[i] = o;
-}
-
-// dx[b,f,e] = g[b] * (s[b,e] - x[b,f,e])      (g, s fp32; x, dx of type T)
+// dx[b,f,e] = g[b] * (s[b,e] - x[b,f,e])      (g, s fp32; x, dx of type T: four consecutive elements per thread, one
+// 16-byte (fp32) or 8-byte (bf16) access, common.h load4 / store4)
 template <class T>
 __global__ void __launch_bounds__(256) fm_bwd_kernel(const float* __restrict__ g, const float* __restrict__ s,
                                                      const T* __restrict__ x, int64_t B, int F, int E,
@@ -81,8 +66,8 @@ __global__ void __launch_bounds__(256) fm_bwd_kernel(const float* __restrict__ g
     const int c = (int)(i % e4);
     const float gb = g[b];
     const float4 sv = reinterpret_cast<const float4*>(s)[b * e4 + c];
-    const float4 xv = fm_load4(x, i);
-    fm_store4(dx, i, make_float4(gb * (sv.x - xv.x), gb * (sv.y - xv.y), gb * (sv.z - xv.z), gb * (sv.w - xv.w)));
+    const float4 xv = load4(x + 4 * i);
+    store4(dx + 4 * i, make_float4(gb * (sv.x - xv.x), gb * (sv.y - xv.y), gb * (sv.z - xv.z), gb * (sv.w - xv.w)));
   }
 }
 
@@ -136,7 +121,7 @@ extern "C" int mapx_fm_fwd_bf16(const mapx_bf16* x, int64_t B, int F, int E, flo
   if (B == 0) return MAPX_OK;
   MAPX_REQUIRE(x && out && s, "fm_fwd_bf16: null pointer");
   const int grid = mapx::grid_for(B * E, 256);
-  const mapx::bf16_t* xh = reinterpret_cast<const mapx::bf16_t*>(x);
+  const mapx::bf16_t* xh = mapx::hc(x);
 #define MAPX_FM(E_) hipLaunchKernelGGL((mapx::fm_fwd_kernel<E_, mapx::bf16_t>), dim3(grid), dim3(256), 0, stream, xh, B, F, out, s)
   switch (E) {
     case 8: MAPX_FM(8); break;
@@ -157,6 +142,6 @@ extern "C" int mapx_fm_bwd_bf16(const float* g, const float* s, const mapx_bf16*
   MAPX_REQUIRE(((uintptr_t)s % 16 == 0) && ((uintptr_t)x % 8 == 0) && ((uintptr_t)dx % 8 == 0),
                "fm_bwd_bf16: s must be 16-byte, x and dx 8-byte aligned");
   hipLaunchKernelGGL(mapx::fm_bwd_kernel<mapx::bf16_t>, dim3(mapx::grid_for(B * F * E / 4, 256)), dim3(256), 0, stream, g, s,
-                     reinterpret_cast<const mapx::bf16_t*>(x), B, F, E, reinterpret_cast<mapx::bf16_t*>(dx));
+                     mapx::hc(x), B, F, E, mapx::hm(dx));
   return mapx::check_launch("fm_bwd_bf16");
 }

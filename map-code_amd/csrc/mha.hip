@@ -5,7 +5,8 @@
 // [E,2E) = K, [2E,3E) = V; head h owns columns [h*dh, (h+1)*dh) of each third (dh = E/H).  Per group g = b*H + h:
 //   P = softmax(Q K^T / sqrt(dh)) [F,F] (kept, undropped, for backward);  P~ = P * m / (1-p);  O = P~ V,
 // O written into o [M, E] at the same columns of the head: the head-concatenated layout out_proj reads.  The keep
-// mask m is regenerated from Philox in backward (mha_keep4: one 128-bit draw per 4 keys of a query row), never stored.
+// mask m is regenerated from Philox in backward (mha_keep4: one dropout draw of common.h per 4 keys of a query row),
+// never stored.
 //
 // Layout (attn.hip's): one wave per group, Q/K/V rows in LDS (16-byte rows, float4 loads along dh), one lane per
 // query row, two groups per wave when F <= 32.  The F x F probabilities live in LDS at a row pitch of F+1 floats
@@ -24,31 +25,10 @@ namespace mapx {
 constexpr int kMhaMaxF = 64, kMhaMaxDh = 64;
 
 // Keep bits of keys 4q .. 4q+3 of query row `row` (= g*F + i) of the probability matrices: bit e set = key 4q+e
-// kept.  THE definition of the attention-dropout mask: both kernels and mapx_mha_dropout_mask call it.
+// kept.  The counter of the attention-dropout mask (the draw itself: common.h): both kernels and
+// mapx_mha_dropout_mask call it.  attn.hip's P mask uses the same counter.
 __device__ inline uint32_t mha_keep4(uint64_t seed, uint64_t off, uint32_t thr, int64_t row, int nq4, int q) {
-  const Philox4 r = philox4x32_10(seed, (uint64_t)(row * nq4 + q), off);
-  return (uint32_t)(r.x >= thr) | ((uint32_t)(r.y >= thr) << 1) | ((uint32_t)(r.z >= thr) << 2) |
-         ((uint32_t)(r.w >= thr) << 3);
-}
-
-__device__ inline uint32_t drop_threshold(float p) { return (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f); }
-
-__device__ inline uint64_t drop_offset(uint64_t offset, const int32_t* offset_dev) {
-  return offset + (offset_dev ? (uint64_t)(uint32_t)*offset_dev : 0ull);
-}
-
-__device__ inline void fma4(float4& acc, float s, const float4& v) {
-  acc.x = fmaf(s, v.x, acc.x);
-  acc.y = fmaf(s, v.y, acc.y);
-  acc.z = fmaf(s, v.z, acc.z);
-  acc.w = fmaf(s, v.w, acc.w);
-}
-
-__device__ inline float dot4(const float4& a, const float4& b, float s) {
-  s = fmaf(a.x, b.x, s);
-  s = fmaf(a.y, b.y, s);
-  s = fmaf(a.z, b.z, s);
-  return fmaf(a.w, b.w, s);
+  return keep_bits4(philox4x32_10(seed, (uint64_t)(row * nq4 + q), off), thr);
 }
 
 // Cooperative 16-byte loads of `nsec` row sections of width dh (each starting at column col0 + s*E of the rows
@@ -336,25 +316,13 @@ __global__ void __launch_bounds__(256) field_pool_bwd_kernel(const T* __restrict
   }
 }
 
-template <typename K>
-static hipError_t allow_lds(K* fn) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-}
-
 // F = dh = 64 needs 104 KB of dynamic LDS in backward: above the 64 KB default, inside the CU's 160 KB
-static hipError_t raise_mha_lds_limit() {
-  static hipError_t done = [] {
-    hipError_t e = hipSuccess;
-#define MAPX_MHA_ALLOW(GPW, DHB)                                                     \
-  if (e == hipSuccess) e = allow_lds(&mha_fwd_kernel<GPW, DHB, float>);              \
-  if (e == hipSuccess) e = allow_lds(&mha_bwd_kernel<GPW, DHB, float>);              \
-  if (e == hipSuccess) e = allow_lds(&mha_fwd_kernel<GPW, DHB, bf16_t>);             \
-  if (e == hipSuccess) e = allow_lds(&mha_bwd_kernel<GPW, DHB, bf16_t>);
-    MAPX_MHA_ALLOW(1, 8) MAPX_MHA_ALLOW(1, 16) MAPX_MHA_ALLOW(1, 32) MAPX_MHA_ALLOW(1, 64)
-    MAPX_MHA_ALLOW(2, 8) MAPX_MHA_ALLOW(2, 16) MAPX_MHA_ALLOW(2, 32) MAPX_MHA_ALLOW(2, 64)
-#undef MAPX_MHA_ALLOW
-    return e;
-  }();
+template <int GPW, class T>
+static hipError_t mha_allow_lds() {
+  static const hipError_t done = allow_dynamic_lds(
+      128 * 1024, &mha_fwd_kernel<GPW, 8, T>, &mha_fwd_kernel<GPW, 16, T>, &mha_fwd_kernel<GPW, 32, T>,
+      &mha_fwd_kernel<GPW, 64, T>, &mha_bwd_kernel<GPW, 8, T>, &mha_bwd_kernel<GPW, 16, T>, &mha_bwd_kernel<GPW, 32, T>,
+      &mha_bwd_kernel<GPW, 64, T>);
   return done;
 }
 
@@ -391,11 +359,12 @@ static int mha_fwd_launch(const char* what, const T* qkv, int64_t B, int F, int 
   const int64_t G = B * H;
   const float scale = 1.0f / sqrtf((float)(E / H));
   const size_t lds = mha_lds_bytes(F, E / H, false);
-  MAPX_HIP(raise_mha_lds_limit());
   if (F <= 32) {
+    MAPX_HIP((mha_allow_lds<2, T>()));
     MAPX_MHA_DISPATCH(mha_fwd_kernel, 2, dim3((unsigned)((G + 1) / 2)), 2 * lds, qkv, G, H, F, E, scale, p, seed, offset,
                       offset_dev_opt, o, probs)
   } else {
+    MAPX_HIP((mha_allow_lds<1, T>()));
     MAPX_MHA_DISPATCH(mha_fwd_kernel, 1, dim3((unsigned)G), lds, qkv, G, H, F, E, scale, p, seed, offset, offset_dev_opt,
                       o, probs)
   }
@@ -414,11 +383,12 @@ static int mha_bwd_launch(const char* what, const T* qkv, const float* probs, co
   const int64_t G = B * H;
   const float scale = 1.0f / sqrtf((float)(E / H));
   const size_t lds = mha_lds_bytes(F, E / H, true);
-  MAPX_HIP(raise_mha_lds_limit());
   if (F <= 32) {
+    MAPX_HIP((mha_allow_lds<2, T>()));
     MAPX_MHA_DISPATCH(mha_bwd_kernel, 2, dim3((unsigned)((G + 1) / 2)), 2 * lds, qkv, probs, d_o, G, H, F, E, scale, p,
                       seed, offset, offset_dev_opt, d_qkv)
   } else {
+    MAPX_HIP((mha_allow_lds<1, T>()));
     MAPX_MHA_DISPATCH(mha_bwd_kernel, 1, dim3((unsigned)G), lds, qkv, probs, d_o, G, H, F, E, scale, p, seed, offset,
                       offset_dev_opt, d_qkv)
   }
@@ -451,9 +421,6 @@ static int field_pool_bwd_launch(const char* what, const T* g, const T* x, const
                      weights_opt, B, F, E, mode, dx, d_scores_opt);
   return check_launch(what);
 }
-
-static inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
-static inline bf16_t* hm(mapx_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
 
 }  // namespace mapx
 

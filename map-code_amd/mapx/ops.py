@@ -617,58 +617,64 @@ def _f32(t, what):
     return t
 
 
-def _attn_half(what, *ts):
-    """True: the bf16 I/O forms (every tensor bf16); False: the fp32 entries.  Mixed element types are an error."""
+def _one_dtype(what, names, *ts, contiguous=False):
+    """True: the bf16 I/O forms (every tensor bf16); False: the fp32 entries.  Mixed element types are an error, and
+    with `contiguous` so is a tensor that is not contiguous."""
     half = is_bf16(ts[0])
     for t in ts:
-        if t.dtype != (BF16 if half else torch.float32) or not t.is_contiguous():
-            raise TypeError(f"{what}: q, k, v (and d_o) are contiguous tensors of one element type, fp32 or bf16")
+        if t.dtype != (BF16 if half else torch.float32):
+            raise TypeError(f"{what}: {names} have one element type, fp32 or bf16 (got {[str(x.dtype) for x in ts]})")
+        if contiguous and not t.is_contiguous():
+            raise TypeError(f"{what}: {names} are contiguous tensors")
     return half
+
+
+def _attn_fwd(entries, what, q, k, v, G, F, A, scaled, *drop):
+    """attn_fwd (no `drop`) and attn_drop_fwd (drop = p, seed, offset_p, offset_o, offset_dev) on `entries` = their
+    (fp32, bf16) C entries."""
+    require_gpu(q, k, v)
+    fn = entries[_one_dtype(what, "q, k, v", q, k, v, contiguous=True)]
+    o = torch.empty_like(q)
+    probs = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
+    check(fn(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), *_attn_drop_args(*drop), ptr(o), ptr(probs), stream()))
+    return o, probs
+
+
+def _attn_bwd(entries, what, q, k, v, probs, d_o, G, F, A, scaled, *drop):
+    require_gpu(q, k, v, probs, d_o)
+    d_o = d_o.contiguous()
+    fn = entries[_one_dtype(what, "q, k, v and d_o", q, k, v, d_o, contiguous=True)]
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(fn(ptr(q), ptr(k), ptr(v), ptr(_f32(probs, f"{what}: probs")), ptr(d_o), G, F, A, int(bool(scaled)),
+             *_attn_drop_args(*drop), ptr(dq), ptr(dk), ptr(dv), stream()))
+    return dq, dk, dv
+
+
+def _attn_drop_args(p=None, seed=0, offset_p=0, offset_o=0, offset_dev=None):
+    return () if p is None else (float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev))
 
 
 def attn_fwd(q, k, v, G, F, A, scaled):
     """q, k, v: G*F*A elements each, fp32 or bf16 (G = B*heads groups of [F, A]) -> (o same size and dtype,
     p [G,F,F] fp32)."""
-    require_gpu(q, k, v)
-    fn = lib.mapx_attn_fwd_bf16 if _attn_half("attn_fwd", q, k, v) else lib.mapx_attn_fwd
-    o = torch.empty_like(q)
-    p = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
-    check(fn(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), ptr(o), ptr(p), stream()))
-    return o, p
+    return _attn_fwd((lib.mapx_attn_fwd, lib.mapx_attn_fwd_bf16), "attn_fwd", q, k, v, G, F, A, scaled)
 
 
 def attn_bwd(q, k, v, p, d_o, G, F, A, scaled):
-    require_gpu(q, k, v, p, d_o)
-    d_o = d_o.contiguous()
-    fn = lib.mapx_attn_bwd_bf16 if _attn_half("attn_bwd", q, k, v, d_o) else lib.mapx_attn_bwd
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(fn(ptr(q), ptr(k), ptr(v), ptr(_f32(p, "attn_bwd: p")), ptr(d_o), G, F, A, int(bool(scaled)),
-             ptr(dq), ptr(dk), ptr(dv), stream()))
-    return dq, dk, dv
+    return _attn_bwd((lib.mapx_attn_bwd, lib.mapx_attn_bwd_bf16), "attn_bwd", q, k, v, p, d_o, G, F, A, scaled)
 
 
 def attn_drop_fwd(q, k, v, G, F, A, scaled, p, seed, offset_p, offset_o, offset_dev=None):
     """attn_fwd with the layer's two dropouts inside the kernel: O = ((P * m_p / (1-p)) V) * m_o / (1-p) with
     (m_p, m_o) = attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev) -> (o, p undropped)."""
-    require_gpu(q, k, v)
-    fn = lib.mapx_attn_drop_fwd_bf16 if _attn_half("attn_drop_fwd", q, k, v) else lib.mapx_attn_drop_fwd
-    o = torch.empty_like(q)
-    probs = torch.empty(G, F, F, dtype=torch.float32, device=q.device)
-    check(fn(ptr(q), ptr(k), ptr(v), G, F, A, int(bool(scaled)), float(p), int(seed), int(offset_p),
-             int(offset_o), ptr(offset_dev), ptr(o), ptr(probs), stream()))
-    return o, probs
+    return _attn_fwd((lib.mapx_attn_drop_fwd, lib.mapx_attn_drop_fwd_bf16), "attn_drop_fwd", q, k, v, G, F, A, scaled,
+                     p, seed, offset_p, offset_o, offset_dev)
 
 
 def attn_drop_bwd(q, k, v, probs, d_o, G, F, A, scaled, p, seed, offset_p, offset_o, offset_dev=None):
     """-> (dq, dk, dv); both masks are regenerated from (seed, offsets)."""
-    require_gpu(q, k, v, probs, d_o)
-    d_o = d_o.contiguous()
-    fn = lib.mapx_attn_drop_bwd_bf16 if _attn_half("attn_drop_bwd", q, k, v, d_o) else lib.mapx_attn_drop_bwd
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(fn(ptr(q), ptr(k), ptr(v), ptr(_f32(probs, "attn_drop_bwd: probs")), ptr(d_o), G, F, A, int(bool(scaled)),
-             float(p), int(seed), int(offset_p), int(offset_o), ptr(offset_dev), ptr(dq), ptr(dk),
-             ptr(dv), stream()))
-    return dq, dk, dv
+    return _attn_bwd((lib.mapx_attn_drop_bwd, lib.mapx_attn_drop_bwd_bf16), "attn_drop_bwd", q, k, v, probs, d_o, G, F,
+                     A, scaled, p, seed, offset_p, offset_o, offset_dev)
 
 
 def attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev=None, device="cuda"):
@@ -682,16 +688,6 @@ def attn_dropout_masks(G, F, A, p, seed, offset_p, offset_o, offset_dev=None, de
 
 
 # --------------------------------------------------------------------------- Transformer attention core
-def _one_dtype(what, names, *ts):
-    """True: the bf16 I/O forms (every tensor bf16); False: the fp32 entries.  Mixed element types are an error, as in
-    _attn_half."""
-    half = is_bf16(ts[0])
-    for t in ts:
-        if t.dtype != (BF16 if half else torch.float32):
-            raise TypeError(f"{what}: {names} have one element type, fp32 or bf16 (got {[str(x.dtype) for x in ts]})")
-    return half
-
-
 def mha_fwd(qkv, B, F, E, H, p=0.0, seed=0, offset=0, offset_dev=None):
     """qkv [B*F, 3E] (the in-projection's output, read in place) -> (o [B*F, E] heads concatenated,
     probs [B*H, F, F] undropped).  p > 0: O = (P * m / (1-p)) V with m = mha_dropout_mask(B, F, H, p, seed, offset)."""

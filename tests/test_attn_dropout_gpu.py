@@ -147,6 +147,20 @@ def test_offset_dev_is_added_to_both_offsets(ops):
         assert torch.equal(x, y)
 
 
+@pytest.mark.parametrize("F", [5, 23, 33])
+def test_the_p_mask_is_the_transformer_cores_mask_for_the_same_draws(ops, F):
+    """Both cores keep key 4c+e of query row `row` iff element e of the draw at counter row * ceil(F/4) + c is kept:
+    for one (seed, offset) the Transformer core's mask of B*H groups is the AutoInt P mask of G = B*H groups."""
+    B, H, A, p = 3, 2, 12, 0.3
+    dev = torch.tensor([5], dtype=torch.int32, device=DEV)
+    for offset_dev in (None, dev):
+        mha = ops.mha_dropout_mask(B, F, H, p, SEED, OFF_P, offset_dev)
+        kp, _ = ops.attn_dropout_masks(B * H, F, A, p, SEED, OFF_P, OFF_O, offset_dev)
+        assert mha.shape == kp.shape == (B * H, F, F)
+        assert 0 < int(kp.sum()) < kp.numel()
+        assert torch.equal(mha, kp)
+
+
 @pytest.mark.parametrize("G,F,A,scaled", [(7, 23, 12, 1), (5, 33, 16, 0)])
 def test_rate_zero_through_the_new_entries_is_the_plain_core_bitwise(ops, G, F, A, scaled):
     q, k, v, d_o = (t.to(DEV) for t in attn_inputs(G, F, A))

@@ -186,6 +186,21 @@ def test_add_layernorm_bf16_matches_float64_torch(ops, R, E, with_s, eps):
     assert torch.equal(dsum, dsum2) and torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
+@pytest.mark.parametrize("R,E", [(5, 12), (67, 64), (3, 4)])
+def test_layernorm_fp32_and_bf16_entries_are_one_forward_kernel(ops, R, E):
+    """On bf16-representable rows the fp32 entry and the bf16 entry (no second addend) see the same fp32 values: the
+    saved (mean, rstd) are bitwise equal, and the bf16 y is the fp32 y rounded once."""
+    g = torch.Generator().manual_seed(100 * R + E)
+    x = _rb(torch.randn(R, E, generator=g, dtype=torch.float64) + 1.5)
+    w = (torch.randn(E, generator=g) * 0.5 + 1.0).to(DEV)
+    b = (torch.randn(E, generator=g) * 0.5).to(DEV)
+    y32, stats32 = ops.layernorm_fwd(x.float().to(DEV), w, b, 1e-5)
+    y16, stats16 = ops.add_layernorm_fwd(_dev(x), None, w, b, 1e-5)
+    assert y32.dtype == torch.float32 and y16.dtype == BF16 and y16.shape == y32.shape == (R, E)
+    assert torch.equal(stats32, stats16)
+    assert torch.equal(y16, y32.to(BF16))
+
+
 def test_add_layernorm_bf16_rejects_fp32_rows_and_wide_rows(ops):
     from mapx.native import MapxError
     x = torch.zeros(8, 16, device=DEV, dtype=BF16)
