@@ -154,6 +154,38 @@ int mapx_cin_pool_fwd(const float* xt, int64_t B, int E, int H, float* out, int6
 int mapx_cin_pool_bwd(const float* g, int64_t ld_g, int64_t B, int E, int H, float* dxt, int accumulate,
                       hipStream_t stream);
 
+/* bf16 compute mode: the CIN without the Hadamard matrix (csrc/cin_fused.hip).  Rows r = (b, d), R = B*E; x0t [R, F],
+ * a layer's input xi [R, H] and output y [R, U] are bf16 with row pitches that are multiples of 8 elements (pad columns
+ * zero); w is the bf16 shadow of the 1x1 convolution's weight viewed [U, F*H]; 2 <= F <= 64, H and U in 1..128.
+ *   fwd         y[r, o] = bf16(bias[o] + sum_{h,m} w[o, h*H + m] * bf16(x0t[r, h] * xi[r, m]))
+ *   bwd_input   with dA = dy w (never stored): dx0t[r, h] (fp32 [R, F]; accumulate_x0: +=) = sum_m dA[r, hH+m] xi[r, m]
+ *               and dxi[r, m] = sum_h dA[r, hH+m] x0t[r, h], which goes to dy_prev[r, m] = bf16(dxi + gpool[r / E, m])
+ *               (gpool: the pooled gradient of the layer below, bf16 with row stride ld_g, or NULL) or, first_layer
+ *               (xi is x0t, H == F, dy_prev and gpool NULL), into dx0t[r, m] as well
+ *   bwd_weight  dw[o, k] (fp32 [U, F*H]) = sum_r dy[r, o] * bf16(x0t[r, h] * xi[r, m]); R is cut into slabs of at least
+ *               mapx_cin_fused_dw_slab_rows() rows whose fp32 partials (ws) are added in slab order
+ *   transpose   out[(b*C + c) * ld_out + r] = x[b, r, c] (pad columns zeroed);  dx3[b, f, d] = bf16(dx0t[(b*E+d)*F + f])
+ *   pool_fwd    out[b * ld_out + o] = bf16(sum_d y[(b*E + d) * ld_y + o]);  pool_bwd  dy[(b*E + d) * ld_dy + o] = g[b * ld_g + o] */
+int mapx_cin_fused_dw_slab_rows(void);
+int mapx_cin_fused_fwd(const mapx_bf16* x0t, int ld_x0, int F, const mapx_bf16* xi, int ld_xi, int H,
+                       const mapx_bf16* w, const float* bias, int U, int64_t R, mapx_bf16* y, int ld_y,
+                       hipStream_t stream);
+int mapx_cin_fused_bwd_input(const mapx_bf16* dy, int ld_dy, int U, const mapx_bf16* w, const mapx_bf16* x0t,
+                             int ld_x0, int F, const mapx_bf16* xi, int ld_xi, int H, int64_t R, float* dx0t,
+                             int accumulate_x0, int first_layer, const mapx_bf16* gpool, int64_t ld_g, int E,
+                             mapx_bf16* dy_prev, int ld_prev, hipStream_t stream);
+size_t mapx_cin_fused_bwd_weight_workspace_bytes(int F, int H, int U, int64_t R);
+int mapx_cin_fused_bwd_weight(const mapx_bf16* dy, int ld_dy, int U, const mapx_bf16* x0t, int ld_x0, int F,
+                              const mapx_bf16* xi, int ld_xi, int H, int64_t R, void* ws, size_t ws_bytes,
+                              float* dw, hipStream_t stream);
+int mapx_cin_transpose_bf16(const mapx_bf16* x, int64_t B, int R, int C, mapx_bf16* out, int ld_out,
+                            hipStream_t stream);
+int mapx_cin_dx3_bf16(const float* dx0t, int64_t B, int E, int F, mapx_bf16* dx3, hipStream_t stream);
+int mapx_cin_pool_fwd_bf16(const mapx_bf16* y, int ld_y, int64_t B, int E, int U, mapx_bf16* out, int64_t ld_out,
+                           hipStream_t stream);
+int mapx_cin_pool_bwd_bf16(const mapx_bf16* g, int64_t ld_g, int64_t B, int E, int U, mapx_bf16* dy, int ld_dy,
+                           hipStream_t stream);
+
 /* ------------------------------------------------------------------ DeepFM terms
  * LR  (models.py:129-143): out[b] = sum_f w[ids[b,f]]  (bias added by the caller).
  * FM  (layers.py:123-131, 'product_sum'): out[b] = 0.5 sum_e((sum_f x)^2 - sum_f x^2), s[b,e] = sum_f x;

@@ -1013,9 +1013,62 @@ class _CinStack(Function):
     backward accumulating into dX0."""
 
     @staticmethod
+    def _forward_bf16(ctx, x3, ws, bs):
+        """bf16 x3 (bf16 compute mode): the fused kernels of csrc/cin_fused.hip, which form the Hadamard
+        operand inside the MFMA loop.  x0t, every layer's Y and the pooled vector are bf16 (one rounding per store); the
+        weights' bf16 shadows are the operands.  Saved for backward: x0t and every layer's bf16 input, nothing of
+        extent R x F*H."""
+        B, F, E = x3.shape
+        x0t = ops.cin_transpose_bf16(x3)
+        units = [w.shape[0] for w in ws]
+        out = torch.empty(B, sum(units), dtype=torch.bfloat16, device=x3.device)
+        wops = [ops.bf16_weight(w) for w in ws]
+        xi, h_in, xs, col = x0t, F, [], 0
+        for w, b, u in zip(wops, bs, units):
+            xs.append(xi)
+            xi = ops.cin_fused_fwd(x0t, F, xi, h_in, w, b)
+            ops.cin_pool_fwd_bf16(xi, u, B, E, out[:, col:col + u])
+            h_in, col = u, col + u
+        ctx.half, ctx.shape, ctx.units = True, (B, F, E), units
+        ctx.slots = [(_grad_slot(w), _grad_slot(b)) for w, b in zip(ws, bs)]
+        ctx.save_for_backward(*xs, *wops)
+        return out
+
+    @staticmethod
+    def _backward_bf16(ctx, g):
+        """Layers in reverse: the top layer's dY is its pooled gradient alone; every dX kernel adds the pooled gradient
+        of the layer below to its dxi and rounds the sum once; dx0t is one running fp32 sum."""
+        B, F, E = ctx.shape
+        units, n = ctx.units, len(ctx.units)
+        xs, wops = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        x0t = xs[0]
+        if g.dtype == torch.float32:
+            g = ops.cast_bf16(g)                  # an fp32 gradient enters the bf16 trunk
+        if g.stride(1) != 1:
+            g = g.contiguous()                    # else read in place: a slice of d(concat) costs no copy
+        grads = [None] * (2 * n)
+        cols = [sum(units[:i]) for i in range(n)]
+        dx0t = torch.empty(B * E, F, dtype=torch.float32, device=g.device)
+        dy = ops.cin_pool_bwd_bf16(g[:, cols[-1]:cols[-1] + units[-1]], B, E)
+        for i in range(n - 1, -1, -1):
+            u, h_in = units[i], (units[i - 1] if i else F)
+            sw, sb = ctx.slots[i]
+            db = ops.colsum(dy[:, :u], out=sb)
+            grads[2 * i + 1] = None if sb is not None else db
+            dw = ops.cin_fused_bwd_weight(dy, u, x0t, F, xs[i], h_in, out=sw)
+            grads[2 * i] = None if sw is not None else dw.view(u, F * h_in, 1)
+            gpool = g[:, cols[i - 1]:cols[i - 1] + h_in] if i else None
+            dy = ops.cin_fused_bwd_input(dy, u, wops[i], x0t, F, xs[i], h_in, dx0t, accumulate_x0=i != n - 1,
+                                         first_layer=i == 0, gpool=gpool, E=E)
+        return (ops.cin_dx3_bf16(dx0t, B, E, F),) + tuple(grads)
+
+    @staticmethod
     def forward(ctx, x3, *wb):
         B, F, E = x3.shape
         ws, bs = wb[0::2], wb[1::2]
+        if ops.is_bf16(x3):
+            return _CinStack._forward_bf16(ctx, x3, ws, bs)
+        ctx.half = False
         x0t = ops.transpose_batched(x3).view(B * E, F)
         units = [w.shape[0] for w in ws]
         out = torch.empty(B, sum(units), dtype=torch.float32, device=x3.device)
@@ -1043,6 +1096,8 @@ class _CinStack(Function):
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.half:
+            return _CinStack._backward_bf16(ctx, g)
         B, F, E = ctx.shape
         ws, x0t = ctx.ws, ctx.x0t
         dx0t = torch.empty_like(x0t)

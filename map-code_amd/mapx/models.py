@@ -1,7 +1,7 @@
 """BaseModel + DCNV2 (host mirror of reference code/models.py:21-127, 282-322): same factory,
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
 is a gfx950 kernel.  The other backbones the factory builds: DNN, DeepFM, xDeepFM, AutoInt, trans, fgcnn
-(from_config still refuses fignn, and trans with compute_dtype=bf16; build_backbone builds both)."""
+(from_config still refuses fignn, and trans / xDeepFM with compute_dtype=bf16; build_backbone builds them)."""
 import logging
 
 import torch
@@ -505,15 +505,30 @@ class AutoInt(BaseModel):
 class xDeepFM(BaseModel):
     """CIN + MLP (reference models.py:235-279): cat([CIN(embed), MLP(embed.flatten)]) — or the CIN alone when
     num_hidden_layers = 0 — feeds the MFP / RFD heads or `fc` (+ the LR term when use_lr).  The LR weight, when present, is the
-    secondary parameter of the embedding's RowTable as in DeepFM."""
+    secondary parameter of the embedding's RowTable as in DeepFM.
+    compute_dtype=bf16 (through build_backbone): the gathered rows, every CIN layer's output, the pooled CIN vector and
+    the MLP are bf16 — the fused kernels of csrc/cin_fused.hip, which never write the Hadamard matrix, and bf16 GEMMs on
+    the weights' shadows; the LR term and every logit stay fp32.  The fused kernels take 2 <= num_fields <= 64 and
+    cin_layer_units in 1..128."""
     used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
                    "cin_layer_units", "use_lr"]
 
     def __init__(self, config: Config):
         super().__init__(model_name="xDeepFM", config=config)
+        from .layers import compute_dtype_of
+        half = compute_dtype_of(config) != torch.float32
+        units = [int(c) for c in str(config.cin_layer_units).split(",")]
+        if half:
+            if config.num_hidden_layers > 0:
+                _refuse_bf16_mlp_options(config, "hidden_act", "hidden_dropout_rate")
+            if min(units) < 1 or max(units) > ops.CIN_MAX_UNITS:
+                raise NotImplementedError(f"cin_layer_units={config.cin_layer_units!r}: the fused CIN kernels of "
+                                          f"compute_dtype=bf16 take 1..{ops.CIN_MAX_UNITS} units per layer")
+            if not 2 <= int(config.num_fields) <= ops.CIN_MAX_FIELDS:
+                raise NotImplementedError(f"num_fields={config.num_fields}: the fused CIN kernels of compute_dtype=bf16 "
+                                          f"take 2..{ops.CIN_MAX_FIELDS} fields")
         self.embed = Embeddings(config)
         self.embed.defer_plan = True
-        units = [int(c) for c in str(config.cin_layer_units).split(",")]
         self.cin = CIN(config.num_fields, units)
         if config.num_hidden_layers > 0:
             self.dnn = MLPBlock(input_dim=config.num_fields * config.embed_size, hidden_size=config.hidden_size,
@@ -530,7 +545,7 @@ class xDeepFM(BaseModel):
             if self.lr_layer is not None:
                 self.embed.table = RowTable("embed.embedding", self.embed.embedding.weight,
                                             self.lr_layer.embed_w.weight)
-            self.fc = HipLinear(final_dim, 1)
+            self.fc = HipLinear(final_dim, 1, out_fp32=half)          # (bf16 mode: the logits stay fp32)
 
     def forward(self, input_ids, labels=None, masked_index=None, noise_samples=None):
         lr = None
@@ -804,13 +819,15 @@ class FiGNN(BaseModel):
 
 
 def build_backbone(config: Config):
-    """Every model name the reference's factory reaches: FiGNN and the Transformer in compute_dtype=bf16 here, the
-    rest through BaseModel.from_config (which still refuses fignn, and trans with bf16, as existing tests pin; making it
-    delegate is a one-line follow-up)."""
+    """Every model name the reference's factory reaches: FiGNN, and the Transformer and xDeepFM in compute_dtype=bf16
+    here, the rest through BaseModel.from_config (which still refuses fignn, and trans / xDeepFM with bf16, as existing
+    tests pin; making it delegate is a one-line follow-up)."""
     from .layers import compute_dtype_of
     name = str(config.model_name).lower()
     if name == "trans" and compute_dtype_of(config) != torch.float32:
         return Transformer(config)
+    if name == "xdeepfm" and compute_dtype_of(config) != torch.float32:
+        return xDeepFM(config)
     if name == "fignn":
         if compute_dtype_of(config) != torch.float32:
             raise NotImplementedError("compute_dtype=bf16 is built for DCNv2, DNN, DeepFM and AutoInt, "

@@ -38,6 +38,16 @@ SIGNATURES = {
     "mapx_cin_outer_bwd": (_i, [_p, _i64, _p, _i, _p, _i, _i64, _p, _i, _p, _p]),
     "mapx_cin_pool_fwd": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),
     "mapx_cin_pool_bwd": (_i, [_p, _i64, _i64, _i, _i, _p, _i, _p]),
+    "mapx_cin_fused_dw_slab_rows": (_i, []),
+    "mapx_cin_fused_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i64, _p, _i, _p]),
+    "mapx_cin_fused_bwd_input": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i64, _p, _i, _i, _p, _i64, _i, _p, _i,
+                                      _p]),
+    "mapx_cin_fused_bwd_weight_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
+    "mapx_cin_fused_bwd_weight": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i64, _p, _sz, _p, _p]),
+    "mapx_cin_transpose_bf16": (_i, [_p, _i64, _i, _i, _p, _i, _p]),
+    "mapx_cin_dx3_bf16": (_i, [_p, _i64, _i, _i, _p, _p]),
+    "mapx_cin_pool_fwd_bf16": (_i, [_p, _i, _i64, _i, _i, _p, _i64, _p]),
+    "mapx_cin_pool_bwd_bf16": (_i, [_p, _i64, _i64, _i, _i, _p, _i, _p]),
     "mapx_host_alloc_coherent": (_i, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "mapx_host_free": (_i, [_p]),
     "mapx_lr_sum_fwd": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _p]),

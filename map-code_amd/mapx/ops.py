@@ -573,6 +573,115 @@ def cin_pool_bwd(g, B, E, dxt, accumulate):
     return dxt
 
 
+# --------------------------------------------------------------------------- xDeepFM in bf16 mode: fused CIN
+# csrc/cin_fused.hip.  Activations are bf16 [R, ld] tensors whose row pitch ld = pad8(width) is a multiple of 8 elements
+# (pad columns zero); the logical width travels beside them.
+CIN_MAX_FIELDS, CIN_MAX_UNITS = 64, 128
+CIN_DW_SLAB_ROWS = lib.mapx_cin_fused_dw_slab_rows()
+
+
+def pad8(n):
+    return (int(n) + 7) // 8 * 8
+
+
+def _cin_bf16(*tensors):
+    require_gpu(*tensors)
+    for t in tensors:
+        if t is not None and t.dtype != BF16:
+            raise TypeError("fused CIN kernels take bf16 activations and the weight's bf16 operand")
+
+
+def cin_transpose_bf16(x3):
+    """bf16 [B,F,E] -> x0t [B*E, pad8(F)]."""
+    _cin_bf16(x3)
+    x3 = x3.contiguous()
+    B, F, E = x3.shape
+    out = torch.empty(B * E, pad8(F), dtype=BF16, device=x3.device)
+    check(lib.mapx_cin_transpose_bf16(ptr(x3), B, F, E, ptr(out), out.shape[1], stream()))
+    return out
+
+
+def cin_dx3_bf16(dx0t, B, E, F):
+    """fp32 dx0t [B*E, F] -> bf16 dx3 [B,F,E] (one rounding)."""
+    require_gpu(dx0t)
+    if dx0t.dtype != torch.float32 or dx0t.shape != (B * E, F):
+        raise TypeError("cin_dx3_bf16: dx0t is fp32 [B*E, F]")
+    out = torch.empty(B, F, E, dtype=BF16, device=dx0t.device)
+    check(lib.mapx_cin_dx3_bf16(ptr(dx0t), B, E, F, ptr(out), stream()))
+    return out
+
+
+def cin_fused_fwd(x0t, F, xi, H, w, bias):
+    """-> y bf16 [R, pad8(U)]: y[r, o] = bias[o] + sum_{h,m} w[o, h*H+m] * bf16(x0t[r,h] * xi[r,m]); w bf16 [U, F*H(, 1)]."""
+    _cin_bf16(x0t, xi, w)
+    require_gpu(bias)
+    U, R = w.shape[0], x0t.shape[0]
+    if w.numel() != U * F * H or xi.shape[0] != R or bias.dtype != torch.float32 or bias.numel() != U:
+        raise ValueError("cin_fused_fwd: w [U, F*H], bias fp32 [U], xi [R, pad8(H)]")
+    y = torch.empty(R, pad8(U), dtype=BF16, device=x0t.device)
+    with _timed("cin_fused_fwd", 2.0 * R * (x0t.shape[1] + xi.shape[1] + y.shape[1])):
+        check(lib.mapx_cin_fused_fwd(ptr(x0t), x0t.shape[1], F, ptr(xi), xi.shape[1], H, ptr(w), ptr(bias), U, R, ptr(y),
+                                     y.shape[1], stream()))
+    return y
+
+
+def cin_fused_bwd_input(dy, U, w, x0t, F, xi, H, dx0t, accumulate_x0, first_layer=False, gpool=None, E=1):
+    """dx0t (fp32 [R,F]) is written or accumulated in place; -> dy_prev bf16 [R, pad8(H)] = bf16(dxi + gpool[r // E])
+    (`gpool`: bf16 [B, H] column slice or None), or None for layer 1 (whose dxi joins dx0t)."""
+    _cin_bf16(dy, w, x0t, xi, gpool)
+    require_gpu(dx0t)
+    R = x0t.shape[0]
+    if dx0t.dtype != torch.float32 or dx0t.shape != (R, F) or w.numel() != U * F * H or dy.shape[0] != R:
+        raise ValueError("cin_fused_bwd_input: dx0t fp32 [R, F], w [U, F*H], dy [R, pad8(U)]")
+    if gpool is not None and (gpool.stride(1) != 1 or gpool.shape != (R // E, H)):
+        raise ValueError("cin_fused_bwd_input: gpool [R / E, H] with unit column stride")
+    prev = None if first_layer else torch.empty(R, pad8(H), dtype=BF16, device=x0t.device)
+    with _timed("cin_fused_bwd_input", 2.0 * R * (dy.shape[1] + x0t.shape[1] + 2 * xi.shape[1]) + 8.0 * R * F):
+        check(lib.mapx_cin_fused_bwd_input(ptr(dy), dy.shape[1], U, ptr(w), ptr(x0t), x0t.shape[1], F, ptr(xi),
+                                           xi.shape[1], H, R, ptr(dx0t), int(accumulate_x0), int(first_layer),
+                                           None if gpool is None else gpool.data_ptr(),
+                                           0 if gpool is None else gpool.stride(0), E, ptr(prev),
+                                           0 if prev is None else prev.shape[1], stream()))
+    return prev
+
+
+def cin_fused_bwd_weight(dy, U, x0t, F, xi, H, out=None):
+    """-> dw fp32 [U, F*H] = sum_r dy[r, :U]^T bf16(x0t[r,h] * xi[r,m]) (into `out`, any shape of U*F*H contiguous
+    floats: the optimizer's gradient slot); slab partials added in slab order."""
+    _cin_bf16(dy, x0t, xi)
+    R = x0t.shape[0]
+    dw = out if out is not None else torch.empty(U, F * H, dtype=torch.float32, device=dy.device)
+    if dw.dtype != torch.float32 or dw.numel() != U * F * H or dy.shape[0] != R or xi.shape[0] != R:
+        raise ValueError("cin_fused_bwd_weight: dw fp32 with U*F*H elements, dy / xi with R rows")
+    require_gpu(dw)
+    nb = lib.mapx_cin_fused_bwd_weight_workspace_bytes(F, H, U, R)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dy.device)
+    with _timed("cin_fused_bwd_weight", 2.0 * R * (dy.shape[1] + x0t.shape[1] + xi.shape[1]) + 2.0 * nb):
+        check(lib.mapx_cin_fused_bwd_weight(ptr(dy), dy.shape[1], U, ptr(x0t), x0t.shape[1], F, ptr(xi), xi.shape[1], H,
+                                            R, ptr(ws), ws.numel(), ptr(dw), stream()))
+    return dw
+
+
+def cin_pool_fwd_bf16(y, U, B, E, out):
+    """out[b, :U] = bf16(sum_d y[(b,d), :U]) (fp32 sum); `out`: a bf16 column slice."""
+    _cin_bf16(y, out)
+    if out.stride(1) != 1 or out.shape != (B, U) or y.shape[0] != B * E:
+        raise ValueError("cin_pool_fwd_bf16: out [B, U] with unit column stride, y [B*E, pad8(U)]")
+    check(lib.mapx_cin_pool_fwd_bf16(ptr(y), y.shape[1], B, E, U, out.data_ptr(), out.stride(0), stream()))
+    return out
+
+
+def cin_pool_bwd_bf16(g, B, E):
+    """g bf16 [B, U] (column slice) -> dy [B*E, pad8(U)]: every row of a sample gets its pooled gradient."""
+    _cin_bf16(g)
+    U = g.shape[1]
+    if g.stride(1) != 1 or g.shape[0] != B:
+        raise ValueError("cin_pool_bwd_bf16: g [B, U] with unit column stride")
+    dy = torch.empty(B * E, pad8(U), dtype=BF16, device=g.device)
+    check(lib.mapx_cin_pool_bwd_bf16(g.data_ptr(), g.stride(0), B, E, U, ptr(dy), dy.shape[1], stream()))
+    return dy
+
+
 # --------------------------------------------------------------------------- DeepFM terms
 def lr_sum(ids, w, validate=False):
     """out[b] = sum_f w[ids[b,f]]   (reference models.py:137-140, before the bias)."""

@@ -18,6 +18,40 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (puts map-code_amd on the path)
 
 
+def build(args, device):
+    """bench.build's configuration, table and Trainer with the model from models.build_backbone, which also builds the
+    modes BaseModel.from_config still refuses (xDeepFM with --dtype bf16)."""
+    import numpy as np
+    from mapx.arguments import Config, TrainingArguments
+    from mapx.dataset import OurDataset, synth_table
+    from mapx.models import build_backbone
+    from mapx.trainer import Trainer
+    wl = bench.WORKLOADS[args.workload]
+    F, V = wl["F"], wl["V"]
+    ids, labels, _, _ = synth_table(args.rows, F, V, seed=42, uniform=args.uniform)
+    feat_count = torch.from_numpy(np.bincount(ids.reshape(-1), minlength=V).astype(np.float32))
+    pt = args.pt
+    cfg = Config(model_name=args.model, data_dir=None, input_size=V, num_fields=F, embed_size=16,
+                 embed_dropout_rate=0.0, embed_norm=False, hidden_size=1000, num_hidden_layers=3,
+                 hidden_act="relu", hidden_dropout_rate=0.0, num_cross_layers=3, pt_neg_num=25,
+                 proj_size=32, pretrain=pt != "CTR", pt_type="MFP" if pt == "CTR" else pt, RFD_replace="Unigram",
+                 feat_count=feat_count, seed=42, rank=0, compute_dtype="bf16" if args.dtype == "bf16" else "fp32",
+                 cin_layer_units="50,50", use_lr=False, num_attn_layers=2, attn_size=40, num_attn_heads=1,
+                 attn_probs_dropout_rate=0.0, res_conn=False, attn_scale=False, dnn_size=1000, num_dnn_layers=0,
+                 dnn_act="relu", dnn_drop=0.0)
+    torch.manual_seed(42)
+    model = build_backbone(cfg)
+    steps_per_epoch = max(1, args.rows // args.batch)
+    need = 2 * (args.preroll + args.warmup + args.steps + 64)
+    targs = TrainingArguments(output_dir="/tmp/mapx_bench", per_gpu_train_batch_size=args.batch,
+                              per_gpu_eval_batch_size=args.batch, learning_rate=1e-3, lr_sched="cosine",
+                              weight_decay=5e-2, num_train_epochs=max(3, -(-need // steps_per_epoch)),
+                              pretrain=pt != "CTR", pt_type="MFP" if pt == "CTR" else pt, sampling_method="randint",
+                              mask_ratio=0.3, seed=42)
+    targs._device = device
+    return Trainer(model, cfg, targs, OurDataset(ids, labels), OurDataset(ids[:args.batch], labels[:args.batch]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pt", default="RFD", choices=["MFP", "RFD", "CTR"])
@@ -35,7 +69,7 @@ def main():
     a.uniform = False
     device = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    tr, cfg, ids, labels, _ = bench.build(a, device, 0)
+    tr = build(a, device)
     tr.args.sampling_method = a.sampling
     train = tr._begin("bench")
     gen = tr._generator()
