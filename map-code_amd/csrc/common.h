@@ -151,6 +151,7 @@ __device__ inline float dot4(const float4& a, const float4& b, float s) {
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 // The C ABI's mapx_bf16 (a uint16_t) as the device element type.
 inline const bf16_t* hc(const mapx_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
@@ -167,6 +168,13 @@ __device__ inline void store4(bf16_t* __restrict__ p, const float4& v) {
   bf16x4_t o;
   o[0] = (bf16_t)v.x; o[1] = (bf16_t)v.y; o[2] = (bf16_t)v.z; o[3] = (bf16_t)v.w;
   *reinterpret_cast<bf16x4_t*>(p) = o;
+}
+// Eight fp32 values as one 16-byte bf16 chunk (what a kernel with 8 columns per lane stores).
+__device__ inline bf16x8_t bf16x8_of(const float4& a, const float4& b) {
+  bf16x8_t o;
+  o[0] = (bf16_t)a.x; o[1] = (bf16_t)a.y; o[2] = (bf16_t)a.z; o[3] = (bf16_t)a.w;
+  o[4] = (bf16_t)b.x; o[5] = (bf16_t)b.y; o[6] = (bf16_t)b.z; o[7] = (bf16_t)b.w;
+  return o;
 }
 
 }  // namespace mapx

@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(256) emb_gather_kernel(const int64_t* __restri
 // The gather of a training step without a catch-up pass in front of it (lazy_adam.h: LazyRows): last[id] is read beside
 // the row and a stale row's missing zero-gradient updates are replayed in registers from its m | v record — the bits
 // the catch-up pass would have stored — and nothing is written; the gradient update that ends the step is the row's
-// one read-modify-write.  OUT = float or __bf16 (8 columns per thread then).
+// one read-modify-write.  OUT = float or bf16_t (8 columns per thread then).
 template <class OUT>
 __global__ void __launch_bounds__(256) emb_gather_lazy_kernel(const int64_t* __restrict__ ids, int64_t n,
                                                               const float* __restrict__ table, int64_t V, int E,
@@ -80,11 +80,7 @@ __global__ void __launch_bounds__(256) emb_gather_lazy_kernel(const int64_t* __r
       }
     }
     if constexpr (kHalf) {
-      typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-      bf16x8_t o;
-      o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)a.z; o[3] = (__bf16)a.w;
-      o[4] = (__bf16)b.x; o[5] = (__bf16)b.y; o[6] = (__bf16)b.z; o[7] = (__bf16)b.w;
-      *reinterpret_cast<bf16x8_t*>(out + row * E + c) = o;
+      *reinterpret_cast<bf16x8_t*>(out + row * E + c) = bf16x8_of(a, b);
     } else {
       *reinterpret_cast<float4*>(out + row * E + c) = a;
       amx = amax4(amx, a.x, a.y, a.z, a.w);
@@ -97,8 +93,7 @@ __global__ void __launch_bounds__(256) emb_gather_lazy_kernel(const int64_t* __r
 // table stays fp32).  8 columns per thread: two 16-B table reads, one 16-B store.
 __global__ void __launch_bounds__(256) emb_gather_bf16_kernel(const int64_t* __restrict__ ids, int64_t n,
                                                               const float* __restrict__ table, int64_t V, int E,
-                                                              __bf16* __restrict__ out, int* __restrict__ err) {
-  typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+                                                              bf16_t* __restrict__ out, int* __restrict__ err) {
   const int per_row = E / 8;
   const int64_t total = n * per_row;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
@@ -113,10 +108,7 @@ __global__ void __launch_bounds__(256) emb_gather_bf16_kernel(const int64_t* __r
       a = *reinterpret_cast<const float4*>(table + id * E + c);
       b = *reinterpret_cast<const float4*>(table + id * E + c + 4);
     }
-    bf16x8_t o;
-    o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)a.z; o[3] = (__bf16)a.w;
-    o[4] = (__bf16)b.x; o[5] = (__bf16)b.y; o[6] = (__bf16)b.z; o[7] = (__bf16)b.w;
-    *reinterpret_cast<bf16x8_t*>(out + row * E + c) = o;
+    *reinterpret_cast<bf16x8_t*>(out + row * E + c) = bf16x8_of(a, b);
   }
 }
 
@@ -193,13 +185,13 @@ extern "C" int mapx_emb_gather_fwd_bf16(const int64_t* ids, int64_t n, const flo
   if (lazy_opt) {
     mapx::LazyRows lz;
     if (!mapx::lazy_rows_from(lazy_opt, E, "emb_gather_fwd_bf16", &lz)) return MAPX_EINVAL;
-    hipLaunchKernelGGL(mapx::emb_gather_lazy_kernel<__bf16>, dim3(mapx::grid_for(n * (E / 8), 256)), dim3(256), 0, stream,
-                       ids, n, table, V, E, reinterpret_cast<__bf16*>(out), err_flag, (mapx::amax_rec*)nullptr,
+    hipLaunchKernelGGL(mapx::emb_gather_lazy_kernel<mapx::bf16_t>, dim3(mapx::grid_for(n * (E / 8), 256)), dim3(256), 0, stream,
+                       ids, n, table, V, E, mapx::hm(out), err_flag, (mapx::amax_rec*)nullptr,
                        (const int32_t*)nullptr, lz);
     return mapx::check_launch("emb_gather_fwd_bf16");
   }
   hipLaunchKernelGGL(mapx::emb_gather_bf16_kernel, dim3(mapx::grid_for(n * (E / 8), 256)), dim3(256), 0, stream, ids, n,
-                     table, V, E, reinterpret_cast<__bf16*>(out), err_flag);
+                     table, V, E, mapx::hm(out), err_flag);
   return mapx::check_launch("emb_gather_fwd_bf16");
 }
 

@@ -1,9 +1,10 @@
-// Dense-trunk entry points (mapx_gemm_f32) and the small kernels around the GEMMs: the grouped encoder's slot
-// layout, deferred slab / partial sums, column sums and the elementwise backward pieces of the ReLU and
-// cross layers.  The products themselves are csrc/gemm_x3.hip (fp32 operands as three bf16 pieces on the
-// bf16 matrix cores) and csrc/gemm_bf16.hip (bf16 mode).  Round 1's fp32-MFMA family (v_mfma_f32_32x32x2_f32,
-// incl. the LDS-DMA deep-K weight-gradient kernel) lived here until round 3; it was the slower of the two
-// (92 vs 130 TF class average) and ran nowhere on the default path, so it was removed rather than kept untested.
+// Dense-trunk entry points of the fp32 products (mapx_gemm_f32, its fused-backward and batched forms) and the grouped
+// encoder: its slot layout kernel and entries.  The products themselves are csrc/gemm_x3.hip (fp32 operands as three
+// bf16 pieces on the bf16 matrix cores) and gemm_h2*.hip; bf16 mode is csrc/gemm_bf16.hip; the column sums, deferred
+// sums and elementwise backward pieces around them are csrc/colsum.hip.  Round 1's fp32-MFMA family
+// (v_mfma_f32_32x32x2_f32, incl. the LDS-DMA deep-K weight-gradient kernel) lived here until round 3; it was the
+// slower of the two (92 vs 130 TF class average) and ran nowhere on the default path, so it was removed rather than
+// kept untested.
 //
 //   C[m,n] = epilogue( sum_k A(m,k) * B(k,n) )
 //   A_KC : A(m,k) = A[m*lda + k]  (k contiguous)      else A(m,k) = A[k*lda + m]
@@ -125,168 +126,8 @@ __global__ void __launch_bounds__(kLayoutMwThreads) enc_group_layout_mw_kernel(
   }
 }
 
-// Deferred slab sums: dst[i] = sum_s src[s*stride + i] for up to kMaxSumTasks independent
-// tasks in ONE launch (split-K slabs of the weight-gradient GEMMs and the row-chunk partials
-// of the bias-gradient column sums of a whole backward pass; 14 tiny launches -> 1).
-constexpr int kMaxSumTasks = 32;
-struct SumTasks {
-  mapx_sum_task t[kMaxSumTasks];
-};
-__global__ void __launch_bounds__(256) sum_tasks_kernel(SumTasks tasks) {
-  const mapx_sum_task tk = tasks.t[blockIdx.y];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tk.n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    int s = 0;
-    // The kernel is a latency chain (a column has one thread, a task a few blocks): 32 loads in flight per
-    // round trip — 128 row-chunk partials of a bias gradient are 4 round trips, not 16 — added in slab order.
-    for (; s + 32 <= tk.nsplit; s += 32) {
-      float x[32];
-#pragma unroll
-      for (int u = 0; u < 32; ++u) x[u] = tk.src[(s + u) * tk.stride + i];
-#pragma unroll
-      for (int u = 0; u < 32; ++u) v += x[u];
-    }
-    for (; s + 8 <= tk.nsplit; s += 8) {
-      float x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = tk.src[(s + u) * tk.stride + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v += x[u];
-    }
-    for (; s < tk.nsplit; ++s) v += tk.src[s * tk.stride + i];
-    tk.dst[i] = v;
-  }
-}
-
-// column sums of X [M,N] (bias gradients): stage 1 = 32 row chunks -> partial[32][N]
-constexpr int kColChunks = 128;
-__global__ void __launch_bounds__(256) colsum_stage1_kernel(const float* __restrict__ x, int64_t ld,
-                                                            int M, int N, float* __restrict__ part) {
-  // block = 64 columns x 4 row lanes
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int rl = threadIdx.x >> 6;
-  const int rows_per = (M + kColChunks - 1) / kColChunks;
-  const int r0 = blockIdx.y * rows_per;
-  const int r1 = (r0 + rows_per < M) ? r0 + rows_per : M;
-  float v = 0.f;
-  if (c < N) {
-#pragma unroll 8                 // eight loads in flight, added in the same order (a tall narrow matrix — xDeepFM's
-    for (int r = r0 + rl; r < r1; r += 4) v += x[(int64_t)r * ld + c];   // [65536, 50] — is one block per chunk: 51 us)
-  }
-  __shared__ float s[4][64];
-  s[rl][threadIdx.x & 63] = v;
-  __syncthreads();
-  if (rl == 0 && c < N)
-    part[(int64_t)blockIdx.y * N + c] = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] +
-                                        s[3][threadIdx.x];
-}
-__global__ void __launch_bounds__(256) colsum_stage2_kernel(const float* __restrict__ part, int N,
-                                                            float* __restrict__ out) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= N) return;
-  float v = 0.f;
-  for (int i = 0; i < kColChunks; ++i) v += part[(int64_t)i * N + c];
-  out[c] = v;
-}
-
-// CrossNetV2 backward, elementwise part of one layer (layers.py:200 differentiated):
-//   t = g * x0 (feeds the dXi / dW GEMMs and db),  dx0 (+)= g * u
-__global__ void __launch_bounds__(256) cross_bwd_pre_kernel(const float* __restrict__ g,
-                                                            const float* __restrict__ x0,
-                                                            const float* __restrict__ u, int64_t n4,
-                                                            float* __restrict__ t,
-                                                            float* __restrict__ dx0, int accumulate) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    const float4 xv = reinterpret_cast<const float4*>(x0)[i];
-    const float4 uv = reinterpret_cast<const float4*>(u)[i];
-    reinterpret_cast<float4*>(t)[i] = make_float4(gv.x * xv.x, gv.y * xv.y, gv.z * xv.z, gv.w * xv.w);
-    float4 d = make_float4(gv.x * uv.x, gv.y * uv.y, gv.z * uv.z, gv.w * uv.w);
-    if (accumulate) {
-      const float4 o = reinterpret_cast<const float4*>(dx0)[i];
-      d.x += o.x; d.y += o.y; d.z += o.z; d.w += o.w;
-    }
-    reinterpret_cast<float4*>(dx0)[i] = d;
-  }
-}
-
-// Elementwise backward steps fused with the bias-gradient column sum (one pass over the
-// data instead of elementwise kernel + colsum stage 1):
-//   OP 0 (ReLU layer):   dz = y > 0 ? dy : 0                      db = colsum(dz)
-//   OP 1 (cross layer):  t = g * x0 ; dx0 (+)= g * u (+ g)        db = colsum(t)
-//                        accumulate bit 0: add to the dx0 already there; bit 1: also add g
-// Block = CL column lanes (x float4) x 256 / CL row lanes over one of kColChunks row chunks; stage 2 adds the
-// chunks.  CL = 64 or 32, whichever wastes fewer lanes on the last column block (N = 368: 92 float4 columns
-// are 2 blocks of 64 with 28 % of the lanes idle, or 3 blocks of 32 with 4 %).
-template <int OP, int CL>
-__global__ void __launch_bounds__(256) ew_colsum_kernel(const float* __restrict__ a, int64_t lda,
-                                                        const float* __restrict__ b, int64_t ldb,
-                                                        const float* __restrict__ c, int M, int N,
-                                                        float* __restrict__ o1, float* __restrict__ o2,
-                                                        int accumulate, float* __restrict__ part,
-                                                        amax_rec* __restrict__ amax_o1, const int32_t* __restrict__ epoch) {
-  // CL lanes x float4 columns per block row; RL row lanes; N % 4 == 0, lda % 4 == 0 (host-checked)
-  constexpr int RL = 256 / CL;
-  const int cl = threadIdx.x % CL;
-  const int col = (blockIdx.x * CL + cl) * 4;
-  const int rl = threadIdx.x / CL;
-  const int rows_per = (M + kColChunks - 1) / kColChunks;
-  const int r0 = blockIdx.y * rows_per;
-  const int r1 = (r0 + rows_per < M) ? r0 + rows_per : M;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  uint32_t amx = 0;                     // max |o1| (dz or t) for the products that read it next (amax.h)
-  if (col < N) {
-#pragma unroll 4
-    for (int r = r0 + rl; r < r1; r += RL) {
-      const int64_t i = ((int64_t)r * N + col) >> 2;
-      const float4 av = reinterpret_cast<const float4*>(a)[((int64_t)r * lda + col) >> 2];   // a may be a column slice
-      const float4 bv = reinterpret_cast<const float4*>(b)[((int64_t)r * ldb + col) >> 2];
-      if (OP == 0) {
-        const float4 dz = make_float4(bv.x > 0.f ? av.x : 0.f, bv.y > 0.f ? av.y : 0.f,
-                                      bv.z > 0.f ? av.z : 0.f, bv.w > 0.f ? av.w : 0.f);
-        reinterpret_cast<float4*>(o1)[i] = dz;
-        amx = amax4(amx, dz.x, dz.y, dz.z, dz.w);
-        v.x += dz.x; v.y += dz.y; v.z += dz.z; v.w += dz.w;
-      } else {
-        const float4 cv = reinterpret_cast<const float4*>(c)[i];
-        const float4 t = make_float4(av.x * bv.x, av.y * bv.y, av.z * bv.z, av.w * bv.w);
-        float4 d = make_float4(av.x * cv.x, av.y * cv.y, av.z * cv.z, av.w * cv.w);
-        if (accumulate & 1) {
-          const float4 o = reinterpret_cast<const float4*>(o2)[i];
-          d.x += o.x; d.y += o.y; d.z += o.z; d.w += o.w;
-        }
-        if (accumulate & 2) {   // first cross layer: Xi IS X0, its gradient g joins the X0 total
-          d.x += av.x; d.y += av.y; d.z += av.z; d.w += av.w;
-        }
-        reinterpret_cast<float4*>(o1)[i] = t;
-        amx = amax4(amx, t.x, t.y, t.z, t.w);
-        reinterpret_cast<float4*>(o2)[i] = d;
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-      }
-    }
-  }
-  if (amax_o1) amax_publish_block(amax_o1, amx, epoch);
-  __shared__ float4 s[RL][CL];
-  s[rl][cl] = v;
-  __syncthreads();
-  if (rl == 0 && col < N) {
-    float4 t = s[0][cl];
-#pragma unroll
-    for (int k = 1; k < RL; ++k) {       // fixed order: bit-reproducible
-      const float4 q = s[k][cl];
-      t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w;
-    }
-    *reinterpret_cast<float4*>(part + (int64_t)blockIdx.y * N + col) = t;
-  }
-}
-
-// 32 instead of 64 column lanes per block when that leaves fewer lanes of the last column block idle
-static inline bool ew_narrow_lanes(int N) {
-  const int c4 = (N + 3) / 4;
-  return ((c4 + 31) / 32) * 32 < ((c4 + 63) / 64) * 64;
-}
+// colsum.hip: dst[i] = sum_s src[s*stride + i] for each task, one launch (here: the slabs of a batched split-K product)
+void sum_tasks_launch(const mapx_sum_task* tasks, int ntasks, hipStream_t stream);
 
 // gemm_x3.hip: the same product on the bf16 matrix cores (three bf16 pieces per fp32 operand, six MFMAs)
 int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, int64_t lda, const float* B,
@@ -401,14 +242,14 @@ extern "C" int mapx_gemm_f32_batched(int count, int a_kc, int b_kc, int M, int N
                                    nullptr, 0, nullptr, 0, nsplit, -1, ws, ws_bytes, &got, stream, &ex);
   if (st != MAPX_OK) return st;
   if (got > 1) {            // slabs of problem z: ws + z * nsplit * M * N, `got` of them in use
-    SumTasks t;
-    memset(&t, 0, sizeof(t));
+    mapx_sum_task t[4];
+    memset(t, 0, sizeof(t));
     for (int z = 0; z < count; ++z) {
-      t.t[z].dst = C[z];
-      t.t[z].src = static_cast<const float*>(ws) + (int64_t)z * nsplit * M * N;
-      t.t[z].stride = (int64_t)M * N; t.t[z].n = (int64_t)M * N; t.t[z].nsplit = got;
+      t[z].dst = C[z];
+      t[z].src = static_cast<const float*>(ws) + (int64_t)z * nsplit * M * N;
+      t[z].stride = (int64_t)M * N; t[z].n = (int64_t)M * N; t[z].nsplit = got;
     }
-    hipLaunchKernelGGL(sum_tasks_kernel, dim3(96, count), dim3(256), 0, stream, t);
+    sum_tasks_launch(t, count, stream);
   }
   return check_launch("gemm_f32_batched");
 }
@@ -478,99 +319,4 @@ extern "C" int mapx_enc_grouped_dw(const float* dh_slots, const float* final_act
     MAPX_HIP(enc_grouped_dw_x3_launch(g, F, stream));
   }
   return check_launch("enc_grouped_dw");
-}
-
-extern "C" size_t mapx_colsum_workspace_bytes(int N) {
-  return (size_t)mapx::kColChunks * N * sizeof(float);
-}
-
-extern "C" int mapx_sum_tasks(const mapx_sum_task* tasks_host, int ntasks, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(ntasks >= 0 && ntasks <= kMaxSumTasks, "sum_tasks: at most %d tasks per call", kMaxSumTasks);
-  if (ntasks == 0) return MAPX_OK;
-  MAPX_REQUIRE(tasks_host, "sum_tasks: null task list");
-  SumTasks t;
-  memset(&t, 0, sizeof(t));
-  for (int i = 0; i < ntasks; ++i) {
-    MAPX_REQUIRE(tasks_host[i].dst && tasks_host[i].src && tasks_host[i].nsplit >= 1 && tasks_host[i].n >= 0,
-                 "sum_tasks: bad task %d", i);
-    t.t[i] = tasks_host[i];
-  }
-  hipLaunchKernelGGL(sum_tasks_kernel, dim3(96, ntasks), dim3(256), 0, stream, t);
-  return check_launch("sum_tasks");
-}
-
-extern "C" int mapx_colsum_chunks(void) { return mapx::kColChunks; }
-
-extern "C" int mapx_colsum(const float* x, int64_t ld, int M, int N, float* out, void* ws,
-                           size_t ws_bytes, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(x && M >= 0 && N > 0, "colsum: bad arguments");
-  if (!ws || ws_bytes < mapx_colsum_workspace_bytes(N)) {
-    set_error("colsum: workspace too small");
-    return MAPX_EWORKSPACE;
-  }
-  float* part = static_cast<float*>(ws);
-  hipLaunchKernelGGL(colsum_stage1_kernel, dim3((N + 63) / 64, kColChunks), dim3(256), 0, stream, x,
-                     ld, M, N, part);
-  if (out)   // out == NULL: the caller sums the kColChunks partial rows later (mapx_sum_tasks)
-    hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, out);
-  return check_launch("colsum");
-}
-
-extern "C" int mapx_relu_mask_colsum(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, int M, int N,
-                                     float* dz, float* db, void* ws, size_t ws_bytes, void* amax_out_opt,
-                                     hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(dy && y && dz && M >= 0 && N > 0, "relu_mask_colsum: bad arguments");
-  MAPX_REQUIRE(N % 4 == 0 && ld_dy % 4 == 0 && ld_dy >= N && (uintptr_t)dy % 16 == 0 && ld_y % 4 == 0 &&
-                   ld_y >= N && (uintptr_t)y % 16 == 0,
-               "relu_mask_colsum: N, ld_dy, ld_y %% 4 != 0 or dy / y not 16-byte aligned");
-  if (!ws || ws_bytes < mapx_colsum_workspace_bytes(N)) {
-    set_error("relu_mask_colsum: workspace too small");
-    return MAPX_EWORKSPACE;
-  }
-  float* part = static_cast<float*>(ws);
-  if (ew_narrow_lanes(N))
-    hipLaunchKernelGGL((ew_colsum_kernel<0, 32>), dim3((N + 127) / 128, kColChunks), dim3(256), 0, stream, dy, ld_dy, y,
-                       ld_y, (const float*)nullptr, M, N, dz, (float*)nullptr, 0, part, static_cast<amax_rec*>(amax_out_opt),
-                       amax_epoch_ptr());
-  else
-    hipLaunchKernelGGL((ew_colsum_kernel<0, 64>), dim3((N + 255) / 256, kColChunks), dim3(256), 0, stream, dy, ld_dy, y,
-                       ld_y, (const float*)nullptr, M, N, dz, (float*)nullptr, 0, part, static_cast<amax_rec*>(amax_out_opt),
-                       amax_epoch_ptr());
-  if (db) hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, db);
-  return check_launch("relu_mask_colsum");
-}
-
-extern "C" int mapx_cross_bwd_pre_colsum(const float* g, int64_t ld_g, const float* x0, const float* u, int M, int N,
-                                         float* t, float* dx0, int accumulate, float* db, void* ws,
-                                         size_t ws_bytes, void* amax_out_opt, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(g && x0 && u && t && dx0 && M >= 0 && N > 0, "cross_bwd_pre_colsum: bad arguments");
-  MAPX_REQUIRE(N % 4 == 0 && ld_g % 4 == 0 && ld_g >= N && (uintptr_t)g % 16 == 0,
-               "cross_bwd_pre_colsum: N, ld_g %% 4 != 0 or g not 16-byte aligned");
-  if (!ws || ws_bytes < mapx_colsum_workspace_bytes(N)) {
-    set_error("cross_bwd_pre_colsum: workspace too small");
-    return MAPX_EWORKSPACE;
-  }
-  float* part = static_cast<float*>(ws);
-  if (ew_narrow_lanes(N))
-    hipLaunchKernelGGL((ew_colsum_kernel<1, 32>), dim3((N + 127) / 128, kColChunks), dim3(256), 0, stream, g, ld_g, x0,
-                       (int64_t)N, u, M, N, t, dx0, accumulate, part, static_cast<amax_rec*>(amax_out_opt), amax_epoch_ptr());
-  else
-    hipLaunchKernelGGL((ew_colsum_kernel<1, 64>), dim3((N + 255) / 256, kColChunks), dim3(256), 0, stream, g, ld_g, x0,
-                       (int64_t)N, u, M, N, t, dx0, accumulate, part, static_cast<amax_rec*>(amax_out_opt), amax_epoch_ptr());
-  if (db) hipLaunchKernelGGL(colsum_stage2_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, db);
-  return check_launch("cross_bwd_pre_colsum");
-}
-
-extern "C" int mapx_cross_bwd_pre(const float* g, const float* x0, const float* u, int64_t n,
-                                  float* t, float* dx0, int accumulate, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(g && x0 && u && t && dx0 && n >= 0 && n % 4 == 0, "cross_bwd_pre: bad arguments");
-  if (n == 0) return MAPX_OK;
-  hipLaunchKernelGGL(cross_bwd_pre_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, g, x0, u,
-                     n / 4, t, dx0, accumulate);
-  return check_launch("cross_bwd_pre");
 }

@@ -4,7 +4,8 @@
 // v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate).  Operands are bf16 in HBM (activations are
 // stored in bf16 by the producing kernel's epilogue; weights are bf16 shadows of the fp32 master
 // weights, refreshed by the optimizer kernel), accumulation, bias / ReLU / cross epilogues and
-// every weight gradient are fp32.
+// every weight gradient are fp32.  This file is the product alone: the mode's column sums, elementwise backward
+// pieces and casts are colsum.hip, the split-K combine is splitk_reduce.h (shared with gemm_x3.hip).
 //
 //   C[m,n] = epilogue( sum_k A(m,k) * B(k,n) )
 //
@@ -29,13 +30,11 @@
 // round trip), LDS stores one K-step ahead.
 #include "../../include/mapx_hip.h"
 #include "common.h"
+#include "splitk_reduce.h"
 #include <utility>
 
 namespace mapx {
 
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -121,18 +120,18 @@ struct OperandH {
   }
 
   // fragment of k16-step s4 (k = 16 s4 + 8 (lane >> 5) + j) for this wave's tile t
-  __device__ static inline bf16x8 frag1(const bf16_t* __restrict__ s, int base, int lane, int s4, int t) {
+  __device__ static inline bf16x8_t frag1(const bf16_t* __restrict__ s, int base, int lane, int s4, int t) {
     const int l31 = lane & 31, kh = lane >> 5;
-    if (KC) return *reinterpret_cast<const bf16x8*>(s + (base + 32 * t + l31) * LD + 16 * s4 + 8 * kh);
+    if (KC) return *reinterpret_cast<const bf16x8_t*>(s + (base + 32 * t + l31) * LD + 16 * s4 + 8 * kh);
     // transposing read: lane 4q+p of a 16-lane group addresses block row q, columns 4p..4p+3, and
     // receives column (lane & 15) of the block's 4 rows
     const int q = (lane >> 2) & 3, p = lane & 3, half = (lane >> 4) & 1;
     const bf16_t* a0 = s + (16 * s4 + 8 * kh + q) * LD + base + 32 * t + 16 * half + 4 * p;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(a0));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(a0 + 4 * LD));
+    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a0));
+    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(a0 + 4 * LD));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   }
-  __device__ static inline void frags(const bf16_t* __restrict__ s, int base, int lane, int s4, bf16x8 (&f)[T]) {
+  __device__ static inline void frags(const bf16_t* __restrict__ s, int base, int lane, int s4, bf16x8_t (&f)[T]) {
 #pragma unroll
     for (int t = 0; t < T; ++t) f[t] = frag1(s, base, lane, s4, t);
   }
@@ -184,13 +183,13 @@ __device__ inline void epilogue_rows_h(const GemmHArgs& a, void* __restrict__ C,
           const float4 p1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.aux1) + o1 + 4);
           x1[0] = p0.x; x1[1] = p0.y; x1[2] = p0.z; x1[3] = p0.w; x1[4] = p1.x; x1[5] = p1.y; x1[6] = p1.z; x1[7] = p1.w;
         } else {
-          const bf16x8 p = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(a.aux1) + o1);
+          const bf16x8_t p = *reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const bf16_t*>(a.aux1) + o1);
 #pragma unroll
           for (int e = 0; e < 8; ++e) x1[e] = (float)p[e];
         }
       }
       if (EPI == MAPX_EPI_BIAS_CROSS) {
-        const bf16x8 p = *reinterpret_cast<const bf16x8*>(a.aux2 + o2);
+        const bf16x8_t p = *reinterpret_cast<const bf16x8_t*>(a.aux2 + o2);
 #pragma unroll
         for (int e = 0; e < 8; ++e) x2[e] = (float)p[e];
       }
@@ -217,16 +216,16 @@ __device__ inline void epilogue_rows_h(const GemmHArgs& a, void* __restrict__ C,
         *reinterpret_cast<float4*>(c) = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<float4*>(c + 4) = make_float4(v[4], v[5], v[6], v[7]);
       } else {
-        bf16x8 o;
+        bf16x8_t o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];          // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-        *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(C) + oc) = o;
+        *reinterpret_cast<bf16x8_t*>(reinterpret_cast<bf16_t*>(C) + oc) = o;
       }
       if (EPI == MAPX_EPI_BIAS_CROSS) {
-        bf16x8 o;
+        bf16x8_t o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (bf16_t)u[e];
-        *reinterpret_cast<bf16x8*>(a.out2 + oo) = o;
+        *reinterpret_cast<bf16x8_t*>(a.out2 + oo) = o;
       }
     } else {
 #pragma unroll
@@ -265,7 +264,7 @@ __device__ inline void epilogue_rows_h_vec(const GemmHArgs& a, void* __restrict_
 #pragma unroll
   for (int it0 = 0; it0 < NIT; it0 += U) {
     float4 t0[U], t1[U], q0[U], q1[U];
-    bf16x8 h1[U], h2[U];
+    bf16x8_t h1[U], h2[U];
     bool ok[U];
     int64_t mrow[U];
 #pragma unroll
@@ -281,10 +280,10 @@ __device__ inline void epilogue_rows_h_vec(const GemmHArgs& a, void* __restrict_
           q0[u] = *reinterpret_cast<const float4*>(p);
           q1[u] = *reinterpret_cast<const float4*>(p + 4);
         } else {
-          h1[u] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(a.aux1) + mrow[u] * a.ld1 + ns);
+          h1[u] = *reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const bf16_t*>(a.aux1) + mrow[u] * a.ld1 + ns);
         }
       }
-      if (kAux2) h2[u] = *reinterpret_cast<const bf16x8*>(a.aux2 + mrow[u] * a.ld2 + ns);
+      if (kAux2) h2[u] = *reinterpret_cast<const bf16x8_t*>(a.aux2 + mrow[u] * a.ld2 + ns);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -308,16 +307,16 @@ __device__ inline void epilogue_rows_h_vec(const GemmHArgs& a, void* __restrict_
           *reinterpret_cast<float4*>(c) = make_float4(v[0], v[1], v[2], v[3]);
           *reinterpret_cast<float4*>(c + 4) = make_float4(v[4], v[5], v[6], v[7]);
         } else {
-          bf16x8 o;
+          bf16x8_t o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];
-          *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(C) + mrow[u] * a.ldc + n) = o;
+          *reinterpret_cast<bf16x8_t*>(reinterpret_cast<bf16_t*>(C) + mrow[u] * a.ldc + n) = o;
         }
         if (kAux2) {
-          bf16x8 o;
+          bf16x8_t o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (bf16_t)w[e];
-          *reinterpret_cast<bf16x8*>(a.out2 + mrow[u] * a.ldo2 + n) = o;
+          *reinterpret_cast<bf16x8_t*>(a.out2 + mrow[u] * a.ldo2 + n) = o;
         }
       }
     }
@@ -480,7 +479,7 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmHArgs a, int c_f32, 
   do {                                                                                                 \
     const bf16_t* const As_cur = smem + (CUR) * kBuf;                                                  \
     const bf16_t* const Bs_cur = As_cur + OpA::LDS_ELEMS;                                              \
-    bf16x8 fa[kHBK / 16][WMT], fb[kHBK / 16][WNT];   /* [k16 step][tile]: read two k16 steps ahead of use */ \
+    bf16x8_t fa[kHBK / 16][WMT], fb[kHBK / 16][WNT];   /* [k16 step][tile]: read two k16 steps ahead of use */ \
     OpA::frags(As_cur, abase, lane, 0, fa[0]);                                                         \
     OpB::frags(Bs_cur, bbase, lane, 0, fb[0]);                                                         \
     OpA::frags(As_cur, abase, lane, 1, fa[1]);                                                         \
@@ -538,7 +537,7 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmHArgs a, int c_f32, 
     do {                                                                                                 \
       const bf16_t* const As_cur = smem + (CUR) * kBuf;                                                  \
       const bf16_t* const Bs_cur = As_cur + OpA::LDS_ELEMS;                                              \
-      bf16x8 af[2][WMT], bf[2][WNT];                                                                     \
+      bf16x8_t af[2][WMT], bf[2][WNT];                                                                     \
       OpA::frags(As_cur, abase, lane, 0, af[0]);                                                         \
       OpB::frags(Bs_cur, bbase, lane, 0, bf[0]);                                                         \
       _Pragma("unroll") for (int s4 = 0; s4 < kHBK / 16; ++s4) {                                         \
@@ -632,27 +631,6 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmHArgs a, int c_f32, 
 #undef MAPX_EPI_CASE
 }
 
-// out[i] = sum_s slabs[s][i] in slab order (deterministic split-K combine of the weight gradients)
-__global__ void __launch_bounds__(256) splitk_reduce_h_kernel(const float* __restrict__ slabs, int64_t slab_stride,
-                                                              int nsplit, int64_t n4, float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 v = reinterpret_cast<const float4*>(slabs)[i];
-    for (int s = 1; s < nsplit; ++s) {
-      const float4 x = reinterpret_cast<const float4*>(slabs + s * slab_stride)[i];
-      v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
-    }
-    reinterpret_cast<float4*>(out)[i] = v;
-  }
-}
-__global__ void __launch_bounds__(256) splitk_reduce_h1_kernel(const float* __restrict__ slabs, int64_t slab_stride,
-                                                               int nsplit, int64_t n, float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    for (int s = 0; s < nsplit; ++s) v += slabs[s * slab_stride + i];
-    out[i] = v;
-  }
-}
-
 template <int WMT, int WNT, bool A_KC, bool B_KC, bool VEC, bool WEAVE>
 static hipError_t launch_one_h(const GemmHArgs& a, int nsplit, int c_f32, int aux1_f32, hipStream_t stream) {
   using OpA = OperandH<64 * WMT, WMT, A_KC, VEC>;
@@ -692,170 +670,6 @@ static hipError_t launch_layout_h(GemmHArgs& a, bool vec, int tile, int nsplit, 
   return launch_tile_h<1, 1, A_KC, B_KC>(a, vec, nsplit, c_f32, aux1_f32, stream);
 }
 
-// ---------------------------------------------------------------------------------------------
-// fp32 <-> bf16 conversion of a flat array (weights shadows outside the optimizer, head gradients)
-__global__ void __launch_bounds__(256) cast_f32_bf16_kernel(const float* __restrict__ src, int64_t n,
-                                                            bf16_t* __restrict__ dst) {
-  const int64_t n8 = n / 8;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    bf16x8 o;
-    o[0] = (bf16_t)a.x; o[1] = (bf16_t)a.y; o[2] = (bf16_t)a.z; o[3] = (bf16_t)a.w;
-    o[4] = (bf16_t)b.x; o[5] = (bf16_t)b.y; o[6] = (bf16_t)b.z; o[7] = (bf16_t)b.w;
-    reinterpret_cast<bf16x8*>(dst)[i] = o;
-  }
-  if (blockIdx.x == 0)
-    for (int64_t i = n8 * 8 + threadIdx.x; i < n; i += blockDim.x) dst[i] = (bf16_t)src[i];
-}
-__global__ void __launch_bounds__(256) cast_bf16_f32_kernel(const bf16_t* __restrict__ src, int64_t n,
-                                                            float* __restrict__ dst) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = (float)src[i];
-}
-
-// ---------------------------------------------------------------------------------------------
-// Elementwise backward steps of the bf16 path fused with the bias-gradient column sum (the bf16
-// counterparts of gemm.hip's ew_colsum_kernel; activations bf16, sums fp32):
-//   OP 0 (ReLU layer):   dz = y > 0 ? dy : 0                      db = colsum(dz)
-//   OP 1 (cross layer):  t = g * x0 ; dx0 (+)= g * u (+ g)        db = colsum(t)     (dx0 kept in fp32)
-//   OP 2 (plain):        nothing written                          db = colsum(a)
-// Block = 64 column lanes x 4 row lanes over one of kColChunksH row chunks; a second launch adds the
-// chunks in order (deterministic).  Scalar columns: any N, any leading dimension.
-constexpr int kColChunksH = 128;
-template <int OP>
-__global__ void __launch_bounds__(256) ew_colsum_h_kernel(const bf16_t* __restrict__ a, int64_t lda,
-                                                          const bf16_t* __restrict__ b, int64_t ldb,
-                                                          const bf16_t* __restrict__ c, int64_t ldc, int M, int N,
-                                                          bf16_t* __restrict__ o1, float* __restrict__ o2,
-                                                          int accumulate, float* __restrict__ part) {
-  const int col = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2;      // 2 columns per lane (one dword of bf16)
-  const int rl = threadIdx.x >> 6;
-  const int rows_per = (M + kColChunksH - 1) / kColChunksH;
-  const int r0 = blockIdx.y * rows_per;
-  const int r1 = (r0 + rows_per < M) ? r0 + rows_per : M;
-  float v0 = 0.f, v1 = 0.f;
-  const bool in0 = col < N, in1 = col + 1 < N;
-  if (in0) {
-    for (int r = r0 + rl; r < r1; r += 4) {
-      const float a0 = (float)a[(int64_t)r * lda + col], a1 = in1 ? (float)a[(int64_t)r * lda + col + 1] : 0.f;
-      if (OP == 2) {
-        v0 += a0; v1 += a1;
-      } else if (OP == 0) {
-        const float y0 = (float)b[(int64_t)r * ldb + col], y1 = in1 ? (float)b[(int64_t)r * ldb + col + 1] : 0.f;
-        const float d0 = y0 > 0.f ? a0 : 0.f, d1 = y1 > 0.f ? a1 : 0.f;
-        o1[(int64_t)r * N + col] = (bf16_t)d0;
-        if (in1) o1[(int64_t)r * N + col + 1] = (bf16_t)d1;
-        v0 += d0; v1 += d1;
-      } else {
-        const float x0 = (float)b[(int64_t)r * ldb + col], x1 = in1 ? (float)b[(int64_t)r * ldb + col + 1] : 0.f;
-        const float u0 = (float)c[(int64_t)r * ldc + col], u1 = in1 ? (float)c[(int64_t)r * ldc + col + 1] : 0.f;
-        const bf16_t t0 = (bf16_t)(a0 * x0), t1 = (bf16_t)(a1 * x1);
-        float d0 = a0 * u0, d1 = a1 * u1;
-        if (accumulate & 1) { d0 += o2[(int64_t)r * N + col]; if (in1) d1 += o2[(int64_t)r * N + col + 1]; }
-        if (accumulate & 2) { d0 += a0; d1 += a1; }
-        o1[(int64_t)r * N + col] = t0;
-        o2[(int64_t)r * N + col] = d0;
-        if (in1) { o1[(int64_t)r * N + col + 1] = t1; o2[(int64_t)r * N + col + 1] = d1; }
-        v0 += (float)t0; v1 += (float)t1;        // db is the column sum of what the dW GEMM reads
-      }
-    }
-  }
-  __shared__ float s[4][128];
-  s[rl][2 * (threadIdx.x & 63)] = v0;
-  s[rl][2 * (threadIdx.x & 63) + 1] = v1;
-  __syncthreads();
-  if (rl == 0 && in0) {
-    const int k = 2 * threadIdx.x;
-    part[(int64_t)blockIdx.y * N + col] = s[0][k] + s[1][k] + s[2][k] + s[3][k];
-    if (in1) part[(int64_t)blockIdx.y * N + col + 1] = s[0][k + 1] + s[1][k + 1] + s[2][k + 1] + s[3][k + 1];
-  }
-}
-// The same three operations, 8 columns (one 16-byte bf16 chunk) per lane: N % 8 == 0, leading
-// dimensions % 8 == 0, 16-byte aligned bases (the trunk's widths 368 / 400 / 624 / 1000 / 736 all are).
-template <int OP>
-__global__ void __launch_bounds__(256) ew_colsum_h8_kernel(const bf16_t* __restrict__ a, int64_t lda,
-                                                           const bf16_t* __restrict__ b, int64_t ldb,
-                                                           const bf16_t* __restrict__ c, int64_t ldc, int M, int N,
-                                                           bf16_t* __restrict__ o1, float* __restrict__ o2,
-                                                           int accumulate, float* __restrict__ part) {
-  const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int col = (blockIdx.x * 64 + lane) * 8;
-  const int rows_per = (M + kColChunksH - 1) / kColChunksH;
-  const int r0 = blockIdx.y * rows_per;
-  const int r1 = (r0 + rows_per < M) ? r0 + rows_per : M;
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = 0.f;
-  if (col < N) {
-#pragma unroll 2
-    for (int r = r0 + rl; r < r1; r += 4) {
-      const bf16x8 av = *reinterpret_cast<const bf16x8*>(a + (int64_t)r * lda + col);
-      if (OP == 2) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += (float)av[e];
-      } else if (OP == 0) {
-        const bf16x8 yv = *reinterpret_cast<const bf16x8*>(b + (int64_t)r * ldb + col);
-        bf16x8 d;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          d[e] = (float)yv[e] > 0.f ? av[e] : (bf16_t)0.f;
-          v[e] += (float)d[e];
-        }
-        *reinterpret_cast<bf16x8*>(o1 + (int64_t)r * N + col) = d;
-      } else {
-        const bf16x8 xv = *reinterpret_cast<const bf16x8*>(b + (int64_t)r * ldb + col);
-        const bf16x8 uv = *reinterpret_cast<const bf16x8*>(c + (int64_t)r * ldc + col);
-        float4 d0 = make_float4(0.f, 0.f, 0.f, 0.f), d1 = d0;
-        float* dp = o2 + (int64_t)r * N + col;
-        if (accumulate & 1) {
-          d0 = *reinterpret_cast<const float4*>(dp);
-          d1 = *reinterpret_cast<const float4*>(dp + 4);
-        }
-        float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-        bf16x8 t;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float g = (float)av[e];
-          t[e] = (bf16_t)(g * (float)xv[e]);
-          d[e] += g * (float)uv[e];
-          if (accumulate & 2) d[e] += g;
-          v[e] += (float)t[e];
-        }
-        *reinterpret_cast<bf16x8*>(o1 + (int64_t)r * N + col) = t;
-        *reinterpret_cast<float4*>(dp) = make_float4(d[0], d[1], d[2], d[3]);
-        *reinterpret_cast<float4*>(dp + 4) = make_float4(d[4], d[5], d[6], d[7]);
-      }
-    }
-  }
-  __shared__ float s[4][64][9];          // 9: the 8 values of a lane on distinct banks from its neighbours'
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s[rl][lane][e] = v[e];
-  __syncthreads();
-  if (rl == 0 && col < N) {
-    float t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = s[0][lane][e] + s[1][lane][e] + s[2][lane][e] + s[3][lane][e];
-    float* dst = part + (int64_t)blockIdx.y * N + col;
-    *reinterpret_cast<float4*>(dst) = make_float4(t[0], t[1], t[2], t[3]);
-    *reinterpret_cast<float4*>(dst + 4) = make_float4(t[4], t[5], t[6], t[7]);
-  }
-}
-
-__global__ void __launch_bounds__(256) colsum_stage2_h_kernel(const float* __restrict__ part, int N,
-                                                              float* __restrict__ out) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= N) return;
-  float v = 0.f;
-  for (int i = 0; i < kColChunksH; ++i) v += part[(int64_t)i * N + c];
-  out[c] = v;
-}
-
-__global__ void __launch_bounds__(256) relu_mask_h_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
-                                                          int64_t n, bf16_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (float)y[i] > 0.f ? dy[i] : (bf16_t)0.f;
-}
-
 }  // namespace mapx
 
 extern "C" int mapx_gemm_bf16(int a_kc, int b_kc, int M, int N, int K, const mapx_bf16* A, int64_t lda,
@@ -887,12 +701,12 @@ extern "C" int mapx_gemm_bf16(int a_kc, int b_kc, int M, int N, int K, const map
   MAPX_REQUIRE(nsplit == 1 || (epi == MAPX_EPI_NONE && c_f32), "gemm_bf16: split-K needs EPI_NONE and an fp32 output");
 
   GemmHArgs g;
-  g.A = reinterpret_cast<const bf16_t*>(A); g.lda = lda;
-  g.B = reinterpret_cast<const bf16_t*>(B); g.ldb = ldb;
+  g.A = hc(A); g.lda = lda;
+  g.B = hc(B); g.ldb = ldb;
   g.C = C; g.ldc = ldc;
   g.M = M; g.N = N; g.K = K; g.epi = epi; g.bias = bias;
-  g.aux1 = aux1; g.ld1 = ld1; g.aux2 = reinterpret_cast<const bf16_t*>(aux2); g.ld2 = ld2;
-  g.out2 = reinterpret_cast<bf16_t*>(out2); g.ldo2 = ldo2;
+  g.aux1 = aux1; g.ld1 = ld1; g.aux2 = hc(aux2); g.ld2 = ld2;
+  g.out2 = hm(out2); g.ldo2 = ldo2;
   g.k_chunk = K > 0 ? K : kHBK; g.slab_stride = 0;
   if (nsplit > 1) {
     const size_t need = (size_t)nsplit * M * N * sizeof(float);
@@ -924,112 +738,7 @@ extern "C" int mapx_gemm_bf16(int a_kc, int b_kc, int M, int N, int K, const map
   MAPX_HIP(lerr);
   if (nsplit > 1) {
     MAPX_REQUIRE(ldc == N, "gemm_bf16: split-K output must be dense (ldc == N)");
-    const int64_t n = (int64_t)M * N;
-    if (n % 4 == 0 && (uintptr_t)C % 16 == 0)
-      hipLaunchKernelGGL(splitk_reduce_h_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream,
-                         static_cast<const float*>(ws), g.slab_stride, nsplit, n / 4, static_cast<float*>(C));
-    else
-      hipLaunchKernelGGL(splitk_reduce_h1_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-                         static_cast<const float*>(ws), g.slab_stride, nsplit, n, static_cast<float*>(C));
+    splitk_reduce_launch(ws, g.slab_stride, nsplit, (int64_t)M * N, static_cast<float*>(C), stream);
   }
   return check_launch("gemm_bf16");
-}
-
-extern "C" int mapx_cast_f32_bf16(const float* src, int64_t n, mapx_bf16* dst, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(n >= 0, "cast_f32_bf16: negative size");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(src && dst && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, "cast_f32_bf16: null or unaligned pointer");
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(ceil_div(n, 8), 256)), dim3(256), 0, stream, src, n,
-                     reinterpret_cast<bf16_t*>(dst));
-  return check_launch("cast_f32_bf16");
-}
-
-extern "C" int mapx_cast_bf16_f32(const mapx_bf16* src, int64_t n, float* dst, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(n >= 0, "cast_bf16_f32: negative size");
-  if (n == 0) return MAPX_OK;
-  MAPX_REQUIRE(src && dst, "cast_bf16_f32: null pointer");
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-                     reinterpret_cast<const bf16_t*>(src), n, dst);
-  return check_launch("cast_bf16_f32");
-}
-
-extern "C" size_t mapx_colsum_bf16_workspace_bytes(int N) { return (size_t)mapx::kColChunksH * N * sizeof(float); }
-
-// 8-column lanes when every operand allows 16-byte accesses, scalar column pairs otherwise
-template <int OP>
-static void launch_ew_colsum_h(const mapx::bf16_t* a, int64_t lda, const mapx::bf16_t* b, int64_t ldb,
-                               const mapx::bf16_t* c, int64_t ldc, int M, int N, mapx::bf16_t* o1, float* o2,
-                               int accumulate, float* part, hipStream_t stream) {
-  using namespace mapx;
-  auto al16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };
-  const bool vec = N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && al16(a) && al16(b) && al16(c) &&
-                   al16(o1) && al16(o2) && al16(part);
-  if (vec)
-    hipLaunchKernelGGL(ew_colsum_h8_kernel<OP>, dim3((N + 511) / 512, kColChunksH), dim3(256), 0, stream, a, lda, b,
-                       ldb, c, ldc, M, N, o1, o2, accumulate, part);
-  else
-    hipLaunchKernelGGL(ew_colsum_h_kernel<OP>, dim3((N + 127) / 128, kColChunksH), dim3(256), 0, stream, a, lda, b,
-                       ldb, c, ldc, M, N, o1, o2, accumulate, part);
-}
-
-static int colsum_ws_ok(const char* what, void* ws, size_t ws_bytes, int N) {
-  if (!ws || ws_bytes < mapx_colsum_bf16_workspace_bytes(N)) {
-    mapx::set_error("%s: workspace too small", what);
-    return 0;
-  }
-  return 1;
-}
-
-extern "C" int mapx_colsum_bf16(const mapx_bf16* x, int64_t ld, int M, int N, float* out, void* ws, size_t ws_bytes,
-                                hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(x && M >= 0 && N > 0 && ld >= N, "colsum_bf16: bad arguments");
-  if (!colsum_ws_ok("colsum_bf16", ws, ws_bytes, N)) return MAPX_EWORKSPACE;
-  float* part = static_cast<float*>(ws);
-  const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-  launch_ew_colsum_h<2>(xb, ld, xb, ld, xb, ld, M, N, nullptr, nullptr, 0, part, stream);
-  if (out)     // out == NULL: the caller adds the chunk rows later (mapx_sum_tasks), as with mapx_colsum
-    hipLaunchKernelGGL(colsum_stage2_h_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, out);
-  return check_launch("colsum_bf16");
-}
-
-extern "C" int mapx_relu_mask_colsum_bf16(const mapx_bf16* dy, int64_t ld_dy, const mapx_bf16* y, int64_t ld_y, int M,
-                                          int N, mapx_bf16* dz, float* db, void* ws, size_t ws_bytes,
-                                          hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(dy && y && dz && M >= 0 && N > 0 && ld_dy >= N && ld_y >= N, "relu_mask_colsum_bf16: bad arguments");
-  if (!colsum_ws_ok("relu_mask_colsum_bf16", ws, ws_bytes, N)) return MAPX_EWORKSPACE;
-  float* part = static_cast<float*>(ws);
-  launch_ew_colsum_h<0>(reinterpret_cast<const bf16_t*>(dy), ld_dy, reinterpret_cast<const bf16_t*>(y), ld_y,
-                        reinterpret_cast<const bf16_t*>(y), ld_y, M, N, reinterpret_cast<bf16_t*>(dz), nullptr, 0, part,
-                        stream);
-  if (db) hipLaunchKernelGGL(colsum_stage2_h_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, db);
-  return check_launch("relu_mask_colsum_bf16");
-}
-
-extern "C" int mapx_cross_bwd_pre_colsum_bf16(const mapx_bf16* g, int64_t ld_g, const mapx_bf16* x0, const mapx_bf16* u,
-                                              int M, int N, mapx_bf16* t, float* dx0, int accumulate, float* db,
-                                              void* ws, size_t ws_bytes, hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(g && x0 && u && t && dx0 && M >= 0 && N > 0 && ld_g >= N, "cross_bwd_pre_colsum_bf16: bad arguments");
-  if (!colsum_ws_ok("cross_bwd_pre_colsum_bf16", ws, ws_bytes, N)) return MAPX_EWORKSPACE;
-  float* part = static_cast<float*>(ws);
-  launch_ew_colsum_h<1>(reinterpret_cast<const bf16_t*>(g), ld_g, reinterpret_cast<const bf16_t*>(x0), (int64_t)N,
-                        reinterpret_cast<const bf16_t*>(u), (int64_t)N, M, N, reinterpret_cast<bf16_t*>(t), dx0,
-                        accumulate, part, stream);
-  if (db) hipLaunchKernelGGL(colsum_stage2_h_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, part, N, db);
-  return check_launch("cross_bwd_pre_colsum_bf16");
-}
-
-extern "C" int mapx_relu_mask_bf16(const mapx_bf16* dy, const mapx_bf16* y, int64_t n, mapx_bf16* out,
-                                   hipStream_t stream) {
-  using namespace mapx;
-  MAPX_REQUIRE(dy && y && out && n >= 0, "relu_mask_bf16: bad arguments");
-  if (n == 0) return MAPX_OK;
-  hipLaunchKernelGGL(relu_mask_h_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-                     reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<const bf16_t*>(y), n,
-                     reinterpret_cast<bf16_t*>(out));
-  return check_launch("relu_mask_bf16");
 }

@@ -23,6 +23,7 @@
 // through LDS as fp32 rows and moves every operand with 16-byte accesses.
 #include "amax.h"
 #include "gemm_x3_common.h"
+#include "splitk_reduce.h"
 #include "gemm_grouped.h"
 
 namespace mapx {
@@ -491,28 +492,6 @@ static hipError_t launch_layout_x3(GemmX3Args& a, bool vec, int tile, int nsplit
 #undef MAPX_X3
 }
 
-__global__ void __launch_bounds__(256) splitk_reduce_x3_kernel(const float* __restrict__ slabs, int64_t slab_stride,
-                                                               int nsplit, int64_t n, float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    for (int s = 0; s < nsplit; ++s) v += slabs[s * slab_stride + i];
-    out[i] = v;
-  }
-}
-// 16-byte form (n % 4 == 0, aligned slabs and output): a quarter of the memory instructions; same order of adds
-__global__ void __launch_bounds__(256) splitk_reduce_x3_v4_kernel(const float* __restrict__ slabs, int64_t slab_stride,
-                                                                  int nsplit, int64_t n4, float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 v = reinterpret_cast<const float4*>(slabs)[i];
-    v.x += 0.f; v.y += 0.f; v.z += 0.f; v.w += 0.f;          // (0 + x first, as the scalar form adds)
-    for (int s = 1; s < nsplit; ++s) {
-      const float4 x = reinterpret_cast<const float4*>(slabs + s * slab_stride)[i];
-      v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
-    }
-    reinterpret_cast<float4*>(out)[i] = v;
-  }
-}
-
 bool gemm_f32h2_try(GemmX3Args& g, int a_kc, int b_kc, bool vec, int tile, bool hinted, int nsplit,
                     int batch, hipStream_t stream, hipError_t* err);      // gemm_h2.hip
 
@@ -605,13 +584,7 @@ int gemm_f32x3_launch(int a_kc, int b_kc, int M, int N, int K, const float* A, i
   if (nsplit_deferred) *nsplit_deferred = nsplit > 1 ? nsplit : 0;
   if (nsplit > 1 && !nsplit_deferred) {
     MAPX_REQUIRE(ldc == N, "gemm_f32: split-K output must be dense (ldc == N)");
-    const int64_t n = (int64_t)M * N;
-    if (n % 4 == 0 && g.slab_stride % 4 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)C % 16 == 0)
-      hipLaunchKernelGGL(splitk_reduce_x3_v4_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream,
-                         static_cast<const float*>(ws), g.slab_stride, nsplit, n / 4, C);
-    else
-      hipLaunchKernelGGL(splitk_reduce_x3_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-                         static_cast<const float*>(ws), g.slab_stride, nsplit, n, C);
+    splitk_reduce_launch(ws, g.slab_stride, nsplit, (int64_t)M * N, C, stream);
   }
   return check_launch("gemm_f32 (3 x bf16)");
 }

@@ -267,25 +267,7 @@ __global__ void __launch_bounds__(256) mask_rfd_kernel(const int64_t* __restrict
   }
 }
 
-// ReLU backward: out = y > 0 ? dy : 0  (y = the layer's activated output)
-__global__ void __launch_bounds__(256) relu_mask_kernel(const float* __restrict__ dy,
-                                                        const float* __restrict__ y, int64_t n,
-                                                        float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = y[i] > 0.f ? dy[i] : 0.f;
-}
-
 }  // namespace mapx
-
-extern "C" int mapx_relu_mask(const float* dy, const float* y, int64_t n, float* out,
-                              hipStream_t stream) {
-  MAPX_REQUIRE(dy && y && out && n >= 0, "relu_mask: bad arguments");
-  if (n == 0) return MAPX_OK;
-  hipLaunchKernelGGL(mapx::relu_mask_kernel, dim3(mapx::grid_for(n, 256)), dim3(256), 0, stream, dy,
-                     y, n, out);
-  return mapx::check_launch("relu_mask");
-}
 
 extern "C" size_t mapx_bce_workspace_bytes(void) { return mapx::kLossBlocks * 3 * sizeof(float); }
 

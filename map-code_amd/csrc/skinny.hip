@@ -16,24 +16,9 @@ namespace mapx {
 
 constexpr int kSkinnyChunks = 128;       // row chunks of the weight gradient (= partial rows per output)
 
-// Element access of the streaming kernels: fp32, or (bf16 compute mode: the finetune head reads the trunk's bf16
-// activations and the weight's bf16 operand) bf16 widened to fp32 — products and sums are fp32 either way, like the
-// bf16 MFMA's.
-typedef __bf16 sk_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ inline float4 sk_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ inline float4 sk_ld4(const __bf16* p) {
-  const sk_bf16x4 v = *reinterpret_cast<const sk_bf16x4*>(p);
-  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-__device__ inline float sk_ld1(const float* p) { return *p; }
-__device__ inline float sk_ld1(const __bf16* p) { return (float)*p; }
-__device__ inline void sk_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ inline void sk_st4(__bf16* p, float4 v) {
-  sk_bf16x4 o;
-  o[0] = (__bf16)v.x; o[1] = (__bf16)v.y; o[2] = (__bf16)v.z; o[3] = (__bf16)v.w;
-  *reinterpret_cast<sk_bf16x4*>(p) = o;
-}
-
+// Element access of the streaming kernels (common.h: load4 / store4): fp32, or (bf16 compute mode: the finetune head
+// reads the trunk's bf16 activations and the weight's bf16 operand) bf16 widened to fp32 — products and sums are fp32
+// either way, like the bf16 MFMA's.
 template <int NT, class T = float>
 __global__ void __launch_bounds__(256) skinny_fwd_kernel(const T* __restrict__ x, int64_t ldx,
                                                          const T* __restrict__ w, int64_t ldw,
@@ -54,11 +39,11 @@ __global__ void __launch_bounds__(256) skinny_fwd_kernel(const T* __restrict__ x
   for (int k = 4 * lane; k < K; k += 256) {
     float4 xv[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) xv[r] = sk_ld4(xr[r] + k);
+    for (int r = 0; r < R; ++r) xv[r] = load4(xr[r] + k);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       if (n < N) {
-        const float4 wv = sk_ld4(w + (int64_t)n * ldw + k);
+        const float4 wv = load4(w + (int64_t)n * ldw + k);
 #pragma unroll
         for (int r = 0; r < R; ++r)
           acc[r][n] += xv[r].x * wv.x + xv[r].y * wv.y + xv[r].z * wv.z + xv[r].w * wv.w;
@@ -102,12 +87,12 @@ __global__ void __launch_bounds__(256) skinny_dw_kernel(const T* __restrict__ dy
 #pragma unroll
   for (int n = 0; n < NT; ++n) acc[n] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int m = m0; m < m1; ++m) {
-    const float4 xv = sk_ld4(x + (int64_t)m * ldx + k);
+    const float4 xv = load4(x + (int64_t)m * ldx + k);
     const T* __restrict__ d = dy + (int64_t)m * ldy;           // the same N values for every thread: one line
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       if (n < N) {
-        const float g = sk_ld1(d + n);
+        const float g = (float)d[n];
         acc[n].x += g * xv.x; acc[n].y += g * xv.y; acc[n].z += g * xv.z; acc[n].w += g * xv.w;
       }
     }
@@ -138,17 +123,17 @@ __global__ void __launch_bounds__(256) skinny_dx_kernel(const T* __restrict__ dy
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
     if (n < N) {
-      const float4 wv = sk_ld4(w + (int64_t)n * ldw + k);
+      const float4 wv = load4(w + (int64_t)n * ldw + k);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const float g = sk_ld1(dr[r] + n);
+        const float g = (float)dr[r][n];
         acc[r].x += g * wv.x; acc[r].y += g * wv.y; acc[r].z += g * wv.z; acc[r].w += g * wv.w;
       }
     }
   }
 #pragma unroll
   for (int r = 0; r < R; ++r)
-    if (r0 + r < M) sk_st4(dx + (r0 + r) * lddx + k, acc[r]);
+    if (r0 + r < M) store4(dx + (r0 + r) * lddx + k, acc[r]);
 }
 
 // Wider layers (8 < N <= 32 outputs: RFD's Linear(736 -> 23)): the weight-gradient kernel above re-reads N gradients
@@ -339,49 +324,54 @@ __global__ void __launch_bounds__(256) skinny_join_bwd_kernel(
   }
 }
 
-template <template <int> class Launch, class... A>
+// NT = the smallest built count of outputs >= N; the bf16 forms are built for N <= 8 only (host-checked)
+template <template <int, class> class Launch, class T, class... A>
 static bool skinny_dispatch(int N, A... a) {
-  if (N <= 1) Launch<1>::go(a...);
-  else if (N <= 4) Launch<4>::go(a...);
-  else if (N <= 8) Launch<8>::go(a...);
-  else if (N <= 16) Launch<16>::go(a...);
-  else if (N <= 24) Launch<24>::go(a...);
-  else if (N <= 32) Launch<32>::go(a...);
-  else if (N <= 48) Launch<48>::go(a...);
-  else if (N <= 64) Launch<64>::go(a...);
-  else return false;
+  if (N <= 1) Launch<1, T>::go(a...);
+  else if (N <= 4) Launch<4, T>::go(a...);
+  else if (N <= 8) Launch<8, T>::go(a...);
+  else if constexpr (sizeof(T) == sizeof(float)) {
+    if (N <= 16) Launch<16, T>::go(a...);
+    else if (N <= 24) Launch<24, T>::go(a...);
+    else if (N <= 32) Launch<32, T>::go(a...);
+    else if (N <= 48) Launch<48, T>::go(a...);
+    else if (N <= 64) Launch<64, T>::go(a...);
+    else return false;
+  } else return false;
   return true;
 }
 
-template <int NT>
+template <int NT, class T>
 // (the forward and dX kernels do not stride over the grid: their grids cover every row, uncapped — grid_for's cap
 // of 2048 blocks left the rows past 32 768 (forward) / 2048 * 256 * 4 / (K / 4) (dX) unwritten)
 struct FwdLaunch {
-  static void go(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, int M, int N, int K,
+  static void go(const T* x, int64_t ldx, const T* w, int64_t ldw, const float* bias, int M, int N, int K,
                  int relu, float* y, int64_t ldy, hipStream_t stream) {
-    hipLaunchKernelGGL(skinny_fwd_kernel<NT>, dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, stream, x, ldx, w, ldw, bias, M, N,
-                       K, relu, y, ldy);
+    hipLaunchKernelGGL((skinny_fwd_kernel<NT, T>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, stream, x, ldx, w, ldw,
+                       bias, M, N, K, relu, y, ldy);
   }
 };
-template <int NT>
+template <int NT, class T>
 struct DwLaunch {
-  static void go(const float* dy, int64_t ldy, const float* x, int64_t ldx, int M, int N, int K, float* part,
+  static void go(const T* dy, int64_t ldy, const T* x, int64_t ldx, int M, int N, int K, float* part,
                  int chunks, hipStream_t stream) {
-    hipLaunchKernelGGL(skinny_dw_kernel<NT>, dim3(grid_for(K / 4, 256), chunks), dim3(256), 0, stream, dy, ldy,
+    hipLaunchKernelGGL((skinny_dw_kernel<NT, T>), dim3(grid_for(K / 4, 256), chunks), dim3(256), 0, stream, dy, ldy,
                        x, ldx, M, N, K, part);
   }
 };
-template <int NT>
+template <int NT, class T>
 struct DxLaunch {
-  static void go(const float* dy, int64_t ldy, const float* w, int64_t ldw, int M, int N, int K, float* dx,
+  static void go(const T* dy, int64_t ldy, const T* w, int64_t ldw, int M, int N, int K, T* dx,
                  int64_t lddx, hipStream_t stream) {
     const int64_t threads = (int64_t)((M + 3) / 4) * (K / 4);
-    hipLaunchKernelGGL(skinny_dx_kernel<NT>, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, stream, dy, ldy, w, ldw, M, N,
-                       K, dx, lddx);
+    hipLaunchKernelGGL((skinny_dx_kernel<NT, T>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, stream, dy, ldy, w,
+                       ldw, M, N, K, dx, lddx);
   }
 };
 
-static bool al16(const void* p, int64_t ld) { return ((uintptr_t)p % 16 == 0) && ld % 4 == 0; }
+// rows read four elements at a time: base aligned to four of them (16 B fp32, 8 B bf16) and ld % 4 == 0
+template <class T>
+static bool al4(const T* p, int64_t ld) { return ((uintptr_t)p % (4 * sizeof(T)) == 0) && ld % 4 == 0; }
 
 }  // namespace mapx
 
@@ -391,9 +381,9 @@ extern "C" int mapx_skinny_linear_fwd(const float* x, int64_t ldx, const float* 
                                       int M, int N, int K, int relu, float* y, int64_t ldy, hipStream_t stream) {
   using namespace mapx;
   MAPX_REQUIRE(x && w && y && M >= 0 && N >= 1 && N <= 32 && K >= 4 && K % 4 == 0, "skinny_linear_fwd: bad sizes");
-  MAPX_REQUIRE(al16(x, ldx) && al16(w, ldw) && ldy >= N, "skinny_linear_fwd: rows of x and w must be 16-byte aligned");
+  MAPX_REQUIRE(al4(x, ldx) && al4(w, ldw) && ldy >= N, "skinny_linear_fwd: rows of x and w must be 16-byte aligned");
   if (M == 0) return MAPX_OK;
-  skinny_dispatch<FwdLaunch>(N, x, ldx, w, ldw, bias_opt, M, N, K, relu, y, ldy, stream);
+  skinny_dispatch<FwdLaunch, float>(N, x, ldx, w, ldw, bias_opt, M, N, K, relu, y, ldy, stream);
   return check_launch("skinny_linear_fwd");
 }
 
@@ -402,7 +392,7 @@ extern "C" int mapx_skinny_linear_dw(const float* dy, int64_t ldy, const float* 
   using namespace mapx;
   MAPX_REQUIRE(dy && x && part && M >= 1 && N >= 1 && N <= 64 && K >= 4 && K % 4 == 0 && ldy >= N && chunks >= 1 &&
                    chunks <= 65535, "skinny_linear_dw: bad sizes (N <= 64)");
-  MAPX_REQUIRE(al16(x, ldx) && (uintptr_t)part % 16 == 0, "skinny_linear_dw: rows of x must be 16-byte aligned");
+  MAPX_REQUIRE(al4(x, ldx) && (uintptr_t)part % 16 == 0, "skinny_linear_dw: rows of x must be 16-byte aligned");
   const int rows_per = (M + chunks - 1) / chunks;
   if (K <= 64 && (N > 32 || (N > 8 && rows_per > 64)))
     hipLaunchKernelGGL(skinny_dw_tall_kernel, dim3(1, chunks), dim3(256), 0, stream, dy, ldy, x, ldx, M, N, K, part);
@@ -413,7 +403,7 @@ extern "C" int mapx_skinny_linear_dw(const float* dy, int64_t ldy, const float* 
     hipLaunchKernelGGL(skinny_dw_tiled_kernel<4>, dim3(grid_for(K, kTK), chunks), dim3(256), 0, stream, dy, ldy, x, ldx,
                        M, N, K, part);
   else
-    skinny_dispatch<DwLaunch>(N, dy, ldy, x, ldx, M, N, K, part, chunks, stream);
+    skinny_dispatch<DwLaunch, float>(N, dy, ldy, x, ldx, M, N, K, part, chunks, stream);
   return check_launch("skinny_linear_dw");
 }
 
@@ -422,28 +412,22 @@ extern "C" int mapx_skinny_linear_dx(const float* dy, int64_t ldy, const float* 
   using namespace mapx;
   MAPX_REQUIRE(dy && w && dx && M >= 0 && N >= 1 && N <= 64 && K >= 4 && K % 4 == 0 && ldy >= N,
                "skinny_linear_dx: bad sizes");
-  MAPX_REQUIRE(al16(w, ldw) && al16(dx, lddx), "skinny_linear_dx: rows of w and dx must be 16-byte aligned");
+  MAPX_REQUIRE(al4(w, ldw) && al4(dx, lddx), "skinny_linear_dx: rows of w and dx must be 16-byte aligned");
   if (M == 0) return MAPX_OK;
-  skinny_dispatch<DxLaunch>(N, dy, ldy, w, ldw, M, N, K, dx, lddx, stream);
+  skinny_dispatch<DxLaunch, float>(N, dy, ldy, w, ldw, M, N, K, dx, lddx, stream);
   return check_launch("skinny_linear_dx");
 }
 
 // bf16 compute mode: the same three products on bf16 activations / gradients and the weight's bf16 operand
 // (N <= 8; products and sums fp32; y and the weight gradient's partial rows fp32, dx bf16).
-static bool al8h(const void* p, int64_t ld) { return ((uintptr_t)p % 8 == 0) && ld % 4 == 0; }
-
 extern "C" int mapx_skinny_linear_fwd_bf16(const mapx_bf16* x, int64_t ldx, const mapx_bf16* w, int64_t ldw,
                                            const float* bias_opt, int M, int N, int K, int relu, float* y, int64_t ldy,
                                            hipStream_t stream) {
   using namespace mapx;
   MAPX_REQUIRE(x && w && y && M >= 0 && N >= 1 && N <= 8 && K >= 4 && K % 4 == 0, "skinny_linear_fwd_bf16: bad sizes (N <= 8)");
-  MAPX_REQUIRE(al8h(x, ldx) && al8h(w, ldw) && ldy >= N, "skinny_linear_fwd_bf16: rows of x and w must be 8-byte aligned");
+  MAPX_REQUIRE(al4(x, ldx) && al4(w, ldw) && ldy >= N, "skinny_linear_fwd_bf16: rows of x and w must be 8-byte aligned");
   if (M == 0) return MAPX_OK;
-  const __bf16* xx = reinterpret_cast<const __bf16*>(x);
-  const __bf16* ww = reinterpret_cast<const __bf16*>(w);
-#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_fwd_kernel<NT, __bf16>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, stream, xx, ldx, ww, ldw, bias_opt, M, N, K, relu, y, ldy)
-  if (N == 1) MAPX_SKH(1); else if (N <= 4) MAPX_SKH(4); else MAPX_SKH(8);
-#undef MAPX_SKH
+  skinny_dispatch<FwdLaunch, bf16_t>(N, hc(x), ldx, hc(w), ldw, bias_opt, M, N, K, relu, y, ldy, stream);
   return check_launch("skinny_linear_fwd_bf16");
 }
 
@@ -452,12 +436,8 @@ extern "C" int mapx_skinny_linear_dw_bf16(const mapx_bf16* dy, int64_t ldy, cons
   using namespace mapx;
   MAPX_REQUIRE(dy && x && part && M >= 1 && N >= 1 && N <= 8 && K >= 4 && K % 4 == 0 && ldy >= N && chunks >= 1 &&
                    chunks <= 65535, "skinny_linear_dw_bf16: bad sizes (N <= 8)");
-  MAPX_REQUIRE(al8h(x, ldx) && (uintptr_t)part % 16 == 0, "skinny_linear_dw_bf16: rows of x must be 8-byte aligned");
-  const __bf16* dd = reinterpret_cast<const __bf16*>(dy);
-  const __bf16* xx = reinterpret_cast<const __bf16*>(x);
-#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_dw_kernel<NT, __bf16>), dim3(grid_for(K / 4, 256), chunks), dim3(256), 0, stream, dd, ldy, xx, ldx, M, N, K, part)
-  if (N == 1) MAPX_SKH(1); else if (N <= 4) MAPX_SKH(4); else MAPX_SKH(8);
-#undef MAPX_SKH
+  MAPX_REQUIRE(al4(x, ldx) && (uintptr_t)part % 16 == 0, "skinny_linear_dw_bf16: rows of x must be 8-byte aligned");
+  skinny_dispatch<DwLaunch, bf16_t>(N, hc(dy), ldy, hc(x), ldx, M, N, K, part, chunks, stream);
   return check_launch("skinny_linear_dw_bf16");
 }
 
@@ -466,15 +446,9 @@ extern "C" int mapx_skinny_linear_dx_bf16(const mapx_bf16* dy, int64_t ldy, cons
   using namespace mapx;
   MAPX_REQUIRE(dy && w && dx && M >= 0 && N >= 1 && N <= 8 && K >= 4 && K % 4 == 0 && ldy >= N,
                "skinny_linear_dx_bf16: bad sizes (N <= 8)");
-  MAPX_REQUIRE(al8h(w, ldw) && al8h(dx, lddx), "skinny_linear_dx_bf16: rows of w and dx must be 8-byte aligned");
+  MAPX_REQUIRE(al4(w, ldw) && al4(dx, lddx), "skinny_linear_dx_bf16: rows of w and dx must be 8-byte aligned");
   if (M == 0) return MAPX_OK;
-  const __bf16* dd = reinterpret_cast<const __bf16*>(dy);
-  const __bf16* ww = reinterpret_cast<const __bf16*>(w);
-  __bf16* out = reinterpret_cast<__bf16*>(dx);
-  const int64_t threads = (int64_t)((M + 3) / 4) * (K / 4);
-#define MAPX_SKH(NT) hipLaunchKernelGGL((skinny_dx_kernel<NT, __bf16>), dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, stream, dd, ldy, ww, ldw, M, N, K, out, lddx)
-  if (N == 1) MAPX_SKH(1); else if (N <= 4) MAPX_SKH(4); else MAPX_SKH(8);
-#undef MAPX_SKH
+  skinny_dispatch<DxLaunch, bf16_t>(N, hc(dy), ldy, hc(w), ldw, M, N, K, hm(dx), lddx, stream);
   return check_launch("skinny_linear_dx_bf16");
 }
 
@@ -489,8 +463,8 @@ extern "C" int mapx_skinny_join_bwd(const float* dz, int64_t lddz, const float* 
                "skinny_join_bwd: null pointer");
   MAPX_REQUIRE(M >= 1 && N >= 1 && N <= 8 && D >= 4 && H >= 4 && D % 4 == 0 && H % 4 == 0 && lddz >= N,
                "skinny_join_bwd: bad sizes");
-  MAPX_REQUIRE(al16(w, ldw) && al16(final_act, ldf) && al16(x0, ldx0) && al16(u, ldu) && al16(g, ldg) && al16(t, ldt) &&
-                   al16(dx0, lddx0) && al16(dzr, lddzr) && (uintptr_t)part_cross % 16 == 0 && (uintptr_t)part_deep % 16 == 0,
+  MAPX_REQUIRE(al4(w, ldw) && al4(final_act, ldf) && al4(x0, ldx0) && al4(u, ldu) && al4(g, ldg) && al4(t, ldt) &&
+                   al4(dx0, lddx0) && al4(dzr, lddzr) && (uintptr_t)part_cross % 16 == 0 && (uintptr_t)part_deep % 16 == 0,
                "skinny_join_bwd: rows must be 16-byte aligned");
   const dim3 grid(grid_for((D + H) / 4, 32), (M + 127) / 128);
 #define MAPX_SJ(NT)                                                                                                   \

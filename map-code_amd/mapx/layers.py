@@ -602,21 +602,15 @@ class _Linear(Function):
         half = ops.is_bf16(x)
         ctx.kpad, ctx.sw_real = 0, None
         wop = None
-        if (not half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
-                and link_in is None):
+        if x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32 and link_in is None:
             # An input width that is not a multiple of 8 floats (DeepFM's heads read cat([dnn, lr + fm]): 1001 columns)
             # leaves the GEMMs their scalar operand path — 172 / 161 / 123 us for the forward / dW / dX of a
             # 4096 x 736 x 1001 layer against ~40 each.  Both operands are padded with zero columns to the next multiple
-            # of 8 instead (two pad launches, one copy of dW back into its slot).
+            # of 8 instead (two pad launches, one copy of dW back into its slot).  The same in bf16 mode (the bf16
+            # GEMM's 16-byte chunks hold 8 elements): x and the weight's shadow are padded.
             ctx.kpad, ctx.sw_real = (-x.shape[1]) % 8, _grad_slot(w)
             x = torch.nn.functional.pad(x, (0, ctx.kpad))
-            w = torch.nn.functional.pad(w.detach(), (0, ctx.kpad))
-        elif (half and x.is_cuda and x.shape[1] % 8 != 0 and x.shape[0] >= 256 and w.shape[0] > 32
-                and link_in is None):
-            # the same in bf16 mode (the bf16 GEMM's 16-byte chunks hold 8 elements): x and the weight's shadow padded
-            ctx.kpad, ctx.sw_real = (-x.shape[1]) % 8, _grad_slot(w)
-            x = torch.nn.functional.pad(x, (0, ctx.kpad))
-            wop = torch.nn.functional.pad(ops.bf16_weight(w), (0, ctx.kpad))
+            wop = torch.nn.functional.pad(ops.bf16_weight(w) if half else w.detach(), (0, ctx.kpad))
         if half and relu and out_f32:
             raise NotImplementedError("a ReLU layer with an fp32 result inside the bf16 trunk")
         if wop is None:

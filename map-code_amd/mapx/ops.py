@@ -1717,6 +1717,11 @@ def _skinny(Nn, K, *mats, bwd=False):
         and all(_rows16(m) for m in mats)
 
 
+def _streaming(half, Nn, K, *mats, bwd=False):
+    """Do the narrow-layer streaming kernels of the element type take this layer?"""
+    return _skinny_h(Nn, K, *mats) if half else _skinny(Nn, K, *mats, bwd=bwd)
+
+
 def _sum_now(dst, src, stride, nsplit, n):
     arr = (N.SumTask * 1)()
     arr[0].dst, arr[0].src, arr[0].stride, arr[0].n, arr[0].nsplit = dst.data_ptr(), src.data_ptr(), stride, n, nsplit
@@ -1729,19 +1734,15 @@ def linear_fwd(x, w, b, relu=False, out=None, out_dtype=None):
     (`out_dtype=torch.float32`: the heads' logits) fp32."""
     M, K = x.shape
     Nn = w.shape[0]
-    if out_dtype in (None, torch.float32) and _skinny(Nn, K, x, w) and (out is None or out.dtype == torch.float32):
+    half = is_bf16(x)
+    f32_out = out_dtype == torch.float32 or (out_dtype is None and not half)
+    if f32_out and _streaming(half, Nn, K, x, w) and (out is None or out.dtype == torch.float32):
         require_gpu(x, w)
         y = out if out is not None else torch.empty(M, Nn, dtype=torch.float32, device=x.device)
-        with _timed("skinny_linear", 4.0 * (M * K + Nn * K + M * Nn)):
-            check(lib.mapx_skinny_linear_fwd(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(b), M, Nn, K, int(relu),
-                                             y.data_ptr(), y.stride(0), stream()))
-        return y
-    if out_dtype == torch.float32 and _skinny_h(Nn, K, x, w) and (out is None or out.dtype == torch.float32):
-        require_gpu(x, w)
-        y = out if out is not None else torch.empty(M, Nn, dtype=torch.float32, device=x.device)
-        with _timed("skinny_linear", 2.0 * (M * K + Nn * K) + 4.0 * M * Nn):
-            check(lib.mapx_skinny_linear_fwd_bf16(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(b), M, Nn, K, int(relu),
-                                                  y.data_ptr(), y.stride(0), stream()))
+        fn = lib.mapx_skinny_linear_fwd_bf16 if half else lib.mapx_skinny_linear_fwd
+        with _timed("skinny_linear", float(x.element_size()) * (M * K + Nn * K) + 4.0 * M * Nn):
+            check(fn(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(b), M, Nn, K, int(relu), y.data_ptr(), y.stride(0),
+                     stream()))
         return y
     return gemm(x, w, True, True, M, Nn, K, out=out, epi=N.EPI_BIAS_RELU if relu else N.EPI_BIAS,
                 bias=b, out_dtype=out_dtype)
@@ -1774,21 +1775,14 @@ def linear_bwd_input(dy, w, out=None, add=None, relu_of=None, colsum_to=None):
     summed into `colsum_to` by flush_deferred()."""
     M, Nn = dy.shape
     K = w.shape[1]
-    if add is None and relu_of is None and _skinny(Nn, K, w, bwd=True) and dy.dtype == torch.float32 and dy.dim() == 2 \
-            and dy.stride(1) == 1 and (out is None or _rows16(out)):
+    half = is_bf16(dy)
+    if add is None and relu_of is None and (half or dy.dtype == torch.float32) and _streaming(half, Nn, K, w, bwd=True) \
+            and dy.dim() == 2 and dy.stride(1) == 1 and (out is None or (_rows8h if half else _rows16)(out)):
         require_gpu(dy, w)
-        dx = out if out is not None else torch.empty(M, K, dtype=torch.float32, device=dy.device)
-        with _timed("skinny_linear", 4.0 * (M * K + Nn * K + M * Nn)):
-            check(lib.mapx_skinny_linear_dx(ptr(dy), dy.stride(0), ptr(w), w.stride(0), M, Nn, K, dx.data_ptr(),
-                                            dx.stride(0), stream()))
-        return dx
-    if add is None and relu_of is None and dy.dim() == 2 and _skinny_h(Nn, K, w) and is_bf16(dy) and dy.stride(1) == 1 \
-            and (out is None or _rows8h(out)):
-        require_gpu(dy, w)
-        dx = out if out is not None else torch.empty(M, K, dtype=torch.bfloat16, device=dy.device)
-        with _timed("skinny_linear", 2.0 * (M * K + Nn * K + M * Nn)):
-            check(lib.mapx_skinny_linear_dx_bf16(ptr(dy), dy.stride(0), ptr(w), w.stride(0), M, Nn, K, dx.data_ptr(),
-                                                 dx.stride(0), stream()))
+        dx = out if out is not None else torch.empty(M, K, dtype=dy.dtype, device=dy.device)
+        fn = lib.mapx_skinny_linear_dx_bf16 if half else lib.mapx_skinny_linear_dx
+        with _timed("skinny_linear", float(dy.element_size()) * (M * K + Nn * K + M * Nn)):
+            check(fn(ptr(dy), dy.stride(0), ptr(w), w.stride(0), M, Nn, K, dx.data_ptr(), dx.stride(0), stream()))
         return dx
     epi, aux, out2 = N.EPI_NONE, None, None
     if add is not None:
@@ -1804,10 +1798,11 @@ def linear_bwd_input(dy, w, out=None, add=None, relu_of=None, colsum_to=None):
     return dx
 
 
-def _splits_wide_tiles(M, Nn, Kred):
+def _splits_wide_tiles(M, Nn, Kred, count=1):
     """split-K factor for the bf16-MFMA kernels (bf16 operands, or fp32 cut into three bf16 pieces):
-    128 x 128 tiles, split over K until they cover the 256 CUs, K chunk >= 256."""
-    tiles = math.ceil(M / 128) * math.ceil(Nn / 128)
+    128 x 128 tiles (of `count` equal problems in one launch), split over K until they cover the 256 CUs,
+    K chunk >= 256."""
+    tiles = math.ceil(M / 128) * math.ceil(Nn / 128) * count
     ns = 1
     while ns < 16 and tiles * ns * 2 <= 288 and Kred // (ns * 2) >= 256:
         ns *= 2
@@ -1824,12 +1819,12 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
     # gave a timing-dependent wrong result beside MFMA kernels in round 3; the re-written loop has passed every
     # bitwise graph == eager run since, but the mechanism was never found, so the default is the GEMM.)
     tall = SKINNY and SKINNY_TALL and 32 < Nn <= 64 and 4 <= K <= 64 and K % 4 == 0 and Bn >= 8192 and _rows16(x)
-    ok = _skinny(Nn, K, x, bwd=True) or tall
+    half = is_bf16(dy)                       # (bf16: at most 8 outputs, so none of the wide forms' rules below applies)
+    ok = _skinny_h(Nn, K, x) if half else dy.dtype == torch.float32 and (_skinny(Nn, K, x, bwd=True) or tall)
     rows_cap = 64 if (Nn > 32 and K > 64) else _TALL_ROWS     # (33..64 outputs x many columns: the LDS-tiled form only)
     if ok and Nn > 32 and K > 64 and Bn > 64 * 2048:
         ok = False
-    if Bn >= 1 and ok and dy.dtype == torch.float32 and dy.dim() == 2 \
-            and dy.stride(1) == 1 \
+    if Bn >= 1 and ok and dy.dim() == 2 and dy.stride(1) == 1 \
             and (out is None or (out.dtype == torch.float32 and out.is_contiguous())):
         require_gpu(dy, x)
         chunks = lib.mapx_skinny_chunks()
@@ -1837,27 +1832,11 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
             chunks *= 2
         dw = out if out is not None else torch.empty(Nn, K, dtype=torch.float32, device=dy.device)
         part = torch.empty(chunks, Nn * K, dtype=torch.float32, device=dy.device)
-        with _timed("skinny_linear", 4.0 * (Bn * K + Bn * Nn + chunks * Nn * K)):
-            check(lib.mapx_skinny_linear_dw(ptr(dy), dy.stride(0), ptr(x), x.stride(0), Bn, Nn, K, ptr(part), chunks,
-                                            stream()))
+        fn = lib.mapx_skinny_linear_dw_bf16 if half else lib.mapx_skinny_linear_dw
+        with _timed("skinny_linear", float(dy.element_size()) * (Bn * K + Bn * Nn) + 4.0 * chunks * Nn * K):
+            check(fn(ptr(dy), dy.stride(0), ptr(x), x.stride(0), Bn, Nn, K, ptr(part), chunks, stream()))
         if defer and out is not None:
             defer_sum(dw, part, Nn * K, chunks, Nn * K)          # with the step's other partial sums
-        else:
-            _sum_now(dw, part, Nn * K, chunks, Nn * K)
-        return dw
-    if Bn >= 1 and is_bf16(dy) and dy.dim() == 2 and dy.stride(1) == 1 and _skinny_h(Nn, K, x) \
-            and (out is None or (out.dtype == torch.float32 and out.is_contiguous())):
-        require_gpu(dy, x)
-        chunks = lib.mapx_skinny_chunks()
-        while -(-Bn // chunks) > _TALL_ROWS and chunks < 2048:
-            chunks *= 2
-        dw = out if out is not None else torch.empty(Nn, K, dtype=torch.float32, device=dy.device)
-        part = torch.empty(chunks, Nn * K, dtype=torch.float32, device=dy.device)
-        with _timed("skinny_linear", 2.0 * (Bn * K + Bn * Nn) + 4.0 * chunks * Nn * K):
-            check(lib.mapx_skinny_linear_dw_bf16(ptr(dy), dy.stride(0), ptr(x), x.stride(0), Bn, Nn, K, ptr(part), chunks,
-                                                 stream()))
-        if defer and out is not None:
-            defer_sum(dw, part, Nn * K, chunks, Nn * K)
         else:
             _sum_now(dw, part, Nn * K, chunks, Nn * K)
         return dw
@@ -1870,41 +1849,32 @@ def linear_bwd_weight(dy, x, out=None, defer=False):
     return gemm(dy, x, False, False, Nn, K, Bn, out=out, nsplit=ns, record=False)
 
 
-def _partials_h(Nn, device, defer):
-    """Workspace of the bf16 column-sum kernels -> (buffer, chunk rows); defer: a buffer of its own (it lives until
-    flush_deferred sums it) instead of the stream's scratch."""
-    nb = lib.mapx_colsum_bf16_workspace_bytes(Nn)
-    buf = torch.empty(nb, dtype=torch.uint8, device=device) if defer else scratch(nb, device)
-    return buf, nb // (4 * Nn)
-
-
 def _partials(Nn, device, defer):
+    """Workspace of the column-sum kernels, either element type: COLSUM_CHUNKS partial rows of Nn floats.  defer: a
+    buffer of its own (it lives until flush_deferred sums it) instead of the stream's scratch."""
     nb = lib.mapx_colsum_workspace_bytes(Nn)
     return torch.empty(nb, dtype=torch.uint8, device=device) if defer else scratch(nb, device)
+
+
+def _colsum_operand(t, half):
+    """t as the fused column-sum kernels read it: in place when the rows qualify (fp32: row_sliceable, the float4
+    lanes; bf16: unit column stride, the kernel picks its lanes by alignment), else a contiguous copy."""
+    return t if (t.stride(1) == 1 if half else row_sliceable(t)) else t.contiguous()
 
 
 def colsum(x, out=None, defer=False):
     """Column sums; defer (needs out): leave the row-chunk partials for flush_deferred()."""
     require_gpu(x)
     M, Nn = x.shape
-    if is_bf16(x):
-        later = defer and out is not None
-        if out is None:
-            out = torch.empty(Nn, dtype=torch.float32, device=x.device)
-        if x.stride(1) != 1:
-            x = x.contiguous()
-        ws, chunks = _partials_h(Nn, x.device, later)
-        check(lib.mapx_colsum_bf16(x.data_ptr(), x.stride(0), M, Nn, None if later else ptr(out), ptr(ws), ws.numel(),
-                                   stream()))
-        if later:
-            defer_sum(out, ws.view(torch.float32), Nn, chunks, Nn)
-        return out
+    half = is_bf16(x)
     defer = defer and out is not None
     if out is None:
         out = torch.empty(Nn, dtype=torch.float32, device=x.device)
+    if half and x.stride(1) != 1:            # (the fp32 kernel is handed x as it is)
+        x = x.contiguous()
     ws = _partials(Nn, x.device, defer)
-    check(lib.mapx_colsum(x.data_ptr(), x.stride(0), M, Nn, None if defer else ptr(out), ptr(ws),
-                          ws.numel(), stream()))
+    fn = lib.mapx_colsum_bf16 if half else lib.mapx_colsum
+    check(fn(x.data_ptr(), x.stride(0), M, Nn, None if defer else ptr(out), ptr(ws), ws.numel(), stream()))
     if defer:
         defer_sum(out, ws.view(torch.float32), Nn, COLSUM_CHUNKS, Nn)
     return out
@@ -1946,36 +1916,20 @@ def row_sliceable(x):
 
 
 def relu_mask_colsum(dy, y, db=None, defer=False):
-    """-> (dz = y > 0 ? dy : 0, db = colsum(dz)) in one pass.  dy may be a column slice."""
-    if is_bf16(dy):
-        if dy.stride(1) != 1:
-            dy = dy.contiguous()
-        if y.stride(1) != 1:
-            y = y.contiguous()
-        M, Nn = dy.shape
-        dz = torch.empty(M, Nn, dtype=BF16, device=dy.device)
-        later = defer and db is not None
-        if db is None:
-            db = torch.empty(Nn, dtype=torch.float32, device=dy.device)
-        ws, chunks = _partials_h(Nn, dy.device, later)
-        check(lib.mapx_relu_mask_colsum_bf16(dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), M, Nn, ptr(dz),
-                                             None if later else ptr(db), ptr(ws), ws.numel(), stream()))
-        if later:
-            defer_sum(db, ws.view(torch.float32), Nn, chunks, Nn)
-        return dz, db
-    if not row_sliceable(dy):
-        dy = dy.contiguous()
-    if not row_sliceable(y):
-        y = y.contiguous()
+    """-> (dz = y > 0 ? dy : 0, db = colsum(dz)) in one pass.  dy may be a column slice.  fp32: dz carries its
+    magnitude record."""
+    half = is_bf16(dy)
+    dy, y = _colsum_operand(dy, half), _colsum_operand(y, half)
     M, Nn = dy.shape
-    dz = torch.empty(M, Nn, dtype=torch.float32, device=dy.device)
+    dz = torch.empty(M, Nn, dtype=BF16 if half else torch.float32, device=dy.device)
     defer = defer and db is not None
     if db is None:
         db = torch.empty(Nn, dtype=torch.float32, device=dy.device)
     ws = _partials(Nn, dy.device, defer)
-    rec = amax_record(dy.device)
-    check(lib.mapx_relu_mask_colsum(dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), M, Nn, ptr(dz),
-                                    None if defer else ptr(db), ptr(ws), ws.numel(), ptr(rec), stream()))
+    rec = None if half else amax_record(dy.device)
+    fn = lib.mapx_relu_mask_colsum_bf16 if half else lib.mapx_relu_mask_colsum
+    check(fn(dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), M, Nn, ptr(dz), None if defer else ptr(db), ptr(ws),
+             ws.numel(), *(() if half else (ptr(rec),)), stream()))
     if defer:
         defer_sum(db, ws.view(torch.float32), Nn, COLSUM_CHUNKS, Nn)
     return tag(dz, rec), db
@@ -1983,29 +1937,11 @@ def relu_mask_colsum(dy, y, db=None, defer=False):
 
 def cross_bwd_pre_colsum(g, x0, u, dx0=None, db=None, defer=False, plus_g=False):
     """-> (t = g*x0, dx0 (+)= g*u (+ g if plus_g), db = colsum(t)) in one pass.  g may be a column slice.
-    bf16 mode: g, x0, u, t bf16; the running dx0 and db fp32."""
-    if is_bf16(g):
-        if g.stride(1) != 1:
-            g = g.contiguous()
-        M, Nn = g.shape
-        t = torch.empty(M, Nn, dtype=BF16, device=g.device)
-        acc = dx0 is not None
-        if dx0 is None:
-            dx0 = torch.empty(M, Nn, dtype=torch.float32, device=g.device)
-        later = defer and db is not None
-        if db is None:
-            db = torch.empty(Nn, dtype=torch.float32, device=g.device)
-        ws, chunks = _partials_h(Nn, g.device, later)
-        check(lib.mapx_cross_bwd_pre_colsum_bf16(g.data_ptr(), g.stride(0), ptr(x0), ptr(u), M, Nn, ptr(t), ptr(dx0),
-                                                 int(acc) | (2 if plus_g else 0), None if later else ptr(db), ptr(ws),
-                                                 ws.numel(), stream()))
-        if later:
-            defer_sum(db, ws.view(torch.float32), Nn, chunks, Nn)
-        return t, dx0, db
-    if not row_sliceable(g):
-        g = g.contiguous()
+    bf16 mode: g, x0, u, t bf16; the running dx0 and db fp32.  fp32: t carries its magnitude record."""
+    half = is_bf16(g)
+    g = _colsum_operand(g, half)
     M, Nn = g.shape
-    t = torch.empty(M, Nn, dtype=torch.float32, device=g.device)
+    t = torch.empty(M, Nn, dtype=BF16 if half else torch.float32, device=g.device)
     acc = dx0 is not None
     if dx0 is None:
         dx0 = torch.empty(M, Nn, dtype=torch.float32, device=g.device)
@@ -2013,10 +1949,10 @@ def cross_bwd_pre_colsum(g, x0, u, dx0=None, db=None, defer=False, plus_g=False)
     if db is None:
         db = torch.empty(Nn, dtype=torch.float32, device=g.device)
     ws = _partials(Nn, g.device, defer)
-    rec = amax_record(g.device)
-    check(lib.mapx_cross_bwd_pre_colsum(g.data_ptr(), g.stride(0), ptr(x0), ptr(u), M, Nn, ptr(t), ptr(dx0),
-                                        int(acc) | (2 if plus_g else 0),
-                                        None if defer else ptr(db), ptr(ws), ws.numel(), ptr(rec), stream()))
+    rec = None if half else amax_record(g.device)
+    fn = lib.mapx_cross_bwd_pre_colsum_bf16 if half else lib.mapx_cross_bwd_pre_colsum
+    check(fn(g.data_ptr(), g.stride(0), ptr(x0), ptr(u), M, Nn, ptr(t), ptr(dx0), int(acc) | (2 if plus_g else 0),
+             None if defer else ptr(db), ptr(ws), ws.numel(), *(() if half else (ptr(rec),)), stream()))
     if defer:
         defer_sum(db, ws.view(torch.float32), Nn, COLSUM_CHUNKS, Nn)
     return tag(t, rec), dx0, db
@@ -2104,10 +2040,7 @@ def linear_bwd_weight_batched(dys, xs, outs):
         if d.shape != (Bn, Nn) or x.shape != (Bn, K) or o.shape != (Nn, K) or not (d.is_contiguous() and x.is_contiguous()
                                                                                    and o.is_contiguous()):
             raise ValueError("linear_bwd_weight_batched: equal shapes, contiguous operands")
-    tiles = math.ceil(Nn / 128) * math.ceil(K / 128) * cnt
-    ns = 1
-    while ns < 16 and tiles * ns * 2 <= 288 and Bn // (ns * 2) >= 256:
-        ns *= 2
+    ns = _splits_wide_tiles(Nn, K, Bn, count=cnt)
     ws = scratch(cnt * lib.mapx_gemm_splitk_workspace_bytes(Nn, K, ns), dys[0].device) if ns > 1 else None
     PP = C.c_void_p * cnt
     scales = None

@@ -605,6 +605,49 @@ def test_colsum_family(ops, N):
                 torch.testing.assert_close(db2.cpu().double(), t_want.double().sum(0), rtol=0, atol=_db_bound(t_want))
 
 
+@pytest.mark.parametrize("M", [70, 300])
+def test_deferred_sums_equal_immediate_sums(ops, M):
+    """`out` / `db` given and defer=True, then flush_deferred(): the same bits as the call that sums at once, for the
+    three column-sum wrappers in fp32 and bf16 and for linear_bwd_weight on the bf16 streaming kernel (N = 3, K = 20).
+    M = 70: fewer rows than the 128 row chunks; M = 300: three rows per chunk, the last used chunk partial.
+    N = 5: fp32 colsum only (the fp32 fused forms need N % 4 == 0) and the bf16 column-pair form; 12: the fp32 32-lane
+    form, bf16 column pairs; 136: the fp32 64-lane form, the bf16 8-column form; 264: the fp32 32-lane form over more
+    than one column block, the bf16 8-column form."""
+    ops.flush_deferred()
+    nan = lambda *shape: torch.full(shape, float("nan"), device=DEV)
+
+    def flushed(*outs):
+        assert all(bool(torch.isnan(o).all()) for o in outs)          # nothing summed yet
+        ops.flush_deferred()
+        return outs
+
+    for N in (5, 12, 136, 264):
+        g = torch.Generator().manual_seed(M + N)
+        for dt in (F32, BF):
+            half = dt == BF
+            x, y, x0, u = (_rand(g, M, N).to(dt).to(DEV) for _ in range(4))
+            now = ops.colsum(x, out=nan(N))
+            later, = flushed(ops.colsum(x, out=nan(N), defer=True))
+            assert torch.equal(later, now), (N, dt)
+            if N % 4 and not half:
+                continue
+            dz, db = ops.relu_mask_colsum(x, y, db=nan(N))
+            dz2, db2 = ops.relu_mask_colsum(x, y, db=nan(N), defer=True)
+            flushed(db2)
+            assert torch.equal(dz2, dz) and torch.equal(db2, db), (N, dt)
+            t, dx0, db = ops.cross_bwd_pre_colsum(x, x0, u, db=nan(N))
+            t2, dx02, db2 = ops.cross_bwd_pre_colsum(x, x0, u, db=nan(N), defer=True)
+            flushed(db2)
+            assert torch.equal(t2, t) and torch.equal(dx02, dx0) and torch.equal(db2, db), (N, dt)
+    N, K = 3, 20
+    g = torch.Generator().manual_seed(M)
+    dy, x = _rand(g, M, N).to(BF).to(DEV), _rand(g, M, K).to(BF).to(DEV)
+    assert ops._skinny_h(N, K, x)
+    now = ops.linear_bwd_weight(dy, x, out=nan(N, K))
+    later, = flushed(ops.linear_bwd_weight(dy, x, out=nan(N, K), defer=True))
+    assert torch.equal(later, now) and not bool(torch.isnan(now).any())
+
+
 def test_bf16_wrappers_copy_a_column_strided_operand(ops):
     """The bf16 wrappers .contiguous() an operand with a non-unit column stride (ops.py: colsum "if x.stride(1) != 1",
     relu_mask_colsum, cross_bwd_pre_colsum, act_bwd likewise): equality with the dense call's summation order is owed
