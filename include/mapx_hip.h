@@ -790,6 +790,48 @@ int mapx_vocab_map(const int32_t* slot_of_row, const int32_t* slot_entry, const 
                    const int32_t* n_kept, int64_t n, int64_t base, int64_t* ids_out, int64_t ld_out,
                    hipStream_t stream);
 
+/* ------------------------------------------------------------------ raw delimited text -> int64 columns
+ * read_feat of data_preprocess/proc_avazu.py:26-85 and proc_criteo.py:24-88: one chunk of the raw file, cut at a
+ * line end, lies on the device as bytes; the outputs are the columns mapx_vocab_* take.
+ * (Added inside ABI 48: purely additive, no existing entry changed; a binding that needs them finds them by name.)
+ *
+ * buf [n_bytes] u8, 16-byte aligned, n_bytes <= 2^30; the allocation holds at least round_up(n_bytes, 16) bytes: the
+ * kernels load 16 bytes at a time up to that bound and never beyond; what the pad bytes hold changes no result.
+ *  index   line_start [<= max_lines] = byte offset of every non-blank line, line_no [<= max_lines] = its physical line
+ *          number inside the chunk (0-based, blank lines counted).  A line ends at '\n' (or at n_bytes); one '\r'
+ *          directly in front of that is stripped; a line empty after that is blank and skipped.  counts [2] =
+ *          {non-blank lines, '\n' bytes}: when counts[0] > max_lines only the first max_lines entries were written.
+ *          Three launches (tile counts, scan, fill), integer only, no atomics.
+ *  parse   one lane per line.  Source field f of `schema` (a HOST pointer; the table travels as a kernel argument)
+ *          is of kind[f] and writes out[(out_col[f] + j) * ld + row0 + line], j < 4 for YYMMDDHH (weekday with
+ *          Monday = 0, day, hour, weekday > 4), j = 0 otherwise, nothing for SKIP:
+ *            INT     -?[0-9]{1,18}
+ *            BUCKET  empty -> -1; INT syntax, v <= 2 -> v, else the number of thresholds <= v
+ *                    (thresholds [n_thresholds] i64 ascending: entry b-1 = the smallest v with floor(log(v)^2) >= b)
+ *            HEX     empty -> -1; [0-9a-f]{1,14} -> (value << 4) | width
+ *          n_cols = number of output columns (bounds out_col), ld >= row0 + n_lines.  *err (one u64, set by the
+ *          entry to all ones) receives by integer atomicMin (line_no << 32) | (source column << 16) | reason of
+ *          every bad line: the smallest line, then column, on every run.  A bad line writes only inside its row.
+ *          A wave owns 64 consecutive lines; mode 0: it stages their byte span in LDS when the span fits
+ *          mapx_rawtext_window_bytes(), else reads global memory; mode 1: every wave reads global memory. */
+enum { MAPX_RT_SKIP = 0, MAPX_RT_INT = 1, MAPX_RT_BUCKET = 2, MAPX_RT_HEX = 3, MAPX_RT_YYMMDDHH = 4 };
+enum { MAPX_RT_E_QUOTE = 1, MAPX_RT_E_FEW = 2, MAPX_RT_E_MANY = 3, MAPX_RT_E_INT = 4, MAPX_RT_E_HEX = 5,
+       MAPX_RT_E_DATE = 6 };
+#define MAPX_RT_MAX_FIELDS 64
+typedef struct mapx_rawtext_schema {
+  int32_t delimiter;                      /* the byte between fields */
+  int32_t n_fields;                       /* source fields per line, <= MAPX_RT_MAX_FIELDS */
+  uint8_t kind[MAPX_RT_MAX_FIELDS];       /* MAPX_RT_* per source field */
+  int16_t out_col[MAPX_RT_MAX_FIELDS];    /* first output column per source field */
+} mapx_rawtext_schema;
+size_t mapx_rawtext_index_workspace_bytes(int64_t n_bytes);
+int mapx_rawtext_index(const uint8_t* buf, int64_t n_bytes, void* workspace, size_t workspace_bytes,
+                       int32_t* line_start, int32_t* line_no, int64_t max_lines, int32_t* counts, hipStream_t stream);
+int mapx_rawtext_parse(const uint8_t* buf, int64_t n_bytes, const int32_t* line_start, const int32_t* line_no,
+                       int64_t n_lines, const mapx_rawtext_schema* schema, const int64_t* thresholds, int n_thresholds,
+                       int64_t* out, int64_t ld, int64_t row0, int n_cols, uint64_t* err, int mode, hipStream_t stream);
+int mapx_rawtext_window_bytes(void);
+
 /* ------------------------------------------------------------------ FGCNN backbone
  * models.py:325-407, layers.py:204-251 (FGCNNBlock) and :105-137 (InnerProductLayer, output="inner_product").
  * All tensors fp32 and dense, [B, C, H, E] with E % 4 == 0 and 16-byte aligned; at most 32 channels, odd kernel

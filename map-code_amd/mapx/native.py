@@ -158,6 +158,10 @@ SIGNATURES = {
     "mapx_vocab_rank_keys": (_i, [_p, _p, _i64, C.c_int32, _p, _p]),
     "mapx_vocab_assign": (_i, [_p, _p, _p, _p, _i64, C.c_int32, _p, _p, _p, _p, _p]),
     "mapx_vocab_map": (_i, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p]),
+    "mapx_rawtext_index_workspace_bytes": (_sz, [_i64]),
+    "mapx_rawtext_index": (_i, [_p, _i64, _p, _sz, _p, _p, _i64, _p, _p]),
+    "mapx_rawtext_parse": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _i, _p, _i64, _i64, _i, _p, _i, _p]),
+    "mapx_rawtext_window_bytes": (_i, []),
     "mapx_replay_coef_table_bytes": (_sz, [_i]),
     "mapx_replay_coef_table": (_i, [_p, _i, _i, _d, _d, _p, _p, _p]),
     "mapx_table_adam": (_i, [_p, _p, _p, _i64, _i, _f, _p, _p, _p, _i64, _f, _p, _p, _i64, _i64, _p, _p, _p, _p,
@@ -210,6 +214,15 @@ class LazyRows(C.Structure):
                 ("last", _p), ("sched", _p), ("sched_len", _i), ("done", _p),
                 ("aux", _p), ("aux_len", _i), ("aux_rows", _i),
                 ("beta1", _d), ("beta2", _d), ("eps", _d), ("coef_opt", _p)]
+
+
+RT_MAX_FIELDS = 64
+
+
+class RawtextSchema(C.Structure):
+    """mapx_rawtext_schema (include/mapx_hip.h)."""
+    _fields_ = [("delimiter", C.c_int32), ("n_fields", C.c_int32), ("kind", C.c_uint8 * RT_MAX_FIELDS),
+                ("out_col", C.c_int16 * RT_MAX_FIELDS)]
 
 
 class MapxError(RuntimeError):

@@ -1,0 +1,64 @@
+"""Raw Avazu / Criteo file -> the dataset directory mapx/dataset.py reads, on the GPU:
+
+    python -m mapx.preprocess --dataset avazu|criteo --raw PATH --n_core K --out DIR [--name NAME] [--chunk_mb M]
+                              [--split a,b,c]
+
+read_feat (mapx/rawtext.py over csrc/rawtext.hip) and generate_dataset (mapx/vocab.py over csrc/vocab.hip) of the
+reference's data_preprocess/proc_avazu.py / proc_criteo.py in one pass: `<name>-meta.json`, `<name>.npz` and, with
+--split, a seeded random `split.pkl` (the reference's own split files come from split_criteo_x4.py and are used as
+they are when present)."""
+import argparse
+import os
+import sys
+
+
+def _split(text):
+    try:
+        parts = tuple(float(x) for x in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: three fractions a,b,c")
+    if len(parts) != 3 or min(parts) < 0 or abs(sum(parts) - 1.0) > 1e-6:
+        raise argparse.ArgumentTypeError(f"{text!r}: three non-negative fractions that sum to 1")
+    return parts
+
+
+def _positive(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: an integer")
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: must be at least 1")
+    return v
+
+
+def parser():
+    p = argparse.ArgumentParser(prog="python -m mapx.preprocess", description=__doc__.split("\n\n")[0])
+    p.add_argument("--dataset", required=True, choices=("avazu", "criteo"))
+    p.add_argument("--raw", required=True, help="train.gz / train.txt (a .gz path is streamed through gzip)")
+    p.add_argument("--n_core", required=True, type=_positive, help="keep values seen at least this often")
+    p.add_argument("--out", required=True, help="dataset directory")
+    p.add_argument("--name", default=None, help="file prefix inside --out (default: the dataset's name)")
+    p.add_argument("--chunk_mb", type=_positive, default=256, help="bytes of the file on the device at a time (<= 1024)")
+    p.add_argument("--split", type=_split, default=None, help="train,valid,test fractions of a seeded random split.pkl")
+    return p
+
+
+def main(argv=None):
+    p = parser()
+    args = p.parse_args(argv)
+    if args.chunk_mb > 1024:
+        p.error("--chunk_mb: at most 1024")
+    if not os.path.isfile(args.raw):
+        p.error(f"--raw: {args.raw} is not a file")
+    from . import rawtext, vocab
+    meta, input_size = vocab.generate_dataset_from_text(args.raw, rawtext.SCHEMAS[args.dataset], args.n_core, args.out,
+                                                        args.name or args.dataset, chunk_bytes=args.chunk_mb << 20,
+                                                        split=args.split)
+    print(f"{args.out}: {len(meta['index'])} rows, {len(meta['field_names']) - 1} fields, input_size {input_size}, "
+          f"avg_ctr {meta['avg_ctr']:.6f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

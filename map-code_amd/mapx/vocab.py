@@ -106,17 +106,20 @@ def build_field(keys, n_core, base, out_col, name="", capacity=None):
     return FieldVocab(name, ranked_keys[:k], ranked_counts[:k], base, U)
 
 
-def build_vocab(columns, n_core, device="cuda"):
+def build_vocab(columns, n_core, device="cuda", decoders=None):
     """columns: ordered {field name: raw column [N]} (the reference's valid_fields without 'click'), host arrays or
     device int64 tensors.  -> (feat_ids int64 [N, F] on the device, [FieldVocab], feat_map {str: id},
-    input_size) — `feat_map` as proc_avazu.py:213-250 builds it, `input_size` = len(feat_map)."""
+    input_size) — `feat_map` as proc_avazu.py:213-250 builds it, `input_size` = len(feat_map).
+    decoders: {field name: code -> str} for tensor columns whose codes do not print as themselves (the hash-string
+    codes of mapx.rawtext); absent names print as integers."""
     names = list(columns)
+    decoders = decoders or {}
     dec, cols = {}, []
     for name in names:
         c = columns[name]
         if torch.is_tensor(c):
             cols.append(c.to(device=device, dtype=torch.int64).contiguous())
-            dec[name] = lambda v: str(int(v))
+            dec[name] = decoders.get(name, lambda v: str(int(v)))
         else:
             codes, dec[name] = encode_column(c)
             cols.append(torch.as_tensor(codes).to(device))
@@ -138,7 +141,7 @@ def build_vocab(columns, n_core, device="cuda"):
 
 
 def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types=None, seed=42, device="cuda",
-                     split=None):
+                     split=None, string_columns=None, decoders=None, shuffle=True):
     """The whole of reference generate_dataset() (proc_avazu.py:193-302 / proc_criteo.py:90-196) for raw columns
     held in memory: rows shuffled by numpy's seeded permutation (np.random.seed(42); shuffle(arange(N)) —
     :194-199), vocabulary and ids on the GPU (build_vocab), the reference's meta JSON (index, num_pos, num_neg,
@@ -147,18 +150,33 @@ def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types
     `<name>.npz`).  feat_types: {field: '<cat>' | '<num>'} (default all '<cat>', proc_avazu.py:24); a raw value of
     -1 gets the '<oov>' type (proc_avazu.py:258-261, proc_criteo.py:161-166).
     split: None, or (train, valid, test) fractions for a seeded random `split.pkl` (the reference's own split
-    files come from split_criteo_x4.py — scikit-learn's StratifiedKFold — and are used as they are when present)."""
+    files come from split_criteo_x4.py — scikit-learn's StratifiedKFold — and are used as they are when present).
+    Columns (and labels) may be device int64 tensors (mapx.rawtext): the seeded permutation is still numpy's, on
+    the host; the rows are gathered on the device.  string_columns: names whose values were strings in the raw
+    file: no row of theirs gets the '<oov>' type, because the reference compares a string with -1 there
+    (proc_criteo.py:162).  decoders: see build_vocab.  shuffle=False keeps the file's row order, as
+    proc_criteo.py:98-102 does unless it down-samples."""
     import json
     import os
     import pickle as pkl
     names = list(columns)
     feat_types = feat_types or {n: "<cat>" for n in names}
-    labels = np.asarray(labels)
+    string_columns = set(string_columns or ())
+    labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
     np.random.seed(seed)
     index = np.arange(len(labels))
-    np.random.shuffle(index)
+    if shuffle:
+        np.random.shuffle(index)
     labels = labels[index]
-    shuffled = {n: np.asarray(columns[n])[index] for n in names}
+    index_dev = None
+    shuffled = {}
+    for n in names:
+        if torch.is_tensor(columns[n]):
+            if index_dev is None:
+                index_dev = torch.from_numpy(index).to(columns[n].device)
+            shuffled[n] = columns[n].to(torch.int64)[index_dev]
+        else:
+            shuffled[n] = np.asarray(columns[n])[index]
     field_map, feat_type_map = {"<rsv>": 0}, {"<rsv>": 0}
     for n in names:
         field_map[n] = len(field_map)
@@ -166,13 +184,18 @@ def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types
             feat_type_map[feat_types[n]] = len(feat_type_map)
     if "<oov>" not in feat_type_map:
         feat_type_map["<oov>"] = len(feat_type_map)
-    feat_ids, _fields, feat_map, input_size = build_vocab(shuffled, n_core, device=device)
+    feat_ids, _fields, feat_map, input_size = build_vocab(shuffled, n_core, device=device, decoders=decoders)
     N = len(labels)
     field_ids = np.tile(np.array([field_map[n] for n in names], dtype=np.int32), (N, 1))
     type_ids = np.empty((N, len(names)), dtype=np.int64)
     for j, n in enumerate(names):
         col = shuffled[n]
-        missing = (col == -1) if col.dtype.kind in "iu" else np.zeros(N, dtype=bool)
+        if n in string_columns:
+            missing = np.zeros(N, dtype=bool)
+        elif torch.is_tensor(col):
+            missing = (col == -1).cpu().numpy()
+        else:
+            missing = (col == -1) if col.dtype.kind in "iu" else np.zeros(N, dtype=bool)
         type_ids[:, j] = np.where(missing, feat_type_map["<oov>"], feat_type_map[feat_types[n]])
     meta = {"index": index.tolist(), "num_pos": int(labels.sum()), "num_neg": int(N - labels.sum()),
             "avg_ctr": float(labels.mean()) if N else 0.0, "field_names": ["<rsv>"] + names, "field_map": field_map,
@@ -190,3 +213,15 @@ def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types
             pkl.dump({"train_index": np.sort(perm[:a]), "valid_index": np.sort(perm[a:b]),
                       "test_index": np.sort(perm[b:])}, f)
     return meta, input_size
+
+
+def generate_dataset_from_text(path, schema, n_core, data_dir, dataset_name, chunk_bytes=256 << 20, mode=0, seed=42,
+                               device="cuda", split=None):
+    """Raw file -> dataset directory: mapx.rawtext.read_columns (read_feat on the device), then generate_dataset
+    with the schema's field types, string columns, decoders and row order."""
+    from . import rawtext
+    labels, columns, decode, strings = rawtext.read_columns(path, schema, device=device, chunk_bytes=chunk_bytes,
+                                                            mode=mode)
+    return generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types=schema.feat_types, seed=seed,
+                            device=device, split=split, string_columns=strings, decoders=decode,
+                            shuffle=schema.shuffle)
