@@ -789,6 +789,38 @@ int mapx_vocab_assign(const int32_t* by_first, const int32_t* by_count, const in
 int mapx_vocab_map(const int32_t* slot_of_row, const int32_t* slot_entry, const int32_t* rank_of_entry,
                    const int32_t* n_kept, int64_t n, int64_t base, int64_t* ids_out, int64_t ld_out,
                    hipStream_t stream);
+/* A SAVED vocabulary applied to other rows: feat_map[key] if key in feat_map else feat_map[name-<oov>]
+ * (proc_avazu.py:252-257, proc_criteo.py:155-160) for all F <= MAPX_RT_MAX_FIELDS fields of a file at once.
+ * (Added inside ABI 48: purely additive, no existing entry changed; a binding that needs them finds them by name.)
+ * The ids of a feat_map are consecutive per field: id = base[f] + rank, <oov> = base[f] + n_keys[f]; only ranks are
+ * stored.  keys [n_keys_total] i64 = the kept raw values of all fields concatenated in id order, field f at
+ * [key_off[f], key_off[f+1]).  Field f owns slots [tab_off[f], tab_off[f+1]) of table_keys (i64) / table_rank (i32),
+ * both [n_slots_total]: a power of two of them, more than its keys (mapx_vocab_apply_table_slots(n) = the smallest
+ * power of two >= max(2, 2n); 0 for n outside [0, 2^30)), slot = hash(key) & (slots - 1), linear probing.
+ * key_off, tab_off [F+1], n_keys, base, flag, field_type [F] are device i64 arrays.  err [2] i32: err[0] = the bits
+ * below (0 = fine), err[1] = the smallest field index that set one (INT32_MAX: none); both set by the entry.
+ *  load    clears the slots and inserts every key with its rank (atomicCAS on the key word; which slot of a chain a
+ *          key takes depends on arrival, what a lookup finds does not).  bit 1: a key equals INT64_MIN, the empty
+ *          marker; bit 2: a field's slots are no power of two, not more than its keys, or outside the table;
+ *          bit 4: one key twice in one field.
+ *  apply   columns = a device array of F pointers, each a contiguous i64 [n] column (any 64-bit pattern but
+ *          INT64_MIN).  feat_ids[i * ld_ids + f] = base[f] + rank, or the <oov> id; with type_ids_opt,
+ *          type_ids[i * ld_types + f] = missing_type where flag[f] != 0 and the raw value is -1, else field_type[f]
+ *          (flag, field_type are not read otherwise).  ld_* >= F; nothing outside [n, F] of either is written.
+ *          oov_rows [F] i64 = rows per field that took the <oov> id (set by the entry; integer atomics, one per
+ *          workgroup and field).  bit 1: a value equals INT64_MIN (it is written as <oov>); bit 2 as above.  The
+ *          tables are only read.  mode 0: the ids of 64 rows x F fields pass through LDS and are stored along the
+ *          rows; mode 1: every id is stored by the lane that looked it up (one 8-byte store per row and field).
+ *          n = 0 and fields without keys are valid.  Results do not depend on the mode or on arrival order. */
+size_t mapx_vocab_apply_table_slots(int64_t n_keys);
+int mapx_vocab_apply_load(const int64_t* keys, const int64_t* key_off, const int64_t* tab_off, int n_fields,
+                          int64_t n_keys_total, int64_t n_slots_total, int64_t* table_keys, int32_t* table_rank,
+                          int32_t* err, hipStream_t stream);
+int mapx_vocab_apply(const int64_t* const* columns, int64_t n, int n_fields, const int64_t* table_keys,
+                     const int32_t* table_rank, const int64_t* tab_off, int64_t n_slots_total, const int64_t* n_keys,
+                     const int64_t* base, const int64_t* flag, const int64_t* field_type, int64_t missing_type,
+                     int64_t* feat_ids, int64_t ld_ids, int64_t* type_ids_opt, int64_t ld_types, int64_t* oov_rows,
+                     int32_t* err, int mode, hipStream_t stream);
 
 /* ------------------------------------------------------------------ raw delimited text -> int64 columns
  * read_feat of data_preprocess/proc_avazu.py:26-85 and proc_criteo.py:24-88: one chunk of the raw file, cut at a

@@ -16,17 +16,9 @@
 // 16-byte table slot per row.
 #include "../../include/mapx_hip.h"
 #include "common.h"
+#include "vocab_hash.h"
 
 namespace mapx {
-
-constexpr int64_t kVocabEmpty = INT64_MIN;       // key value no column may hold
-
-__device__ inline uint64_t vocab_hash(uint64_t x) {   // splitmix64 finaliser: raw ids are hashes or small ints
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
 
 __global__ void __launch_bounds__(256) vocab_table_init_kernel(int64_t* __restrict__ tkey, int32_t* __restrict__ tcount,
                                                                int32_t* __restrict__ tfirst, int64_t cap) {

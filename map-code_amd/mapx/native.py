@@ -158,6 +158,9 @@ SIGNATURES = {
     "mapx_vocab_rank_keys": (_i, [_p, _p, _i64, C.c_int32, _p, _p]),
     "mapx_vocab_assign": (_i, [_p, _p, _p, _p, _i64, C.c_int32, _p, _p, _p, _p, _p]),
     "mapx_vocab_map": (_i, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p]),
+    "mapx_vocab_apply_table_slots": (_sz, [_i64]),
+    "mapx_vocab_apply_load": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _p, _p]),
+    "mapx_vocab_apply": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _p]),
     "mapx_rawtext_index_workspace_bytes": (_sz, [_i64]),
     "mapx_rawtext_index": (_i, [_p, _i64, _p, _sz, _p, _p, _i64, _p, _p]),
     "mapx_rawtext_parse": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _i, _p, _i64, _i64, _i, _p, _i, _p]),

@@ -2,11 +2,14 @@
 
     python -m mapx.preprocess --dataset avazu|criteo --raw PATH --n_core K --out DIR [--name NAME] [--chunk_mb M]
                               [--split a,b,c]
+    python -m mapx.preprocess --dataset avazu|criteo --raw PATH --vocab META.json --out DIR [...]
 
 read_feat (mapx/rawtext.py over csrc/rawtext.hip) and generate_dataset (mapx/vocab.py over csrc/vocab.hip) of the
 reference's data_preprocess/proc_avazu.py / proc_criteo.py in one pass: `<name>-meta.json`, `<name>.npz` and, with
 --split, a seeded random `split.pkl` (the reference's own split files come from split_criteo_x4.py and are used as
-they are when present)."""
+they are when present).  With --vocab instead of --n_core nothing is fitted: the file is translated through the
+feat_map saved in META.json by an earlier run (mapx/vocab.py Vocabulary over csrc/vocab_apply.hip), values that map
+does not hold take their field's <oov> id, and the rows stay in file order."""
 import argparse
 import os
 import sys
@@ -36,7 +39,9 @@ def parser():
     p = argparse.ArgumentParser(prog="python -m mapx.preprocess", description=__doc__.split("\n\n")[0])
     p.add_argument("--dataset", required=True, choices=("avazu", "criteo"))
     p.add_argument("--raw", required=True, help="train.gz / train.txt (a .gz path is streamed through gzip)")
-    p.add_argument("--n_core", required=True, type=_positive, help="keep values seen at least this often")
+    how = p.add_mutually_exclusive_group(required=True)
+    how.add_argument("--n_core", type=_positive, help="fit a vocabulary: keep values seen at least this often")
+    how.add_argument("--vocab", metavar="META.json", help="encode with the feat_map of an earlier run's <name>-meta.json")
     p.add_argument("--out", required=True, help="dataset directory")
     p.add_argument("--name", default=None, help="file prefix inside --out (default: the dataset's name)")
     p.add_argument("--chunk_mb", type=_positive, default=256, help="bytes of the file on the device at a time (<= 1024)")
@@ -51,7 +56,18 @@ def main(argv=None):
         p.error("--chunk_mb: at most 1024")
     if not os.path.isfile(args.raw):
         p.error(f"--raw: {args.raw} is not a file")
+    if args.vocab is not None and not os.path.isfile(args.vocab):
+        p.error(f"--vocab: {args.vocab} is not a file")
     from . import rawtext, vocab
+    if args.vocab is not None:
+        meta, input_size = vocab.encode_dataset_from_text(args.raw, rawtext.SCHEMAS[args.dataset], args.vocab, args.out,
+                                                          args.name or args.dataset, chunk_bytes=args.chunk_mb << 20,
+                                                          split=args.split)
+        N = len(meta["index"])
+        share = sorted(((c / N if N else 0.0, n) for n, c in meta["oov_rows"].items()), key=lambda x: -x[0])[:3]
+        print(f"{args.out}: {N} rows, {len(meta['field_names']) - 1} fields, input_size {input_size}, "
+              f"avg_ctr {meta['avg_ctr']:.6f}; <oov> share " + ", ".join(f"{n} {s:.4f}" for s, n in share))
+        return 0
     meta, input_size = vocab.generate_dataset_from_text(args.raw, rawtext.SCHEMAS[args.dataset], args.n_core, args.out,
                                                         args.name or args.dataset, chunk_bytes=args.chunk_mb << 20,
                                                         split=args.split)

@@ -10,12 +10,21 @@ columns are resident on the device.
 Counting / ranking / translating are kernels of csrc/vocab.hip behind include/mapx_hip.h (mapx_vocab_*); the
 two stable sorts of a field's distinct values are the segment plans' radix sort (mapx_seg_plan).  Raw values
 are 64-bit integers: the hexadecimal hash strings of Avazu / Criteo parse to them exactly (`encode_column`),
-anything else is coded by first occurrence on the host.  There is no CPU path."""
+anything else is coded by first occurrence on the host.  There is no CPU path.
+
+A fitted vocabulary can be applied to other rows (a later day's log, a held-out file, a test file): `parse_meta`
+reads the `feat_map` of a `<name>-meta.json` back into per-field key arrays (pure host), `Vocabulary` holds them as
+lookup tables on the device and `encode` translates all fields of a file in one launch — the reference's own line
+`feat_map[key] if key in feat_map else feat_map[f'{name}-<oov>']` (proc_avazu.py:252-257) against a map saved
+earlier (csrc/vocab_apply.hip, mapx_vocab_apply*).  `encode_dataset_from_text` is the raw-file form."""
+import json
+import os
+
 import numpy as np
 import torch
 
 from . import ops
-from .native import MapxError, check, lib, ptr, require_gpu, stream
+from .native import MapxError, RT_MAX_FIELDS, check, lib, ptr, require_gpu, stream
 
 RESERVED = ("<pad>", "<cls>", "<sep>", "<mask>", "<unused0>", "<unused1>", "<unused2>", "<unused3>", "<unused4>",
             "<unused5>")                                  # proc_avazu.py:213-220: ids 0..9
@@ -225,3 +234,294 @@ def generate_dataset_from_text(path, schema, n_core, data_dir, dataset_name, chu
     return generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types=schema.feat_types, seed=seed,
                             device=device, split=split, string_columns=strings, decoders=decode,
                             shuffle=schema.shuffle)
+
+
+# ------------------------------------------------------------------ a saved vocabulary applied to other rows
+class FieldKeys:
+    """One field of a saved feat_map: `keys` int64 [n] = the kept raw values in id order (the codes mapx.rawtext
+    gives the file's values), `base` the id of the first of them, `oov` = base + n the id of `<name>-<oov>`."""
+
+    def __init__(self, name, keys, base):
+        self.name, self.keys, self.base = name, np.ascontiguousarray(keys, dtype=np.int64), int(base)
+        self.oov = self.base + int(self.keys.shape[0])
+
+
+def _invert(name, kind, text, key):
+    """The printed value of a feat_map key -> the column's int64 code."""
+    from . import rawtext
+    if kind == rawtext.HEX:
+        if text == "-1":
+            return -1
+        try:
+            if not text:
+                raise ValueError(text)
+            return rawtext.encode_hex(text)
+        except ValueError:
+            raise ValueError(f"feat_map key {key!r}: {text!r} is not a value of the hash-string column {name!r} "
+                             f"(1 to 14 lower-case hexadecimal digits, or -1)") from None
+    try:
+        v = int(text)
+    except ValueError:
+        v = None
+    if v is None or str(v) != text or not (-(1 << 63) < v < (1 << 63)):
+        raise ValueError(f"feat_map key {key!r}: {text!r} is not an integer value of column {name!r} as it prints")
+    return v
+
+
+def parse_meta(meta, schema):
+    """`field_names` and `feat_map` of a `<name>-meta.json` (a dict, or the file's path) -> [FieldKeys], one per
+    field in order.  Pure host work.  The printed value of every key is inverted by the kind of the schema's
+    column: hash strings through rawtext.encode_hex ('-1', the empty field, -> -1), integers through int(), which
+    must print back as the text.  A feat_map written by the reference's own data_preprocess scripts for the same
+    raw file has exactly these keys (f'{name}-{value}' in Counter.most_common() order, then f'{name}-<oov>'), so it
+    loads too.  ValueError, naming the key or field, when the first ten entries are not RESERVED, the fields are
+    not the schema's columns (label excluded) in order, an id is not the next one, a field's `<name>-<oov>` is
+    missing or not its last id, a value does not invert, or two values of a field invert to one code."""
+    if not isinstance(meta, dict):
+        with open(os.fspath(meta)) as f:
+            meta = json.load(f)
+    kinds = {n: k for n, k in zip(schema.columns, schema.column_kinds) if n != schema.label}
+    names = list(kinds)
+    if list(meta["field_names"]) != ["<rsv>"] + names:
+        raise ValueError(f"field_names {list(meta['field_names'])} are not '<rsv>' and the {schema.name} schema's "
+                         f"columns {names}")
+    items = list(meta["feat_map"].items())
+    if [k for k, _ in items[:len(RESERVED)]] != list(RESERVED):
+        raise ValueError(f"feat_map: the first {len(RESERVED)} keys {[k for k, _ in items[:len(RESERVED)]]} are not "
+                         f"the reserved tokens {list(RESERVED)}")
+    for pos, (key, i) in enumerate(items):
+        if type(i) is not int or i != pos:
+            raise ValueError(f"feat_map key {key!r}: id {i!r} where the ids are consecutive from 0 (expected {pos})")
+    fields, pos = [], len(RESERVED)
+    for name in names:
+        prefix, start = name + "-", pos
+        while pos < len(items) and items[pos][0].startswith(prefix):
+            pos += 1
+        run = [k[len(prefix):] for k, _ in items[start:pos]]
+        if not run:
+            found = repr(items[pos][0]) if pos < len(items) else "the end of the map"
+            raise ValueError(f"feat_map: field {name!r} has no keys where the schema's column order puts them "
+                             f"(found {found})")
+        if run[-1] != "<oov>" or "<oov>" in run[:-1]:
+            raise ValueError(f"feat_map key {prefix + '<oov>'!r} is missing or is not the last id of field {name!r}")
+        codes = np.array([_invert(name, kinds[name], t, prefix + t) for t in run[:-1]], dtype=np.int64)
+        uniq, first = np.unique(codes, return_index=True)
+        if len(uniq) != len(codes):
+            twice = np.setdiff1d(np.arange(len(codes)), first)[0]
+            same = [prefix + t for t, c in zip(run[:-1], codes.tolist()) if c == codes[twice]]
+            raise ValueError(f"feat_map keys {same[0]!r} and {same[1]!r} of field {name!r} are one value ({codes[twice]})")
+        fields.append(FieldKeys(name, codes, start))
+    if pos != len(items):
+        raise ValueError(f"feat_map key {items[pos][0]!r}: not a key of the schema's columns {names} in order")
+    return fields
+
+
+def _is_pow2(c):
+    return c >= 1 and (c & (c - 1)) == 0
+
+
+class Vocabulary:
+    """The lookup tables of a saved vocabulary on the device (csrc/vocab_apply.hip).  fields: [FieldKeys] with
+    consecutive id ranges.  flags[f] != 0: a raw -1 in field f gets `missing_type` in type_ids (integer-origin
+    columns; string-origin columns have flag 0, as in generate_dataset); field_types[f]: the type id otherwise.
+    capacities: table slots per field instead of the default (the smallest power of two >= max(2, 2 n_f)); each a
+    power of two > n_f.  `feat_map`, `field_names`, `input_size` are those of the meta the vocabulary came from."""
+
+    def __init__(self, fields, device="cuda", capacities=None, flags=None, field_types=None, missing_type=0,
+                 decoders=None, meta=None):
+        F = len(fields)
+        if not 1 <= F <= RT_MAX_FIELDS:
+            raise ValueError(f"Vocabulary: 1 to {RT_MAX_FIELDS} fields")
+        n = [int(f.keys.shape[0]) for f in fields]
+        if capacities is None:
+            capacities = [int(lib.mapx_vocab_apply_table_slots(k)) for k in n]
+            if 0 in capacities:
+                raise ValueError("Vocabulary: a field holds at most 2^30 - 1 keys")
+        capacities = [int(c) for c in capacities]
+        if len(capacities) != F:
+            raise ValueError(f"Vocabulary: {len(capacities)} capacities for {F} fields")
+        for f, c, k in zip(fields, capacities, n):
+            if not _is_pow2(c) or c <= k or c > (1 << 31):
+                raise ValueError(f"field {f.name!r}: a capacity of {c} slots for {k} keys (a power of two > {k}, at "
+                                 f"most 2^31)")
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise MapxError("mapx.vocab.Vocabulary looks up on the device (HIP); there is no CPU path")
+        self.fields, self.device, self.capacities = list(fields), dev, capacities
+        self.decoders = decoders or {}
+        self.meta = meta
+        self.field_names = [f.name for f in fields]
+        self.missing_type = int(missing_type)
+        par = np.zeros((6, F + 1), dtype=np.int64)            # key_off, tab_off, n_keys, base, flag, field_type
+        par[0, 1:], par[1, 1:] = np.cumsum(n), np.cumsum(capacities)
+        par[2, :F], par[3, :F] = n, [f.base for f in fields]
+        par[4, :F] = [1] * F if flags is None else [int(bool(x)) for x in flags]
+        par[5, :F] = [0] * F if field_types is None else [int(x) for x in field_types]
+        self._par_host = par
+        self._par = torch.from_numpy(par).to(dev)
+        self.n_keys_total, self.n_slots = int(par[0, F]), int(par[1, F])
+        keys = np.concatenate([f.keys for f in fields]) if self.n_keys_total else np.zeros(0, dtype=np.int64)
+        self._keys = torch.from_numpy(keys).to(dev)
+        self._tkey = torch.empty(self.n_slots, dtype=torch.int64, device=dev)
+        self._trank = torch.empty(self.n_slots, dtype=torch.int32, device=dev)
+        err = torch.empty(2, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.mapx_vocab_apply_load(ptr(self._keys), ptr(self._par[0]), ptr(self._par[1]), F,
+                                            self.n_keys_total, self.n_slots, ptr(self._tkey), ptr(self._trank),
+                                            ptr(err), stream()))
+        bits, field = err.tolist()
+        self._raise(bits, field, "a key of the vocabulary")
+
+    def _raise(self, bits, field, what):
+        if not bits:
+            return
+        name = self.field_names[field] if 0 <= field < len(self.fields) else "?"
+        if bits & 1:
+            raise ValueError(f"field {name!r}: {what} is -2^63, the value the lookup tables reserve")
+        if bits & 4:
+            raise ValueError(f"field {name!r}: one key twice in the vocabulary")
+        raise MapxError(f"field {name!r}: the table slice of {self.capacities[field]} slots does not fit its keys")
+
+    @classmethod
+    def from_meta(cls, meta, schema, device="cuda", capacities=None):
+        """meta: the dict of a `<name>-meta.json`, or its path.  Field types and the '<oov>' type come from the
+        meta's feat_type_map when it has one, else they are numbered as generate_dataset numbers them."""
+        if not isinstance(meta, dict):
+            with open(os.fspath(meta)) as f:
+                meta = json.load(f)
+        fields = parse_meta(meta, schema)
+        tmap = meta.get("feat_type_map")
+        if tmap is None:
+            tmap = {"<rsv>": 0}
+            for f in fields:
+                tmap.setdefault(schema.feat_types[f.name], len(tmap))
+            tmap.setdefault("<oov>", len(tmap))
+        return cls(fields, device=device, capacities=capacities,
+                   flags=[f.name not in schema.string_columns for f in fields],
+                   field_types=[tmap[schema.feat_types[f.name]] for f in fields], missing_type=tmap["<oov>"],
+                   decoders={f.name: schema.decoder(f.name) for f in fields}, meta=meta)
+
+    @property
+    def feat_map(self):
+        if self.meta is not None:
+            return self.meta["feat_map"]
+        fm = {tok: i for i, tok in enumerate(RESERVED)}
+        for f in self.fields:
+            dec = self.decoders.get(f.name, lambda v: str(int(v)))
+            for v in f.keys.tolist():
+                fm[f"{f.name}-{dec(v)}"] = len(fm)
+            fm[f"{f.name}-<oov>"] = len(fm)
+        return fm
+
+    @property
+    def input_size(self):
+        return self.fields[-1].oov + 1
+
+    def _column(self, f, c):
+        """One input column as a contiguous device int64 vector."""
+        if torch.is_tensor(c):
+            if c.dtype != torch.int64 or c.dim() != 1:
+                raise TypeError(f"field {f.name!r}: a tensor column must be an int64 vector")
+            return c.to(self.device).contiguous()
+        a = np.asarray(c)
+        if a.dtype.kind in "iu":
+            codes, _ = encode_column(a)
+        elif a.dtype.kind in "USO":                             # hash strings: the codes the keys were inverted to
+            from . import rawtext
+            codes = np.array([-1 if s in ("-1", "") else rawtext.encode_hex(s) for s in map(str, a.tolist())],
+                             dtype=np.int64)
+        else:
+            raise TypeError(f"field {f.name!r}: dtype {a.dtype} (integers or hash strings)")
+        return torch.from_numpy(np.ascontiguousarray(codes)).to(self.device)
+
+    def encode(self, columns, type_ids=False, feat_ids_out=None, type_ids_out=None, mode=0):
+        """columns: {field name: column} in the vocabulary's field order, or a sequence of F columns; each a device
+        int64 vector or a host array (integers as they are; hash strings through rawtext.encode_hex).
+        -> (feat_ids int64 [N, F] on the device, oov_rows: F host ints, the rows per field that took the field's
+        <oov> id[, type_ids int64 [N, F]]).  One launch for all fields and one device -> host read (error word and
+        counters) at the end.  feat_ids_out / type_ids_out: int64 [N, F] views with unit column stride and any row
+        pitch to write into.  mode: see mapx_vocab_apply (0: row-contiguous stores through LDS, 1: strided stores).
+        ValueError, naming the field, when a column holds -2^63."""
+        F = len(self.fields)
+        if isinstance(columns, dict):
+            if list(columns) != self.field_names:
+                raise ValueError(f"encode: columns {list(columns)} are not the vocabulary's fields {self.field_names}")
+            columns = list(columns.values())
+        if len(columns) != F:
+            raise ValueError(f"encode: {len(columns)} columns for {F} fields")
+        cols = [self._column(f, c) for f, c in zip(self.fields, columns)]
+        N = cols[0].numel()
+        if any(c.numel() != N for c in cols):
+            raise ValueError("encode: columns of different lengths")
+        dev = self.device
+
+        def out(t, what):
+            if t is None:
+                return torch.empty(N, F, dtype=torch.int64, device=dev)
+            require_gpu(t)
+            if t.dtype != torch.int64 or tuple(t.shape) != (N, F) or (F > 1 and t.stride(1) != 1) or \
+                    (N > 1 and t.stride(0) < F):
+                raise TypeError(f"encode: {what} must be int64 [{N}, {F}] with unit column stride and a row pitch >= {F}")
+            return t
+        ids = out(feat_ids_out, "feat_ids_out")
+        types = out(type_ids_out, "type_ids_out") if (type_ids or type_ids_out is not None) else None
+        ld = lambda t: t.stride(0) if N > 1 else F             # (the pitch of a single row is never used)
+        col_ptrs = torch.tensor([c.data_ptr() for c in cols], dtype=torch.int64).to(dev)
+        stat = torch.empty(F + 1, dtype=torch.int64, device=dev)   # oov_rows [F] | the two error words
+        par = self._par
+        with torch.cuda.device(dev):
+            check(lib.mapx_vocab_apply(ptr(col_ptrs), N, F, ptr(self._tkey), ptr(self._trank), ptr(par[1]),
+                                       self.n_slots, ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(par[5]),
+                                       self.missing_type, ids.data_ptr(), ld(ids),
+                                       None if types is None else types.data_ptr(), F if types is None else ld(types),
+                                       ptr(stat), stat.data_ptr() + 8 * F, int(mode), stream()))
+        host = stat.cpu()                                       # the one read; it also ends the launch's use of cols
+        bits, field = host[F:].view(torch.int32).tolist()
+        self._raise(bits, field, "a value of the column")
+        oov_rows = host[:F].tolist()
+        return (ids, oov_rows, types) if types is not None else (ids, oov_rows)
+
+
+def encode_dataset_from_text(path, schema, meta_path, data_dir, dataset_name, chunk_bytes=256 << 20, split=None,
+                             seed=42, device="cuda"):
+    """Raw file -> dataset directory through the vocabulary SAVED in meta_path (the `<name>-meta.json` of an earlier
+    fit): mapx.rawtext.read_columns, then Vocabulary.encode.  Writes `<name>.npz` {feat_ids, field_ids, type_ids,
+    labels} and `<name>-meta.json` with the vocabulary's field_names / field_map / feat_type_map / feat_map verbatim
+    (same key order), this file's num_pos / num_neg / avg_ctr, index = 0..N-1 and `oov_rows` {field: rows that took
+    the field's <oov> id}; with `split`, a `split.pkl` by generate_dataset's seeded rule.  The rows stay in file
+    order: encode mode never shuffles (the ids of a row do not depend on the order, and a file that is scored or
+    evaluated is wanted as it is).  -> (meta, input_size)."""
+    import pickle as pkl
+    from . import rawtext
+    with open(os.fspath(meta_path)) as f:
+        saved = json.load(f)
+    voc = Vocabulary.from_meta(saved, schema, device=device)
+    labels, columns, _decode, _strings = rawtext.read_columns(path, schema, device=device, chunk_bytes=chunk_bytes)
+    feat_ids, oov_rows, type_ids = voc.encode(columns, type_ids=True)
+    labels = labels.cpu().numpy()
+    N, names = len(labels), voc.field_names
+    field_map = saved.get("field_map") or {n: i for i, n in enumerate(["<rsv>"] + names)}
+    feat_type_map = saved.get("feat_type_map")
+    if feat_type_map is None:
+        feat_type_map = {"<rsv>": 0}
+        for n in names:
+            feat_type_map.setdefault(schema.feat_types[n], len(feat_type_map))
+        feat_type_map.setdefault("<oov>", len(feat_type_map))
+    field_ids = np.tile(np.array([field_map[n] for n in names], dtype=np.int32), (N, 1))
+    meta = {"index": list(range(N)), "num_pos": int(labels.sum()), "num_neg": int(N - labels.sum()),
+            "avg_ctr": float(labels.mean()) if N else 0.0, "field_names": saved["field_names"], "field_map": field_map,
+            "feat_type_map": feat_type_map, "feat_map": saved["feat_map"],
+            "oov_rows": {n: int(c) for n, c in zip(names, oov_rows)}}
+    os.makedirs(data_dir, exist_ok=True)
+    with open(os.path.join(data_dir, f"{dataset_name}-meta.json"), "w") as f:
+        json.dump(meta, f, ensure_ascii=False)
+    np.savez(os.path.join(data_dir, f"{dataset_name}.npz"), feat_ids=feat_ids.cpu().numpy(), field_ids=field_ids,
+             type_ids=type_ids.cpu().numpy(), labels=labels.astype(np.int64))
+    if split is not None and not os.path.exists(os.path.join(data_dir, "split.pkl")):
+        rng = np.random.RandomState(seed)
+        perm = rng.permutation(N)
+        a, b = int(N * split[0]), int(N * (split[0] + split[1]))
+        with open(os.path.join(data_dir, "split.pkl"), "wb") as f:
+            pkl.dump({"train_index": np.sort(perm[:a]), "valid_index": np.sort(perm[a:b]),
+                      "test_index": np.sort(perm[b:])}, f)
+    return meta, voc.input_size
