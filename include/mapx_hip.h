@@ -31,7 +31,7 @@ typedef struct ihipStream_t* hipStream_t; /* opaque outside hipcc */
 #include <hip/hip_runtime_api.h>
 #endif
 
-#define MAPX_ABI_VERSION 48
+#define MAPX_ABI_VERSION 49
 
 #define MAPX_OK 0
 #define MAPX_EINVAL (-1)     /* bad argument (shape, null pointer, alignment) */
@@ -763,32 +763,29 @@ int mapx_add_layernorm_bwd_bf16(const mapx_bf16* dy, const mapx_bf16* x, const m
  * keys [n] i64 = the column's raw values (any 64-bit pattern but INT64_MIN).  Steps, each one launch:
  *  table_init  an open-addressing table of `capacity` (power of two, >= 2 x distinct values) slots:
  *              keys INT64_MIN, counts 0, first positions INT32_MAX;
- *  count       every row finds / claims its value's slot: count += 1, first = min(first, row);
- *              slot_of_row [n].  *err_flag |= 1: a key equals INT64_MIN; |= 2: table full;
- *  compact     occupied slots -> entries (order unspecified): slot_entry [capacity], entry_keys /
- *              entry_count / entry_first [>= distinct values]; n_entries_maxc [2] = {#entries, largest count};
+ *  count       every row finds / claims its value's slot: count += 1, first = min(first, row).
+ *              *err_flag |= 1: a key equals INT64_MIN; |= 2: table full;
+ *  compact     occupied slots -> entries (order unspecified): entry_keys / entry_count / entry_first
+ *              [>= distinct values]; n_entries_maxc [2] = {#entries, largest count};
  *  (the caller sorts the entries by first position, then stably by the keys of rank_keys:
  *   mapx_seg_plan twice -> by_first [U], by_count [U]: rank r holds entry by_first[by_count[r]])
  *  rank_keys   keys2[r] = max_count - entry_count[by_first[r]];
- *  assign      rank_of_entry [U]; ranked_keys / ranked_counts [U] = the values and counts in id order;
- *              *n_kept = number of values with count >= n_core (they are ranks 0 .. n_kept-1);
- *  map         ids_out[i * ld_out] = base + (rank < n_kept ? rank : n_kept)   (base + n_kept = <oov>). */
+ *  assign      ranked_keys / ranked_counts [U] = the values and counts in id order;
+ *              *n_kept = number of values with count >= n_core (they are ranks 0 .. n_kept-1).
+ * The column itself is translated through the fitted keys by mapx_vocab_apply_load / mapx_vocab_apply below (since
+ * ABI 49 the fit has no translation entry of its own). */
 int mapx_vocab_table_init(int64_t* table_keys, int32_t* table_count, int32_t* table_first, int64_t capacity,
                           hipStream_t stream);
 int mapx_vocab_count(const int64_t* keys, int64_t n, int64_t* table_keys, int32_t* table_count,
-                     int32_t* table_first, int64_t capacity, int32_t* slot_of_row, int* err_flag,
-                     hipStream_t stream);
+                     int32_t* table_first, int64_t capacity, int* err_flag, hipStream_t stream);
 int mapx_vocab_compact(const int64_t* table_keys, const int32_t* table_count, const int32_t* table_first,
-                       int64_t capacity, int32_t* slot_entry, int64_t* entry_keys, int32_t* entry_count,
-                       int32_t* entry_first, int32_t* n_entries_maxc, hipStream_t stream);
+                       int64_t capacity, int64_t* entry_keys, int32_t* entry_count, int32_t* entry_first,
+                       int32_t* n_entries_maxc, hipStream_t stream);
 int mapx_vocab_rank_keys(const int32_t* entry_count, const int32_t* by_first, int64_t n_entries, int32_t max_count,
                          int32_t* keys2, hipStream_t stream);
 int mapx_vocab_assign(const int32_t* by_first, const int32_t* by_count, const int32_t* entry_count,
-                      const int64_t* entry_keys, int64_t n_entries, int32_t n_core, int32_t* rank_of_entry,
-                      int64_t* ranked_keys, int32_t* ranked_counts, int32_t* n_kept, hipStream_t stream);
-int mapx_vocab_map(const int32_t* slot_of_row, const int32_t* slot_entry, const int32_t* rank_of_entry,
-                   const int32_t* n_kept, int64_t n, int64_t base, int64_t* ids_out, int64_t ld_out,
-                   hipStream_t stream);
+                      const int64_t* entry_keys, int64_t n_entries, int32_t n_core, int64_t* ranked_keys,
+                      int32_t* ranked_counts, int32_t* n_kept, hipStream_t stream);
 /* A SAVED vocabulary applied to other rows: feat_map[key] if key in feat_map else feat_map[name-<oov>]
  * (proc_avazu.py:252-257, proc_criteo.py:155-160) for all F <= MAPX_RT_MAX_FIELDS fields of a file at once.
  * (Added inside ABI 48: purely additive, no existing entry changed; a binding that needs them finds them by name.)

@@ -8,7 +8,7 @@
 // arrays — key i64, rank i32: a 12-byte probe — a power of two of them and more than n_f, so a linear probe always
 // meets an empty slot.  Slot = vocab_hash(key) & (slots_f - 1), as in the fit's table (vocab_hash.h).
 //
-//  load   clears the slots, then every key claims one with atomicCAS on the key word (as vocab_count_kernel does) and
+//  load   clears the slots, then every key claims one (vocab_claim of vocab_hash.h, as vocab_count_kernel does) and
 //         stores its rank.  Which slot a key of a collision chain gets depends on arrival; a lookup walks the chain
 //         up to the first empty slot, so what it finds does not.
 //  apply  a workgroup takes 64 rows x F fields at a time.  Wave w reads the 64 values of fields w, w+4, ... (a lane a
@@ -18,7 +18,9 @@
 //         contiguously along each row — F x 8 bytes per row, the whole tile one run when the pitch is F — instead of
 //         one 8-byte store per 64-byte line and field.  OOV rows: ballot + popcount per wave and field into an LDS
 //         counter that only that wave touches; one integer atomicAdd per workgroup and field at the end.
-//         mode 1 stores every id straight from the probing lane (the strided form of vocab_map_kernel), for comparison.
+//         mode 1 stores every id straight from the probing lane, one 8-byte store per row and field F x 8 bytes
+//         apart, for comparison.
+// The fit translates its own column through the same two steps (mapx/vocab.py: build_field, build_vocab).
 #include "../../include/mapx_hip.h"
 #include "common.h"
 #include "vocab_hash.h"
@@ -71,43 +73,13 @@ __global__ void __launch_bounds__(256) vocab_apply_load_kernel(const int64_t* __
       vocab_apply_error(err, 1, f);
       continue;
     }
-    const uint64_t mask = (uint64_t)cap - 1;
-    uint64_t s = vocab_hash((uint64_t)k) & mask;
-    for (int64_t probes = 0;; ++probes) {
-      if (probes >= cap) {
-        vocab_apply_error(err, 2, f);
-        break;
-      }
-      unsigned long long* cell = reinterpret_cast<unsigned long long*>(tkey + t0 + s);
-      long long seen = (long long)*reinterpret_cast<volatile unsigned long long*>(cell);
-      if (seen == kVocabEmpty)
-        seen = (long long)atomicCAS(cell, (unsigned long long)kVocabEmpty, (unsigned long long)k);
-      if (seen == kVocabEmpty) {                                  // claimed now
-        trank[t0 + s] = (int32_t)(j - s_koff[f]);
-        break;
-      }
-      if (seen == k) {                                            // another position of this field holds the same key
-        vocab_apply_error(err, 4, f);
-        break;
-      }
-      s = (s + 1) & mask;
+    uint64_t s;
+    switch (vocab_claim(tkey + t0, cap, k, &s)) {
+      case kVocabClaimed: trank[t0 + s] = (int32_t)(j - s_koff[f]); break;
+      case kVocabHeld: vocab_apply_error(err, 4, f); break;       // another position of this field holds the same key
+      case kVocabFull: vocab_apply_error(err, 2, f); break;
     }
   }
-}
-
-// rank of `v` among field f's keys, or nf (<oov>).  Plain loads; the walk ends at an empty slot and, whatever the
-// table holds, after `cap` slots.
-__device__ inline int32_t vocab_apply_probe(const int64_t* __restrict__ tkey, const int32_t* __restrict__ trank,
-                                            int64_t t0, int64_t cap, int64_t nf, int64_t v) {
-  const uint64_t mask = (uint64_t)cap - 1;
-  uint64_t s = vocab_hash((uint64_t)v) & mask;
-  for (int64_t probes = 0; probes < cap; ++probes) {
-    const int64_t k = tkey[t0 + s];
-    if (k == v) return trank[t0 + s];
-    if (k == kVocabEmpty) break;
-    s = (s + 1) & mask;
-  }
-  return (int32_t)nf;
 }
 
 template <bool DIRECT>

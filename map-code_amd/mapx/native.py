@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmapx_hip.so")
 
-MAPX_ABI_VERSION = 48
+MAPX_ABI_VERSION = 49
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_CROSS, EPI_ADD, EPI_RELU_MASK, EPI_RELU_MASK_COLSUM = range(7)
 
 _p, _i, _i64, _u64, _f, _d, _sz = (C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double,
@@ -153,11 +153,10 @@ SIGNATURES = {
     "mapx_add_layernorm_bwd_groups": (_i, [_i64, _i]),
     "mapx_add_layernorm_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _p, _p]),
     "mapx_vocab_table_init": (_i, [_p, _p, _p, _i64, _p]),
-    "mapx_vocab_count": (_i, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p]),
-    "mapx_vocab_compact": (_i, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "mapx_vocab_count": (_i, [_p, _i64, _p, _p, _p, _i64, _p, _p]),
+    "mapx_vocab_compact": (_i, [_p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "mapx_vocab_rank_keys": (_i, [_p, _p, _i64, C.c_int32, _p, _p]),
-    "mapx_vocab_assign": (_i, [_p, _p, _p, _p, _i64, C.c_int32, _p, _p, _p, _p, _p]),
-    "mapx_vocab_map": (_i, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _p]),
+    "mapx_vocab_assign": (_i, [_p, _p, _p, _p, _i64, C.c_int32, _p, _p, _p, _p]),
     "mapx_vocab_apply_table_slots": (_sz, [_i64]),
     "mapx_vocab_apply_load": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _p, _p]),
     "mapx_vocab_apply": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _p]),

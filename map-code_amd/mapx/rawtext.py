@@ -327,9 +327,6 @@ def read_columns(path, schema, device="cuda", chunk_bytes=256 << 20, mode=0, tim
     the set of string-origin columns), all tensors on the device.  `.gz` paths are streamed through gzip.
     mode: 0 = every wave stages its lines in LDS when they fit, 1 = every wave reads global memory.
     timing: a dict that receives the seconds spent reading the file, copying to the device and on the device."""
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise MapxError("mapx.rawtext parses on the device (HIP); there is no CPU path")
     path = os.fspath(path)
     gz = path.endswith(".gz")
     with (gzip.open(path, "rb") if gz else open(path, "rb")) as f:

@@ -7,8 +7,9 @@ columns are resident on the device.
     first occurrence — and one <oov> id per field (proc_avazu.py:247-250); every row's value is translated
     through it (:252-257).  The resulting matrix is `feat_ids` of the HDF5 file that code/dataset.py:20-40 reads.
 
-Counting / ranking / translating are kernels of csrc/vocab.hip behind include/mapx_hip.h (mapx_vocab_*); the
-two stable sorts of a field's distinct values are the segment plans' radix sort (mapx_seg_plan).  Raw values
+Counting / ranking are kernels of csrc/vocab.hip behind include/mapx_hip.h (mapx_vocab_*); the two stable sorts of a
+field's distinct values are the segment plans' radix sort (mapx_seg_plan); the rows are translated, and given their
+type_ids, through the vocabulary just fitted by the lookup kernel of csrc/vocab_apply.hip (below).  Raw values
 are 64-bit integers: the hexadecimal hash strings of Avazu / Criteo parse to them exactly (`encode_column`),
 anything else is coded by first occurrence on the host.  There is no CPU path.
 
@@ -69,32 +70,27 @@ class FieldVocab:
         return self.n_kept + 1
 
 
-def build_field(keys, n_core, base, out_col, name="", capacity=None):
-    """Ids of one field.  keys int64 [N] on the device; out_col: an int64 column view (stride = row length) that
-    receives the ids.  -> FieldVocab (device tensors)."""
-    require_gpu(keys, out_col)
+def fit_field(keys, n_core, base, name="", capacity=None):
+    """The vocabulary of one field: count, compact, rank (two stable sorts), n-core cut.  keys int64 [N] on the
+    device.  -> FieldVocab (device tensors).  No row is translated here."""
+    require_gpu(keys)
     if keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous():
-        raise TypeError("build_field: keys must be a contiguous int64 vector")
+        raise TypeError("fit_field: keys must be a contiguous int64 vector")
     N, dev = keys.numel(), keys.device
-    if out_col.dtype != torch.int64 or out_col.shape[0] != N or out_col.dim() != 1:
-        raise TypeError("build_field: out_col must be an int64 column of N rows")
     if N == 0:
         return FieldVocab(name, torch.empty(0, dtype=torch.int64, device=dev),
                           torch.empty(0, dtype=torch.int32, device=dev), base, 0)
     cap = capacity or max(64, 1 << int(np.ceil(np.log2(2 * N + 1))))
     i32 = dict(dtype=torch.int32, device=dev)
     tkey = torch.empty(cap, dtype=torch.int64, device=dev)
-    tcount, tfirst = torch.empty(cap, **i32), torch.empty(cap, **i32)
-    slot_of_row, err = torch.empty(N, **i32), torch.zeros(1, **i32)
+    tcount, tfirst, err = torch.empty(cap, **i32), torch.empty(cap, **i32), torch.zeros(1, **i32)
     check(lib.mapx_vocab_table_init(ptr(tkey), ptr(tcount), ptr(tfirst), cap, stream()))
-    check(lib.mapx_vocab_count(ptr(keys), N, ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(slot_of_row), ptr(err),
-                               stream()))
-    slot_entry = torch.empty(cap, **i32)
+    check(lib.mapx_vocab_count(ptr(keys), N, ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(err), stream()))
     ent_cap = min(N, cap)
     ekey = torch.empty(ent_cap, dtype=torch.int64, device=dev)
     ecount, efirst, nm = torch.empty(ent_cap, **i32), torch.empty(ent_cap, **i32), torch.zeros(2, **i32)
-    check(lib.mapx_vocab_compact(ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(slot_entry), ptr(ekey), ptr(ecount),
-                                 ptr(efirst), ptr(nm), stream()))
+    check(lib.mapx_vocab_compact(ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(ekey), ptr(ecount), ptr(efirst),
+                                 ptr(nm), stream()))
     e, (U, maxc) = int(err.item()), (int(x) for x in nm.tolist())          # offline path: host syncs are fine
     if e & 1:
         raise ValueError(f"field {name!r}: the value -2^63 is reserved by the vocabulary builder")
@@ -105,48 +101,116 @@ def build_field(keys, n_core, base, out_col, name="", capacity=None):
     keys2 = torch.empty(U, **i32)
     check(lib.mapx_vocab_rank_keys(ptr(ecount), ptr(by_first), U, maxc, ptr(keys2), stream()))
     by_count = ops.SegPlan(keys2, maxc + 1).perm
-    rank_of_entry, ranked_counts, n_kept = torch.empty(U, **i32), torch.empty(U, **i32), torch.zeros(1, **i32)
+    ranked_counts, n_kept = torch.empty(U, **i32), torch.zeros(1, **i32)
     ranked_keys = torch.empty(U, dtype=torch.int64, device=dev)
     check(lib.mapx_vocab_assign(ptr(by_first), ptr(by_count), ptr(ecount), ptr(ekey), U, int(n_core),
-                                ptr(rank_of_entry), ptr(ranked_keys), ptr(ranked_counts), ptr(n_kept), stream()))
-    check(lib.mapx_vocab_map(ptr(slot_of_row), ptr(slot_entry), ptr(rank_of_entry), ptr(n_kept), N, int(base),
-                             out_col.data_ptr(), out_col.stride(0), stream()))
+                                ptr(ranked_keys), ptr(ranked_counts), ptr(n_kept), stream()))
     k = int(n_kept.item())
     return FieldVocab(name, ranked_keys[:k], ranked_counts[:k], base, U)
 
 
-def build_vocab(columns, n_core, device="cuda", decoders=None):
-    """columns: ordered {field name: raw column [N]} (the reference's valid_fields without 'click'), host arrays or
-    device int64 tensors.  -> (feat_ids int64 [N, F] on the device, [FieldVocab], feat_map {str: id},
-    input_size) — `feat_map` as proc_avazu.py:213-250 builds it, `input_size` = len(feat_map).
-    decoders: {field name: code -> str} for tensor columns whose codes do not print as themselves (the hash-string
-    codes of mapx.rawtext); absent names print as integers."""
+def build_field(keys, n_core, base, out_col, name="", capacity=None):
+    """Ids of one field.  keys int64 [N] on the device; out_col: an int64 column view (stride = row length) that
+    receives the ids: fit_field, then the column through a one-field Vocabulary of the fitted keys.
+    -> FieldVocab (device tensors)."""
+    require_gpu(keys, out_col)
+    if out_col.dtype != torch.int64 or out_col.dim() != 1 or out_col.shape[0] != keys.numel():
+        raise TypeError("build_field: out_col must be an int64 column of N rows")
+    fv = fit_field(keys, n_core, base, name=name, capacity=capacity)
+    Vocabulary([fv], device=keys.device).encode([keys], feat_ids_out=out_col.unsqueeze(1))
+    return fv
+
+
+def _feat_map(fields, decoders):
+    """proc_avazu.py:213-250: the reserved tokens, then per field f'{name}-{value as printed}' of the kept values in
+    id order and f'{name}-<oov>'.  decoders: {field name: code -> str}; absent names print as integers."""
+    feat_map = {tok: i for i, tok in enumerate(RESERVED)}
+    for f in fields:
+        dec = decoders.get(f.name, lambda v: str(int(v)))
+        for v in f.keys.tolist():                               # (the one device -> host copy of a fitted field's keys)
+            feat_map[f"{f.name}-{dec(v)}"] = len(feat_map)
+        feat_map[f"{f.name}-<oov>"] = len(feat_map)
+        assert feat_map[f"{f.name}-<oov>"] == f.oov
+    return feat_map
+
+
+def _feat_type_map(names, feat_types):
+    """'<rsv>' = 0, the fields' types in order of first appearance, then '<oov>' (proc_avazu.py:211-231)."""
+    tmap = {"<rsv>": 0}
+    for n in names:
+        tmap.setdefault(feat_types[n], len(tmap))
+    tmap.setdefault("<oov>", len(tmap))
+    return tmap
+
+
+def _field_ids(field_map, names, n_rows):
+    return np.tile(np.array([field_map[n] for n in names], dtype=np.int32), (n_rows, 1))
+
+
+def _fit_encode(columns, n_core, device, decoders, types=None):
+    """build_vocab, and with types = (string_columns, feat_types, feat_type_map) also type_ids int64 [N, F] from the
+    same launches: the '<oov>' type where an integer-origin value is -1, else the field's own type."""
     names = list(columns)
     decoders = decoders or {}
-    dec, cols = {}, []
+    dec, cols, flags = {}, [], []
     for name in names:
         c = columns[name]
         if torch.is_tensor(c):
             cols.append(c.to(device=device, dtype=torch.int64).contiguous())
             dec[name] = decoders.get(name, lambda v: str(int(v)))
+            flags.append(True)
         else:
             codes, dec[name] = encode_column(c)
             cols.append(torch.as_tensor(codes).to(device))
+            flags.append(np.asarray(c).dtype.kind in "iu")
     N = cols[0].numel() if cols else 0
     if any(c.numel() != N for c in cols):
         raise ValueError("build_vocab: columns of different lengths")
-    feat_ids = torch.empty(N, len(names), dtype=torch.int64, device=device)
-    feat_map = {tok: i for i, tok in enumerate(RESERVED)}
     fields, base = [], len(RESERVED)
-    for f, (name, keys) in enumerate(zip(names, cols)):
-        fv = build_field(keys, n_core, base, feat_ids[:, f], name=name)
-        for v in fv.keys.cpu().tolist():
-            feat_map[f"{name}-{dec[name](v)}"] = len(feat_map)
-        feat_map[f"{name}-<oov>"] = len(feat_map)
-        assert feat_map[f"{name}-<oov>"] == fv.oov
-        fields.append(fv)
-        base = fv.oov + 1
-    return feat_ids, fields, feat_map, base
+    for name, keys in zip(names, cols):
+        fields.append(fit_field(keys, n_core, base, name=name))
+        base = fields[-1].oov + 1
+    feat_ids = torch.empty(N, len(names), dtype=torch.int64, device=device)
+    type_ids, field_types, missing_type = None, [0] * len(names), 0
+    if types is not None:
+        strings, feat_types, tmap = types
+        type_ids = torch.empty_like(feat_ids)
+        flags = [flag and n not in strings for n, flag in zip(names, flags)]
+        field_types, missing_type = [tmap[feat_types[n]] for n in names], tmap["<oov>"]
+    for g in range(0, len(names), RT_MAX_FIELDS):               # a Vocabulary holds at most RT_MAX_FIELDS fields
+        h = slice(g, g + RT_MAX_FIELDS)
+        voc = Vocabulary(fields[h], device=device, flags=flags[h], field_types=field_types[h],
+                         missing_type=missing_type)
+        voc.encode(cols[h], feat_ids_out=feat_ids[:, h], type_ids_out=None if type_ids is None else type_ids[:, h])
+    return feat_ids, fields, _feat_map(fields, dec), base, type_ids
+
+
+def build_vocab(columns, n_core, device="cuda", decoders=None):
+    """columns: ordered {field name: raw column [N]} (the reference's valid_fields without 'click'), host arrays or
+    device int64 tensors.  -> (feat_ids int64 [N, F] on the device, [FieldVocab], feat_map {str: id},
+    input_size) — `feat_map` as proc_avazu.py:213-250 builds it, `input_size` = len(feat_map).  Every field is fitted
+    (fit_field), then all columns are translated through the fitted keys, up to RT_MAX_FIELDS fields a launch.
+    decoders: {field name: code -> str} for tensor columns whose codes do not print as themselves (the hash-string
+    codes of mapx.rawtext); absent names print as integers."""
+    return _fit_encode(columns, n_core, device, decoders)[:4]
+
+
+def _write_dataset(data_dir, name, meta, feat_ids, field_ids, type_ids, labels, split, seed):
+    """`<name>-meta.json` and `<name>.npz` {feat_ids, field_ids, type_ids, labels} in the layout mapx/dataset.py reads;
+    with `split` = (train, valid, test) fractions and no `split.pkl` there yet, a seeded random one."""
+    import pickle as pkl
+    os.makedirs(data_dir, exist_ok=True)
+    with open(os.path.join(data_dir, f"{name}-meta.json"), "w") as f:
+        json.dump(meta, f, ensure_ascii=False)
+    np.savez(os.path.join(data_dir, f"{name}.npz"), feat_ids=feat_ids.cpu().numpy(), field_ids=field_ids,
+             type_ids=type_ids.cpu().numpy(), labels=labels.astype(np.int64))
+    if split is not None and not os.path.exists(os.path.join(data_dir, "split.pkl")):
+        N = len(labels)
+        perm = np.random.RandomState(seed).permutation(N)
+        a, b = int(N * split[0]), int(N * (split[0] + split[1]))
+        with open(os.path.join(data_dir, "split.pkl"), "wb") as f:
+            pkl.dump({"train_index": np.sort(perm[:a]), "valid_index": np.sort(perm[a:b]),
+                      "test_index": np.sort(perm[b:])}, f)
 
 
 def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types=None, seed=42, device="cuda",
@@ -157,20 +221,16 @@ def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types
     avg_ctr, field_names, field_map, feat_type_map, feat_map) and the table {feat_ids, field_ids, type_ids,
     labels}, written in the layout code/dataset.py:20-40 reads (here: mapx/dataset.py — `<name>-meta.json`,
     `<name>.npz`).  feat_types: {field: '<cat>' | '<num>'} (default all '<cat>', proc_avazu.py:24); a raw value of
-    -1 gets the '<oov>' type (proc_avazu.py:258-261, proc_criteo.py:161-166).
+    -1 gets the '<oov>' type (proc_avazu.py:258-261, proc_criteo.py:161-166), in the launch that translates the ids.
     split: None, or (train, valid, test) fractions for a seeded random `split.pkl` (the reference's own split
     files come from split_criteo_x4.py — scikit-learn's StratifiedKFold — and are used as they are when present).
     Columns (and labels) may be device int64 tensors (mapx.rawtext): the seeded permutation is still numpy's, on
     the host; the rows are gathered on the device.  string_columns: names whose values were strings in the raw
     file: no row of theirs gets the '<oov>' type, because the reference compares a string with -1 there
-    (proc_criteo.py:162).  decoders: see build_vocab.  shuffle=False keeps the file's row order, as
-    proc_criteo.py:98-102 does unless it down-samples."""
-    import json
-    import os
-    import pickle as pkl
+    (proc_criteo.py:162); host columns of string dtype are such columns too.  decoders: see build_vocab.
+    shuffle=False keeps the file's row order, as proc_criteo.py:98-102 does unless it down-samples."""
     names = list(columns)
     feat_types = feat_types or {n: "<cat>" for n in names}
-    string_columns = set(string_columns or ())
     labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
     np.random.seed(seed)
     index = np.arange(len(labels))
@@ -186,41 +246,16 @@ def generate_dataset(columns, labels, n_core, data_dir, dataset_name, feat_types
             shuffled[n] = columns[n].to(torch.int64)[index_dev]
         else:
             shuffled[n] = np.asarray(columns[n])[index]
-    field_map, feat_type_map = {"<rsv>": 0}, {"<rsv>": 0}
-    for n in names:
-        field_map[n] = len(field_map)
-        if feat_types[n] not in feat_type_map:
-            feat_type_map[feat_types[n]] = len(feat_type_map)
-    if "<oov>" not in feat_type_map:
-        feat_type_map["<oov>"] = len(feat_type_map)
-    feat_ids, _fields, feat_map, input_size = build_vocab(shuffled, n_core, device=device, decoders=decoders)
+    field_map = {n: i for i, n in enumerate(["<rsv>"] + names)}
+    feat_type_map = _feat_type_map(names, feat_types)
+    feat_ids, _fields, feat_map, input_size, type_ids = _fit_encode(
+        shuffled, n_core, device, decoders, types=(set(string_columns or ()), feat_types, feat_type_map))
     N = len(labels)
-    field_ids = np.tile(np.array([field_map[n] for n in names], dtype=np.int32), (N, 1))
-    type_ids = np.empty((N, len(names)), dtype=np.int64)
-    for j, n in enumerate(names):
-        col = shuffled[n]
-        if n in string_columns:
-            missing = np.zeros(N, dtype=bool)
-        elif torch.is_tensor(col):
-            missing = (col == -1).cpu().numpy()
-        else:
-            missing = (col == -1) if col.dtype.kind in "iu" else np.zeros(N, dtype=bool)
-        type_ids[:, j] = np.where(missing, feat_type_map["<oov>"], feat_type_map[feat_types[n]])
     meta = {"index": index.tolist(), "num_pos": int(labels.sum()), "num_neg": int(N - labels.sum()),
             "avg_ctr": float(labels.mean()) if N else 0.0, "field_names": ["<rsv>"] + names, "field_map": field_map,
             "feat_type_map": feat_type_map, "feat_map": feat_map}
-    os.makedirs(data_dir, exist_ok=True)
-    with open(os.path.join(data_dir, f"{dataset_name}-meta.json"), "w") as f:
-        json.dump(meta, f, ensure_ascii=False)
-    np.savez(os.path.join(data_dir, f"{dataset_name}.npz"), feat_ids=feat_ids.cpu().numpy(), field_ids=field_ids,
-             type_ids=type_ids, labels=labels.astype(np.int64))
-    if split is not None and not os.path.exists(os.path.join(data_dir, "split.pkl")):
-        rng = np.random.RandomState(seed)
-        perm = rng.permutation(N)
-        a, b = int(N * split[0]), int(N * (split[0] + split[1]))
-        with open(os.path.join(data_dir, "split.pkl"), "wb") as f:
-            pkl.dump({"train_index": np.sort(perm[:a]), "valid_index": np.sort(perm[a:b]),
-                      "test_index": np.sort(perm[b:])}, f)
+    _write_dataset(data_dir, dataset_name, meta, feat_ids, _field_ids(field_map, names, N), type_ids, labels, split,
+                   seed)
     return meta, input_size
 
 
@@ -239,7 +274,8 @@ def generate_dataset_from_text(path, schema, n_core, data_dir, dataset_name, chu
 # ------------------------------------------------------------------ a saved vocabulary applied to other rows
 class FieldKeys:
     """One field of a saved feat_map: `keys` int64 [n] = the kept raw values in id order (the codes mapx.rawtext
-    gives the file's values), `base` the id of the first of them, `oov` = base + n the id of `<name>-<oov>`."""
+    gives the file's values), on the host, `base` the id of the first of them, `oov` = base + n the id of
+    `<name>-<oov>`.  (A fitted field, FieldVocab, is the same with its keys on the device.)"""
 
     def __init__(self, name, keys, base):
         self.name, self.keys, self.base = name, np.ascontiguousarray(keys, dtype=np.int64), int(base)
@@ -321,9 +357,10 @@ def _is_pow2(c):
 
 
 class Vocabulary:
-    """The lookup tables of a saved vocabulary on the device (csrc/vocab_apply.hip).  fields: [FieldKeys] with
-    consecutive id ranges.  flags[f] != 0: a raw -1 in field f gets `missing_type` in type_ids (integer-origin
-    columns; string-origin columns have flag 0, as in generate_dataset); field_types[f]: the type id otherwise.
+    """The lookup tables of a vocabulary on the device (csrc/vocab_apply.hip).  fields: [FieldKeys] (a saved
+    vocabulary) or [FieldVocab] (one just fitted: its keys stay on the device) with consecutive id ranges.
+    flags[f] != 0: a raw -1 in field f gets `missing_type` in type_ids (integer-origin columns; string-origin
+    columns have flag 0: generate_dataset's rule, which it applies through here); field_types[f]: the type id otherwise.
     capacities: table slots per field instead of the default (the smallest power of two >= max(2, 2 n_f)); each a
     power of two > n_f.  `feat_map`, `field_names`, `input_size` are those of the meta the vocabulary came from."""
 
@@ -360,8 +397,7 @@ class Vocabulary:
         self._par_host = par
         self._par = torch.from_numpy(par).to(dev)
         self.n_keys_total, self.n_slots = int(par[0, F]), int(par[1, F])
-        keys = np.concatenate([f.keys for f in fields]) if self.n_keys_total else np.zeros(0, dtype=np.int64)
-        self._keys = torch.from_numpy(keys).to(dev)
+        self._keys = torch.cat([torch.as_tensor(f.keys).to(dev) for f in fields])
         self._tkey = torch.empty(self.n_slots, dtype=torch.int64, device=dev)
         self._trank = torch.empty(self.n_slots, dtype=torch.int32, device=dev)
         err = torch.empty(2, dtype=torch.int32, device=dev)
@@ -390,12 +426,7 @@ class Vocabulary:
             with open(os.fspath(meta)) as f:
                 meta = json.load(f)
         fields = parse_meta(meta, schema)
-        tmap = meta.get("feat_type_map")
-        if tmap is None:
-            tmap = {"<rsv>": 0}
-            for f in fields:
-                tmap.setdefault(schema.feat_types[f.name], len(tmap))
-            tmap.setdefault("<oov>", len(tmap))
+        tmap = meta.get("feat_type_map") or _feat_type_map([f.name for f in fields], schema.feat_types)
         return cls(fields, device=device, capacities=capacities,
                    flags=[f.name not in schema.string_columns for f in fields],
                    field_types=[tmap[schema.feat_types[f.name]] for f in fields], missing_type=tmap["<oov>"],
@@ -403,15 +434,7 @@ class Vocabulary:
 
     @property
     def feat_map(self):
-        if self.meta is not None:
-            return self.meta["feat_map"]
-        fm = {tok: i for i, tok in enumerate(RESERVED)}
-        for f in self.fields:
-            dec = self.decoders.get(f.name, lambda v: str(int(v)))
-            for v in f.keys.tolist():
-                fm[f"{f.name}-{dec(v)}"] = len(fm)
-            fm[f"{f.name}-<oov>"] = len(fm)
-        return fm
+        return self.meta["feat_map"] if self.meta is not None else _feat_map(self.fields, self.decoders)
 
     @property
     def input_size(self):
@@ -491,7 +514,6 @@ def encode_dataset_from_text(path, schema, meta_path, data_dir, dataset_name, ch
     the field's <oov> id}; with `split`, a `split.pkl` by generate_dataset's seeded rule.  The rows stay in file
     order: encode mode never shuffles (the ids of a row do not depend on the order, and a file that is scored or
     evaluated is wanted as it is).  -> (meta, input_size)."""
-    import pickle as pkl
     from . import rawtext
     with open(os.fspath(meta_path)) as f:
         saved = json.load(f)
@@ -501,27 +523,11 @@ def encode_dataset_from_text(path, schema, meta_path, data_dir, dataset_name, ch
     labels = labels.cpu().numpy()
     N, names = len(labels), voc.field_names
     field_map = saved.get("field_map") or {n: i for i, n in enumerate(["<rsv>"] + names)}
-    feat_type_map = saved.get("feat_type_map")
-    if feat_type_map is None:
-        feat_type_map = {"<rsv>": 0}
-        for n in names:
-            feat_type_map.setdefault(schema.feat_types[n], len(feat_type_map))
-        feat_type_map.setdefault("<oov>", len(feat_type_map))
-    field_ids = np.tile(np.array([field_map[n] for n in names], dtype=np.int32), (N, 1))
+    feat_type_map = saved.get("feat_type_map") or _feat_type_map(names, schema.feat_types)
     meta = {"index": list(range(N)), "num_pos": int(labels.sum()), "num_neg": int(N - labels.sum()),
             "avg_ctr": float(labels.mean()) if N else 0.0, "field_names": saved["field_names"], "field_map": field_map,
             "feat_type_map": feat_type_map, "feat_map": saved["feat_map"],
             "oov_rows": {n: int(c) for n, c in zip(names, oov_rows)}}
-    os.makedirs(data_dir, exist_ok=True)
-    with open(os.path.join(data_dir, f"{dataset_name}-meta.json"), "w") as f:
-        json.dump(meta, f, ensure_ascii=False)
-    np.savez(os.path.join(data_dir, f"{dataset_name}.npz"), feat_ids=feat_ids.cpu().numpy(), field_ids=field_ids,
-             type_ids=type_ids.cpu().numpy(), labels=labels.astype(np.int64))
-    if split is not None and not os.path.exists(os.path.join(data_dir, "split.pkl")):
-        rng = np.random.RandomState(seed)
-        perm = rng.permutation(N)
-        a, b = int(N * split[0]), int(N * (split[0] + split[1]))
-        with open(os.path.join(data_dir, "split.pkl"), "wb") as f:
-            pkl.dump({"train_index": np.sort(perm[:a]), "valid_index": np.sort(perm[a:b]),
-                      "test_index": np.sort(perm[b:])}, f)
+    _write_dataset(data_dir, dataset_name, meta, feat_ids, _field_ids(field_map, names, N), type_ids, labels, split,
+                   seed)
     return meta, voc.input_size

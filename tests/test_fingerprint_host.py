@@ -1,5 +1,5 @@
 """State fingerprint, host side: the numpy restatement reproduces the known answers computed from the definition,
-and the library exports the entry point under ABI 48."""
+and the library exports the entry point under ABI 49."""
 import numpy as np
 
 import fingerprint_ref as R
@@ -24,8 +24,8 @@ def test_restatement_reads_bit_patterns_and_positions():
     assert R.fingerprint(R.words_of(a))[0] != R.fingerprint(R.words_of(a[::-1]))[0]
 
 
-def test_library_exports_the_entry_point_under_abi_48():
+def test_library_exports_the_entry_point_under_abi_49():
     from mapx import native
-    assert native.MAPX_ABI_VERSION == 48
-    assert native.lib.mapx_abi_version() == 48
+    assert native.MAPX_ABI_VERSION == 49
+    assert native.lib.mapx_abi_version() == 49
     assert hasattr(native.lib, "mapx_fingerprint_words") and "mapx_fingerprint_words" in native.SIGNATURES

@@ -132,3 +132,80 @@ def test_generate_dataset_is_read_back_by_the_loader(golden_dir, tmp_path):
     ds = BaseDataset(Args())
     tr = ds.get_splited_dataset("train")
     assert tr.X.shape == (int(N * 0.8), len(names)) and ds.feat_count.shape[0] >= input_size - 1
+
+
+def test_vocab_more_than_64_fields():
+    """65 fields of 130 rows: two full 64-row tiles and a 2-row tail, and one field more than a lookup-table group
+    holds.  About five distinct values per column and one singleton, so every field keeps values and has an <oov>
+    row at n_core 2.  feat_map (keys and order) and feat_ids against the Counter restatement."""
+    from mapx import vocab
+    from oracle import vocab as V
+    rng = np.random.RandomState(65)
+    N, F = 130, 65
+    cols = {}
+    for f in range(F):
+        c = (rng.randint(0, 5, size=N).astype(np.int64) - 1) * (f + 1)
+        c[(7 * f) % N] = 1000 + f                                                   # seen once: below n_core
+        cols[f"c{f}"] = c
+    feat_ids, fields, feat_map, input_size = vocab.build_vocab(cols, 2, device=DEV)
+    ref_map, rows = V.build_feat_map({n: c.tolist() for n, c in cols.items()}, 2)
+    assert feat_map == ref_map and list(feat_map) == list(ref_map) and input_size == len(ref_map)
+    got = feat_ids.cpu().numpy()
+    assert got.shape == (N, F) and np.array_equal(got, np.array(rows, dtype=np.int64))
+    for f, fv in enumerate(fields):
+        assert fv.n_kept > 0 and fv.oov == ref_map[f"c{f}-<oov>"] and bool((got[:, f] == fv.oov).any())
+
+
+@pytest.mark.parametrize("n_rows", [64, 65, 129])
+def test_vocab_field_tile_edges(n_rows):
+    """build_field at one full tile of rows, one row more, and two tiles and a row, into the middle column of a
+    three-column matrix: ids against the oracle, the neighbouring columns untouched."""
+    from mapx import vocab
+    from oracle import vocab as V
+    rng = np.random.RandomState(n_rows)
+    col = rng.randint(-1, 9, size=n_rows).astype(np.int64) * 1_000_003
+    out = torch.full((n_rows, 3), -7, dtype=torch.int64, device=DEV)
+    fv = vocab.build_field(torch.from_numpy(col).to(DEV), 3, 10, out[:, 1], name="f")
+    feat_map, rows = V.build_feat_map({"f": col.tolist()}, 3)
+    assert np.array_equal(out[:, 1].cpu().numpy(), np.array(rows, dtype=np.int64)[:, 0])
+    assert bool((out[:, 0] == -7).all()) and bool((out[:, 2] == -7).all())
+    assert fv.oov == feat_map["f-<oov>"]
+
+
+def test_generate_dataset_type_ids_rule(tmp_path):
+    """type_ids of the written table against the rule of proc_criteo.py:161-166 restated here: the '<oov>' type
+    where a value compares equal to -1 — which a string never does — and the field's own type everywhere else.
+    One column of each input kind: host integers, a device tensor, a device tensor named in string_columns (its
+    values were strings in the raw file), host strings."""
+    from mapx import vocab
+    rng = np.random.RandomState(5)
+    N = 203
+    host_int = rng.randint(-1, 4, size=N).astype(np.int64)
+    dev_int = rng.randint(-1, 4, size=N).astype(np.int64)
+    dev_str = rng.randint(-1, 4, size=N).astype(np.int64)
+    host_str = np.array(["-1", "ab", "cd", "-1x"])[rng.randint(0, 4, size=N)]
+    columns = {"hi": host_int, "di": torch.from_numpy(dev_int).to(DEV), "ds": torch.from_numpy(dev_str).to(DEV),
+               "hs": host_str}
+    feat_type_dict = {"hi": "<num>", "di": "<cat>", "ds": "<cat>", "hs": "<num>"}
+    labels = (np.arange(N) % 5 == 0).astype(np.int64)
+    meta, _ = vocab.generate_dataset(columns, labels, 2, str(tmp_path), "t", feat_types=feat_type_dict,
+                                     string_columns=["ds"])
+    feat_type_map = meta["feat_type_map"]
+    assert feat_type_map == {"<rsv>": 0, "<num>": 1, "<cat>": 2, "<oov>": 3}
+    index = meta["index"]
+    raw = {"hi": host_int.tolist(), "di": dev_int.tolist(), "ds": [str(v) for v in dev_str.tolist()],
+           "hs": host_str.tolist()}
+    all_type_ids = []
+    for name in columns:
+        feat = [raw[name][i] for i in index]
+        type_ids = []
+        for f in feat:
+            if f == -1:
+                type_ids.append(feat_type_map["<oov>"])
+            else:
+                type_ids.append(feat_type_map[feat_type_dict[name]])
+        all_type_ids.append(type_ids)
+    want = np.array(all_type_ids, dtype=np.int64).T
+    assert (want[:, :2] == 3).any(axis=0).all() and not (want[:, 2:] == 3).any()     # the draw exercises both branches
+    tab = np.load(os.path.join(str(tmp_path), "t.npz"))
+    assert tab["type_ids"].dtype == np.int64 and np.array_equal(tab["type_ids"], want)

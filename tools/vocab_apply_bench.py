@@ -8,7 +8,8 @@ Columns: --fields int64 columns of --rows values drawn on the device, field card
 mapx.dataset.field_sizes(fields, vocab), ranks by a power-law draw, every rank printed as an 8-digit hash code.  The
 vocabulary is fitted on them at n_core 2 by the existing builder (mapx.vocab.build_vocab); a second, independent draw
 of the same shape is the file that is encoded.  Timed with device events, median of --repeats launches after a
-warm-up, in this process alone:
+warm-up, in this process alone (the fit: a host clock that ends in a device synchronise, the same warm-up and repeats):
+  fit         mapx.vocab.build_vocab on the first draw: count, rank and translate all fields, feat_map names included;
   load        mapx_vocab_apply_load (clear + insert of all kept keys);
   apply/0     mapx_vocab_apply, ids through LDS and stored along the rows, without and with type_ids;
   apply/1     the same with one strided 8-byte store per row and field.
@@ -58,6 +59,20 @@ def _events(fn, repeats, warmup=2):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b) * 1e-3)
+    return times
+
+
+def _host_clock(fn, repeats, warmup=2):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
     return times
 
 
@@ -120,17 +135,22 @@ def main():
         return direct_tables(args, N, F)
     sizes = dataset.field_sizes(F, args.vocab)
     fit_cols = draw_columns(N, sizes, seed=1)
-    t0 = time.perf_counter()
-    feat_ids, fitted, _, input_size = vocab.build_vocab(fit_cols, 2)
-    print(f"fitted {F} fields of {N} rows at n_core 2 in {time.perf_counter() - t0:.1f} s: input_size {input_size}",
-          file=sys.stderr, flush=True)
+    last = {}
+
+    def fit():
+        last["fit"] = vocab.build_vocab(fit_cols, 2)
+    fit_times = _host_clock(fit, args.repeats)
+    feat_ids, fitted, _, input_size = last.pop("fit")
+    print(f"fitted {F} fields of {N} rows at n_core 2 in {statistics.median(fit_times):.2f} s: input_size "
+          f"{input_size}", file=sys.stderr, flush=True)
     fields = [vocab.FieldKeys(fv.name, fv.keys.cpu().numpy(), fv.base) for fv in fitted]
     del feat_ids, fitted, fit_cols
     torch.cuda.empty_cache()
     voc = vocab.Vocabulary(fields, flags=[1] * F, field_types=[1] * F, missing_type=2)
     cols = list(draw_columns(N, sizes, seed=2).values())
     res = {"rows": N, "fields": F, "keys": voc.n_keys_total, "slots": voc.n_slots, "input_size": input_size,
-           "device": torch.cuda.get_device_name(0)}
+           "device": torch.cuda.get_device_name(0),
+           "fit": {"seconds_median": statistics.median(fit_times), "seconds_all": fit_times}}
     par, err = voc._par, torch.empty(2, dtype=torch.int32, device="cuda")
 
     def load():
