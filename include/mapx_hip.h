@@ -904,6 +904,27 @@ int mapx_fgcnn_conv_bwd(const float* g, const float* z, const float* x, const fl
  * Backward: dx[b,i,:] = sum_{j>i} g[b,(i,j)] x[b,j,:] + sum_{j<i} g[b,(j,i)] x[b,j,:]. */
 int mapx_inner_product_fwd(const float* x, int64_t B, int T, int E, float* out, hipStream_t stream);
 int mapx_inner_product_bwd(const float* g, const float* x, int64_t B, int T, int E, float* dx, hipStream_t stream);
+/* The bf16 I/O forms (compute_dtype=bf16): the same kernels with the element type of the activations
+ * exchanged (8-byte aligned rows of E % 4 == 0 bf16), the same LDS contents (fp32), budgets, grids and refusals.
+ * bf16: conv_fwd x, z; pool_fwd z, y; pool_bwd dy, z; conv_bwd z, x, dx; inner_product x, out, g, dx.
+ * fp32 as above: w, bias, gamma, beta, stats, the running statistics, g = dL/du, every parameter gradient; fp64 partials.
+ * conv_fwd's partials are the sums of the STORED (rounded) z widened back, the tensor xhat is recomputed from.
+ * inner_product_bwd_bf16 reads g in place at a row pitch of ldg >= T(T-1)/2 elements (a column slice of a wider
+ * gradient; 2-byte aligned), and the forward's output rows are only 2-byte aligned when T(T-1)/2 is odd. */
+int mapx_fgcnn_conv_fwd_bf16(const mapx_bf16* x, const float* w, const float* bias, int64_t B, int Cin, int Cout, int H,
+                             int E, int kh, mapx_bf16* z, double* part_opt, hipStream_t stream);
+int mapx_fgcnn_pool_fwd_bf16(const mapx_bf16* z, const float* stats_opt, const float* running_mean_opt,
+                             const float* running_var_opt, float eps, const float* gamma, const float* beta, int64_t B,
+                             int C, int H, int E, int ps, int act, mapx_bf16* y, uint8_t* idx_opt, hipStream_t stream);
+int mapx_fgcnn_pool_bwd_bf16(const mapx_bf16* dy, const uint8_t* idx, const mapx_bf16* z, const float* stats,
+                             const float* gamma, const float* beta, int64_t B, int C, int H, int E, int ps, int act,
+                             float* g, double* part, hipStream_t stream);
+int mapx_fgcnn_conv_bwd_bf16(const float* g, const mapx_bf16* z, const mapx_bf16* x, const float* w, const float* stats,
+                             const float* gamma, const float* bsum, int64_t B, int Cin, int Cout, int H, int E, int kh,
+                             mapx_bf16* dx_opt, float* part_w, float* part_b, float* dw, float* db, hipStream_t stream);
+int mapx_inner_product_fwd_bf16(const mapx_bf16* x, int64_t B, int T, int E, mapx_bf16* out, hipStream_t stream);
+int mapx_inner_product_bwd_bf16(const mapx_bf16* g, int64_t ldg, const mapx_bf16* x, int64_t B, int T, int E,
+                                mapx_bf16* dx, hipStream_t stream);
 
 /* ------------------------------------------------------------------ FiGNN backbone
  * layers.py:300-379 (GraphLayer, FiGNNBlock, AttentionalPrediction), models.py:410-438.  All tensors fp32, dense and

@@ -1364,7 +1364,8 @@ def field_pool(x3, mode, scores=None):
 # ----------------------------------------------------------------------------- FGCNN
 class _InnerProduct(Function):
     """InnerProductLayer(output='inner_product') (reference layers.py:132-135): x [B,T,E] -> x_i . x_j over the pairs
-    i < j in masked_select's order, [B, T(T-1)/2]  (csrc/fgcnn.hip)."""
+    i < j in masked_select's order, [B, T(T-1)/2]  (csrc/fgcnn.hip).  fp32 or bf16 (DESIGN §4.9): the output and dx take x's
+    element type; a bf16 gradient that is a column slice of d(dense_input) is read in place."""
 
     @staticmethod
     def forward(ctx, x3):
@@ -1387,7 +1388,9 @@ class _ConvBnActPool(Function):
     three launches forward (conv + partial statistics, their finalise, normalise + act + pool) and four backward
     (csrc/fgcnn.hip).  Train mode normalises with the batch statistics and moves the running ones (and the batch
     counter) on the device; saved for backward: the input, z (the conv output) and one uint8 argmax per pooled
-    element.  Eval mode normalises with the running statistics, saves nothing and has no backward."""
+    element.  Eval mode normalises with the running statistics, saves nothing and has no backward.
+    A bf16 input gives a bf16 z, output and dx; the parameters, the statistics, the buffers and every
+    parameter gradient stay fp32."""
 
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, tracked, ps, act, training):

@@ -1,7 +1,7 @@
 """BaseModel + DCNV2 (host mirror of reference code/models.py:21-127, 282-322): same factory,
 same forward signature and output tuples, same state_dict key layout; every arithmetic step
 is a gfx950 kernel.  The other backbones the factory builds: DNN, DeepFM, xDeepFM, AutoInt, trans, fgcnn
-(from_config still refuses fignn, and trans / xDeepFM with compute_dtype=bf16; build_backbone builds them)."""
+(from_config still refuses fignn, and trans / xDeepFM / fgcnn with compute_dtype=bf16; build_backbone builds them)."""
 import logging
 
 import torch
@@ -674,8 +674,13 @@ class FGCNN(BaseModel):
     embeddings to `combined` [B,T,E], and cat([combined.flatten(1), upper triangle of combined combined^T]) feeds the
     MFP / RFD heads, or `dnn` + `fc_out` (fc_out alone when num_hidden_layers = 0).  Conv, batch norm, pooling and the
     inner products are csrc/fgcnn.hip: at most 32 channels, odd kernel heights <= 15, T <= 192 rows, conv_act tanh |
-    relu, fp32.  Batch norm keeps per-replica buffers that the reference's DistributedDataParallel re-broadcasts from
-    rank 0 at every forward; that is not built, so the model trains on one replica only (`single_replica_only`)."""
+    relu.  Batch norm keeps per-replica buffers that the reference's DistributedDataParallel re-broadcasts from
+    rank 0 at every forward; that is not built, so the model trains on one replica only (`single_replica_only`).
+    compute_dtype=bf16 (through build_backbone): the gathered rows, every stage's input, the saved conv
+    output z, the pooled output, the recombine layers' outputs, `combined`, the inner products, dense_input and the MLP
+    activations are bf16 (the bf16 I/O forms of csrc/fgcnn.hip, bf16 GEMMs on the weights' shadows); the conv weights,
+    the batch-norm parameters, statistics and buffers, g = dL/du inside a stage's backward, every parameter gradient and
+    the heads' logits stay fp32.  hidden_act != relu and hidden_dropout_rate > 0 are refused at construction."""
     used_params = ["embed_size", "hidden_size", "num_hidden_layers", "hidden_dropout_rate", "hidden_act",
                    "share_embedding", "channels", "kernel_heights", "pooling_sizes", "recombined_channels",
                    "conv_act"]
@@ -687,6 +692,10 @@ class FGCNN(BaseModel):
 
     def __init__(self, config: Config):
         super().__init__(model_name="fgcnn", config=config)
+        from .layers import compute_dtype_of
+        half = compute_dtype_of(config) != torch.float32
+        if not config.pretrain and config.num_hidden_layers > 0:
+            _refuse_bf16_mlp_options(config, "hidden_act", "hidden_dropout_rate")
         lists = {k: _int_list(config, k) for k in ("channels", "kernel_heights", "pooling_sizes", "recombined_channels")}
         if len({len(v) for v in lists.values()}) != 1:
             raise ValueError("channels, kernel_heights, pooling_sizes and recombined_channels must list one value per "
@@ -735,10 +744,10 @@ class FGCNN(BaseModel):
             self.dnn = MLPBlock(input_dim=final_dim, hidden_size=config.hidden_size,
                                 num_hidden_layers=config.num_hidden_layers,
                                 hidden_dropout_rate=config.hidden_dropout_rate, hidden_act=config.hidden_act)
-            self.fc_out = HipLinear(config.hidden_size, 1)
+            self.fc_out = HipLinear(config.hidden_size, 1, out_fp32=half)          # (bf16 mode: the logits stay fp32)
         else:
             self.dnn = None
-            self.fc_out = HipLinear(final_dim, 1)
+            self.fc_out = HipLinear(final_dim, 1, out_fp32=half)
 
     @staticmethod
     def compute_input_dim(embedding_dim, num_fields, channels, pooling_sizes, recombined_channels):
@@ -819,15 +828,17 @@ class FiGNN(BaseModel):
 
 
 def build_backbone(config: Config):
-    """Every model name the reference's factory reaches: FiGNN, and the Transformer and xDeepFM in compute_dtype=bf16
-    here, the rest through BaseModel.from_config (which still refuses fignn, and trans / xDeepFM with bf16, as existing
-    tests pin; making it delegate is a one-line follow-up)."""
+    """Every model name the reference's factory reaches: FiGNN, and the Transformer, xDeepFM and FGCNN in
+    compute_dtype=bf16 here, the rest through BaseModel.from_config (which still refuses fignn, and trans / xDeepFM /
+    fgcnn with bf16, as existing tests pin; making it delegate is a one-line follow-up)."""
     from .layers import compute_dtype_of
     name = str(config.model_name).lower()
     if name == "trans" and compute_dtype_of(config) != torch.float32:
         return Transformer(config)
     if name == "xdeepfm" and compute_dtype_of(config) != torch.float32:
         return xDeepFM(config)
+    if name == "fgcnn" and compute_dtype_of(config) != torch.float32:
+        return FGCNN(config)
     if name == "fignn":
         if compute_dtype_of(config) != torch.float32:
             raise NotImplementedError("compute_dtype=bf16 is built for DCNv2, DNN, DeepFM and AutoInt, "

@@ -178,6 +178,12 @@ SIGNATURES = {
     "mapx_fgcnn_conv_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "mapx_inner_product_fwd": (_i, [_p, _i64, _i, _i, _p, _p]),
     "mapx_inner_product_bwd": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
+    "mapx_fgcnn_conv_fwd_bf16": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_pool_fwd_bf16": (_i, [_p, _p, _p, _p, _f, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_pool_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mapx_fgcnn_conv_bwd_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "mapx_inner_product_fwd_bf16": (_i, [_p, _i64, _i, _i, _p, _p]),
+    "mapx_inner_product_bwd_bf16": (_i, [_p, _i64, _p, _i64, _i, _i, _p, _p]),
     "mapx_fignn_weights_staged": (_i, [_i, _i, _i]),
     "mapx_fignn_graph_fwd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p, _p]),
     "mapx_fignn_graph_bwd_groups": (_i, [_i64]),

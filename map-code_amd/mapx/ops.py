@@ -868,18 +868,25 @@ def _f32c(*ts):
             raise TypeError("fgcnn kernels take contiguous fp32 tensors")
 
 
+def _fg_half(what, names, *ts):
+    """The activations of an fgcnn kernel: contiguous, all fp32 (False) or all bf16 (True: the `_bf16` entries, whose
+    parameters, statistics and parameter gradients stay fp32)."""
+    return _one_dtype(what, names, *ts, contiguous=True)
+
+
 def fgcnn_conv_fwd(x, w, bias, stats=True):
     """x [B,Cin,H,E], w [Cout,Cin,kh(,1)], bias [Cout] -> (z [B,Cout,H,E], part [B,Cout,2] fp64 | None): the
     convolution and, with `stats`, the per-sample partial sums of the batch statistics from the same launch."""
     require_gpu(x, w, bias)
-    _f32c(x, w, bias)
+    _f32c(w, bias)
+    fn = lib.mapx_fgcnn_conv_fwd_bf16 if _fg_half("fgcnn_conv_fwd", "x", x) else lib.mapx_fgcnn_conv_fwd
     B, Cin, H, E = x.shape
     Cout, kh = w.shape[0], w.shape[2]
     if w.shape[1] != Cin or w.numel() != Cout * Cin * kh:
         raise ValueError(f"fgcnn_conv_fwd: weight {tuple(w.shape)} does not fit the input {tuple(x.shape)}")
-    z = torch.empty(B, Cout, H, E, dtype=torch.float32, device=x.device)
+    z = torch.empty(B, Cout, H, E, dtype=x.dtype, device=x.device)
     part = torch.empty(B, Cout, 2, dtype=torch.float64, device=x.device) if stats else None
-    check(lib.mapx_fgcnn_conv_fwd(ptr(x), ptr(w), ptr(bias), B, Cin, Cout, H, E, kh, ptr(z), ptr(part), stream()))
+    check(fn(ptr(x), ptr(w), ptr(bias), B, Cin, Cout, H, E, kh, ptr(z), ptr(part), stream()))
     return z, part
 
 
@@ -907,29 +914,34 @@ def fgcnn_pool_fwd(z, gamma, beta, ps, act, stats=None, running_mean=None, runni
     """BatchNorm (batch `stats` [C,2], or the running statistics) -> act -> max-pool over ps rows:
     z [B,C,H,E] -> (y [B,C,Hp,E], idx uint8 [B,C,Hp,E] | None)."""
     require_gpu(z, gamma, beta, stats, running_mean, running_var)
-    _f32c(z, gamma, beta, stats, running_mean, running_var)
+    _f32c(gamma, beta, stats, running_mean, running_var)
+    fn = lib.mapx_fgcnn_pool_fwd_bf16 if _fg_half("fgcnn_pool_fwd", "z", z) else lib.mapx_fgcnn_pool_fwd
     B, C, H, E = z.shape
     _, Hp = fgcnn_pool_shape(H, ps)
-    y = torch.empty(B, C, max(Hp, 0), E, dtype=torch.float32, device=z.device)
+    y = torch.empty(B, C, max(Hp, 0), E, dtype=z.dtype, device=z.device)
     idx = torch.empty(B, C, max(Hp, 0), E, dtype=torch.uint8, device=z.device) if save else None
-    check(lib.mapx_fgcnn_pool_fwd(ptr(z), ptr(stats), ptr(running_mean), ptr(running_var), float(eps), ptr(gamma),
-                                  ptr(beta), B, C, H, E, int(ps), FGCNN_ACTS[act], ptr(y), ptr(idx), stream()))
+    check(fn(ptr(z), ptr(stats), ptr(running_mean), ptr(running_var), float(eps), ptr(gamma), ptr(beta), B, C, H, E,
+             int(ps), FGCNN_ACTS[act], ptr(y), ptr(idx), stream()))
     return y, idx
 
 
 def fgcnn_bwd(dy, idx, z, x, w, stats, gamma, beta, ps, act, dw=None, db=None, dgamma=None, dbeta=None, need_dx=True):
     """Backward of pool <- act <- BatchNorm (batch statistics) <- conv: -> (dx | None, dw, db, dgamma, dbeta).
-    dw / db / dgamma / dbeta: optional destinations (the optimizer's gradient slots)."""
+    dw / db / dgamma / dbeta: optional destinations (the optimizer's gradient slots).  dy, z, x (and dx) share one
+    element type, fp32 or bf16; g = dL/du between the launches and every parameter gradient are fp32."""
     require_gpu(dy, idx, z, x, w, stats, gamma, beta)
     dy = dy.contiguous()
-    _f32c(dy, z, x, w, stats, gamma, beta, dw, db, dgamma, dbeta)
+    _f32c(w, stats, gamma, beta, dw, db, dgamma, dbeta)
+    half = _fg_half("fgcnn_bwd", "dy, z and x", dy, z, x)
+    pool_bwd = lib.mapx_fgcnn_pool_bwd_bf16 if half else lib.mapx_fgcnn_pool_bwd
+    conv_bwd = lib.mapx_fgcnn_conv_bwd_bf16 if half else lib.mapx_fgcnn_conv_bwd
     B, Cin, H, E = x.shape
     Cout, kh = w.shape[0], w.shape[2]
     dev = x.device
-    g = torch.empty_like(z)
+    g = torch.empty(z.shape, dtype=torch.float32, device=dev)
     part = torch.empty(B, Cout, 2, dtype=torch.float64, device=dev)
-    check(lib.mapx_fgcnn_pool_bwd(ptr(dy), ptr(idx), ptr(z), ptr(stats), ptr(gamma), ptr(beta), B, Cout, H, E, int(ps),
-                                  FGCNN_ACTS[act], ptr(g), ptr(part), stream()))
+    check(pool_bwd(ptr(dy), ptr(idx), ptr(z), ptr(stats), ptr(gamma), ptr(beta), B, Cout, H, E, int(ps),
+                   FGCNN_ACTS[act], ptr(g), ptr(part), stream()))
     bsum = torch.empty(Cout, 2, dtype=torch.float32, device=dev)
     dgamma = torch.empty_like(gamma) if dgamma is None else dgamma
     dbeta = torch.empty_like(beta) if dbeta is None else dbeta
@@ -940,26 +952,39 @@ def fgcnn_bwd(dy, idx, z, x, w, stats, gamma, beta, ps, act, dw=None, db=None, d
     dx = torch.empty_like(x) if need_dx else None
     dw = torch.empty_like(w) if dw is None else dw
     db = torch.empty(Cout, dtype=torch.float32, device=dev) if db is None else db
-    check(lib.mapx_fgcnn_conv_bwd(ptr(g), ptr(z), ptr(x), ptr(w), ptr(stats), ptr(gamma), ptr(bsum), B, Cin, Cout, H, E,
-                                  kh, ptr(dx), ptr(pw), ptr(pb), ptr(dw), ptr(db), stream()))
+    check(conv_bwd(ptr(g), ptr(z), ptr(x), ptr(w), ptr(stats), ptr(gamma), ptr(bsum), B, Cin, Cout, H, E, kh, ptr(dx),
+                   ptr(pw), ptr(pb), ptr(dw), ptr(db), stream()))
     return dx, dw, db, dgamma, dbeta
 
 
 def inner_product_fwd(x3):
     """x3 [B,T,E] -> [B, T(T-1)/2]: x_i . x_j over the pairs i < j, row-major (layers.py:132-135)."""
     require_gpu(x3)
-    _f32c(x3)
+    fn = lib.mapx_inner_product_fwd_bf16 if _fg_half("inner_product_fwd", "x", x3) else lib.mapx_inner_product_fwd
     B, T, E = x3.shape
-    out = torch.empty(B, T * (T - 1) // 2, dtype=torch.float32, device=x3.device)
-    check(lib.mapx_inner_product_fwd(ptr(x3), B, T, E, ptr(out), stream()))
+    out = torch.empty(B, T * (T - 1) // 2, dtype=x3.dtype, device=x3.device)
+    check(fn(ptr(x3), B, T, E, ptr(out), stream()))
     return out
 
 
 def inner_product_bwd(g, x3):
+    """g [B, T(T-1)/2], x3 [B,T,E] -> dx [B,T,E].  A bf16 g is read in place when its rows are unit-stride (a column
+    slice of d(dense_input): odd offset and pitch); an fp32 one is made contiguous first."""
     require_gpu(g, x3)
+    B, T, E = x3.shape
+    if is_bf16(x3):
+        if g.dim() != 2 or g.stride(1) != 1 or (B > 1 and g.stride(0) < g.shape[1]):
+            g = g.contiguous()
+        _fg_half("inner_product_bwd", "x", x3)
+        if g.dtype != BF16 or tuple(g.shape) != (B, T * (T - 1) // 2):
+            raise TypeError(f"inner_product_bwd: g is bf16 [B, T(T-1)/2] like x (got {g.dtype} {tuple(g.shape)})")
+        dx = torch.empty_like(x3)
+        # (the pitch: guard-band cases in tests/test_bf16_fgcnn_extents_gpu.py)
+        ldg = g.stride()[0] if B > 1 else g.shape[1]
+        check(lib.mapx_inner_product_bwd_bf16(g.data_ptr(), ldg, ptr(x3), B, T, E, ptr(dx), stream()))
+        return dx
     g = g.contiguous()
     _f32c(g, x3)
-    B, T, E = x3.shape
     dx = torch.empty_like(x3)
     check(lib.mapx_inner_product_bwd(ptr(g), ptr(x3), B, T, E, ptr(dx), stream()))
     return dx

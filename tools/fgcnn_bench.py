@@ -2,10 +2,13 @@
 E = 16, the flag-default channel lists (channels 14,16,18,20, kernel heights 7, pooling 2, recombined 3: T = 92
 feature rows); MFP, RFD and finetune (CTR) steps through Trainer.run_step (the captured step replayed after the first
 few).  One JSON line per arm.
+--dtype fp32 bf16 runs every step arm in both compute modes (DESIGN §4.9), alternated arm by arm in the one process;
+--rounds N repeats the whole alternation N times (take the median of an arm's lines).
 --torch-trunk adds forward + backward of the trunk alone (embeddings [B,23,16] -> the heads' input [B,5658]): the mapx
 conv / batch-norm / pool / inner-product kernels against torch's own conv2d / batch_norm / max_pool2d / bmm +
 masked_select on the same GPU, same fp32 weights (the recombine layers are torch.nn.Linear there).
-    python tools/fgcnn_bench.py [--pt MFP RFD CTR] [--steps 100] [--torch-trunk] [--no-steps]"""
+    python tools/fgcnn_bench.py [--pt MFP RFD CTR] [--dtype fp32 bf16] [--rounds 3] [--steps 100] [--torch-trunk]
+                                [--no-steps]"""
 import argparse
 import json
 import os
@@ -21,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "map-code_amd"))
 F_AVAZU, V_AVAZU = 23, 9449445
 
 
-def make_config(a, pt, feat_count):
+def make_config(a, pt, feat_count, dtype="fp32"):
     from mapx.arguments import MODEL_FLAGS, Config
     fg = {n: d for n, _t, d, _h in MODEL_FLAGS if n in ("share_embedding", "channels", "kernel_heights", "pooling_sizes",
                                                         "recombined_channels", "conv_act")}      # the flag defaults
@@ -29,17 +32,17 @@ def make_config(a, pt, feat_count):
                   embed_dropout_rate=0.0, embed_norm=False, hidden_size=a.hidden, num_hidden_layers=a.layers,
                   hidden_act="relu", hidden_dropout_rate=0.0, num_cross_layers=0, pt_neg_num=25, proj_size=32,
                   pretrain=pt != "CTR", pt_type="MFP" if pt == "CTR" else pt, RFD_replace="Unigram",
-                  feat_count=feat_count, seed=42, rank=0, compute_dtype="fp32")
+                  feat_count=feat_count, seed=42, rank=0, compute_dtype=dtype)
 
 
-def step_arm(a, pt, ids, labels, feat_count, device):
+def step_arm(a, pt, dtype, ids, labels, feat_count, device):
     from mapx.arguments import TrainingArguments
     from mapx.dataset import OurDataset
-    from mapx.models import BaseModel
+    from mapx.models import build_backbone
     from mapx.trainer import Trainer
     torch.manual_seed(42)
-    cfg = make_config(a, pt, feat_count)
-    model = BaseModel.from_config(cfg)
+    cfg = make_config(a, pt, feat_count, dtype)
+    model = build_backbone(cfg)
     targs = TrainingArguments(output_dir="/tmp/mapx_fgcnn_bench", per_gpu_train_batch_size=a.batch,
                               per_gpu_eval_batch_size=a.batch, learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2,
                               num_train_epochs=1000, pretrain=pt != "CTR", pt_type="MFP" if pt == "CTR" else pt,
@@ -68,7 +71,7 @@ def step_arm(a, pt, ids, labels, feat_count, device):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     live = [g for g in tr._graphs.values() if not isinstance(g, int)]
-    return {"arm": f"fgcnn {pt}", "batch": a.batch, "feature_rows": model.total_features,
+    return {"arm": f"fgcnn {pt}", "dtype": dtype, "batch": a.batch, "feature_rows": model.total_features,
             "ms_per_step": 1e3 * dt / a.steps, "samples_per_s": a.batch * a.steps / dt, "graphed": bool(live),
             "loss": float(out[0].detach())}
 
@@ -153,6 +156,8 @@ def main():
     ap.add_argument("--vocab", type=int, default=V_AVAZU)
     ap.add_argument("--hidden", type=int, default=1000)
     ap.add_argument("--layers", type=int, default=3)
+    ap.add_argument("--dtype", nargs="+", default=["fp32"], choices=["fp32", "bf16"], help="compute_dtype of the step arms")
+    ap.add_argument("--rounds", type=int, default=1, help="repeat the alternation of the step arms")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--torch-trunk", action="store_true")
@@ -164,8 +169,10 @@ def main():
     ids, labels, _, _ = synth_table(a.rows, F_AVAZU, a.vocab, seed=42)
     feat_count = torch.from_numpy(np.bincount(ids.reshape(-1), minlength=a.vocab).astype(np.float32))
     if not a.no_steps:
-        for pt in a.pt:
-            print(json.dumps(step_arm(a, pt, ids, labels, feat_count, device)), flush=True)
+        for rnd in range(a.rounds):
+            for pt in a.pt:
+                for dtype in a.dtype:
+                    print(json.dumps(dict(step_arm(a, pt, dtype, ids, labels, feat_count, device), round=rnd)), flush=True)
     if a.torch_trunk:
         print(json.dumps(trunk_arm(a, feat_count, device)), flush=True)
 
