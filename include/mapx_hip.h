@@ -985,6 +985,23 @@ int mapx_fingerprint_words(const void* data, int64_t n_words,
                            int blocks       /* 0 = auto; otherwise the first launch's grid size */,
                            hipStream_t stream);
 
+/* ------------------------------------------------------------------ scoring (mapx/score.py)
+ * The two launches a scoring step has beyond the model's forward (trainer.py:163-199 runs the forward over a labelled
+ * split and keeps two numbers; nothing in the reference writes per-row probabilities).  Both walk N rows by the device
+ * int64 *cursor, which the caller advances inside the step (mapx_step_advance), so that a captured step replays on
+ * the next B rows by itself.  *cursor >= N is valid (nothing but pad rows is written); no atomics.
+ * score_block: for i < B, r = *cursor + i:  r < N: batch[i, :] = ids[r, :] (ids int64 [>= N, F] at a row pitch of
+ *   ld_ids >= F elements) and oov_fields[r] = #{f : ids[r, f] == oov_id[f]};  r >= N: batch[i, :] = 0 (the <pad> id)
+ *   and nothing else.  1 <= F <= 64; batch [B, F] dense and 16-byte aligned; writes nothing outside batch and
+ *   oov_fields[*cursor .. min(*cursor + B, N)).  ids and oov_fields may be NULL when N == 0.
+ * score_sink: for r = *cursor + i < N:  logits_out[r] = logits[i] (bit for bit), probs[r] = 1 / (1 + expf(-logits[i]))
+ *   in fp32 — the device function mapx_eval_metrics ranks and sums; rows >= N are dropped.  logits [B] fp32
+ *   (16-byte accesses when all three bases are 16-byte aligned); writes nothing outside probs / logits_out [*cursor .. min(*cursor + B, N)). */
+int mapx_score_block(const int64_t* ids, int64_t ld_ids, int64_t N, const int64_t* cursor, int64_t B, int F,
+                     const int64_t* oov_id, int64_t* batch, uint8_t* oov_fields, hipStream_t stream);
+int mapx_score_sink(const float* logits, int64_t N, const int64_t* cursor, int64_t B, float* probs, float* logits_out,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

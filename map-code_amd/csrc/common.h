@@ -145,6 +145,10 @@ __device__ inline float dot4(const float4& a, const float4& b, float s) {
 }
 // (fignn.hip keeps gn_dot4, hand-written v_fmac_f32, for dot products that run side by side: see its comment.)
 
+// THE fp32 sigmoid of a logit (trainer.py:190, torch.sigmoid on fp32): what the evaluation metrics rank and sum
+// (metrics.hip) is what a scoring run writes out (score.hip), bit for bit.
+__device__ inline float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // ---------------------------------------------------------------- bf16 I/O (bf16 compute mode)
 // Kernels templated on an element type T = float | bf16_t differ only here: a load widens to fp32 (exact), all
 // arithmetic is fp32, a store rounds to nearest even once (v_cvt_pk_bf16_f32).

@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(kEvalBlock) eval_prepare_kernel(
   double ll = 0.0, sx = 0.0, sp = 0.0, np = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kEvalBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kEvalBlock) {
     const float x = logits[i];
-    const float p32 = 1.0f / (1.0f + expf(-x));
+    const float p32 = sigmoid_f32(x);
     const bool y = labels[i] > 0.5f;
     keys[i] = __float_as_uint(p32);
     pos[i] = y ? 1 : 0;

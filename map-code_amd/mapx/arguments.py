@@ -172,10 +172,9 @@ class TrainingArguments(_Bag):
         return self.per_gpu_eval_batch_size * max(1, self.n_gpu)
 
 
-def build_parser():
-    ap = argparse.ArgumentParser(prog="run.py", allow_abbrev=False,
-                                 description="DCNv2 scratch / MFP / RFD / finetune on MI355X")
-    for name, typ, default, hlp in MODEL_FLAGS + EXTENSION_MODEL_FLAGS + TRAINING_FLAGS:
+def add_flags(ap, flags):
+    """The (name, type, default, help) flags as argparse arguments (run.py; mapx.score takes the model flags)."""
+    for name, typ, default, hlp in flags:
         kw = dict(dest=name, help=hlp or None)
         if default is REQUIRED:
             kw["required"] = True
@@ -188,6 +187,12 @@ def build_parser():
         else:
             kw.update(type=typ)
         ap.add_argument(f"--{name}", **kw)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="run.py", allow_abbrev=False,
+                                 description="DCNv2 scratch / MFP / RFD / finetune on MI355X")
+    add_flags(ap, MODEL_FLAGS + EXTENSION_MODEL_FLAGS + TRAINING_FLAGS)
     return ap
 
 

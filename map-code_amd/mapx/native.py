@@ -194,6 +194,8 @@ SIGNATURES = {
     "mapx_fignn_layer_wgrad": (_i, [_p, _p, _i64, _i, _i] + [_p] * 9 + [_i, _i, _p]),
     "mapx_fignn_pred_fwd": (_i, [_p, _p, _i64, _i, _p, _p]),
     "mapx_fignn_pred_bwd": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p]),
+    "mapx_score_block": (_i, [_p, _i64, _i64, _p, _i64, _i, _p, _p, _p, _p]),
+    "mapx_score_sink": (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
 }
 
 

@@ -2412,6 +2412,54 @@ def step_advance(done, cursor=None, stride=0):
     check(lib.mapx_step_advance(ptr(done), ptr(cursor), int(stride), stream()))
 
 
+def _score_cursor(name, cursor):
+    if cursor.dtype != torch.int64 or cursor.numel() != 1 or not cursor.is_cuda:
+        raise TypeError(f"{name}: the cursor is an int64 device scalar")
+
+
+def score_block(ids, n_rows, cursor, oov_id, batch, oov_fields):
+    """batch [B, F] = rows [*cursor, *cursor + B) of ids (int64 [>= n_rows, F], unit column stride, any row pitch),
+    zeros (<pad>) from row n_rows on; oov_fields[r] (uint8 [>= n_rows]) = the fields of row r that hold oov_id[f]
+    (include/mapx_hip.h: mapx_score_block).  Everything is preallocated: the launch is one node of a captured step."""
+    require_gpu(ids, cursor, oov_id, batch, oov_fields)
+    _score_cursor("score_block", cursor)
+    B, F = batch.shape
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] != F or (F > 1 and ids.stride(1) != 1) or \
+            (ids.shape[0] > 1 and ids.stride(0) < F):
+        raise TypeError(f"score_block: ids must be int64 [rows, {F}] with unit column stride and a row pitch >= {F}")
+    if batch.dtype != torch.int64 or not batch.is_contiguous() or oov_id.dtype != torch.int64 or oov_id.numel() != F \
+            or not oov_id.is_contiguous():
+        raise TypeError(f"score_block: batch is contiguous int64 [B, {F}], oov_id contiguous int64 [{F}]")
+    n_rows = int(n_rows)
+    if not 0 <= n_rows <= ids.shape[0] or oov_fields.dtype != torch.uint8 or oov_fields.dim() != 1 \
+            or not oov_fields.is_contiguous() or oov_fields.numel() < n_rows:
+        raise ValueError(f"score_block: {n_rows} rows of an id matrix of {ids.shape[0]} and oov_fields (uint8) of "
+                         f"{oov_fields.numel()}")
+    ld = ids.stride(0) if ids.shape[0] > 1 else F
+    with _timed("score_block", B * F * 16.0 + B):
+        check(lib.mapx_score_block(ids.data_ptr() if n_rows else None, ld, n_rows, ptr(cursor), B, F, ptr(oov_id),
+                                   ptr(batch), oov_fields.data_ptr() if n_rows else None, stream()))
+    return batch
+
+
+def score_sink(logits, n_rows, cursor, probs, logits_out):
+    """logits_out[r] = logits[i], probs[r] = sigmoid(logits[i]) in fp32 for r = *cursor + i < n_rows (include/mapx_hip.h:
+    mapx_score_sink; the sigmoid is the one eval_metrics ranks).  logits: fp32, B elements."""
+    require_gpu(logits, cursor, probs, logits_out)
+    _score_cursor("score_sink", cursor)
+    n_rows = int(n_rows)
+    for name, t in (("logits", logits), ("probs", probs), ("logits_out", logits_out)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"score_sink: {name} must be contiguous fp32")
+    if n_rows < 0 or probs.numel() < n_rows or logits_out.numel() < n_rows:
+        raise ValueError(f"score_sink: {n_rows} rows, probs of {probs.numel()}, logits_out of {logits_out.numel()}")
+    B = logits.numel()
+    with _timed("score_sink", B * 12.0):
+        check(lib.mapx_score_sink(logits.data_ptr() if B else None, n_rows, ptr(cursor), B,
+                                  probs.data_ptr() if n_rows else None, logits_out.data_ptr() if n_rows else None,
+                                  stream()))
+
+
 def replay_coef_table(aux, beta1, beta2, done, coef=None):
     """The closed-form replay's coefficients for every gap ending at *done (include/mapx_hip.h:
     mapx_replay_coef_table) -> coef [2, aux_len, 12] f32 (allocated once by the caller, rewritten every step)."""

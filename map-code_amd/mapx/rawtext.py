@@ -3,8 +3,9 @@
 
 The file is streamed in chunks cut at line ends (`iter_chunks`, pure host); every chunk is copied to the device,
 indexed (line starts, physical line numbers) and parsed by the kernels of csrc/rawtext.hip behind
-include/mapx_hip.h (mapx_rawtext_*), straight into preallocated columns.  The columns feed `vocab.build_vocab`.
-There is no CPU parsing path.
+include/mapx_hip.h (mapx_rawtext_*), straight into preallocated columns.  The columns feed `vocab.build_vocab`;
+`iter_columns` hands them over chunk by chunk instead (mapx.score: files that need not fit the device), and the
+UNLABELED schemas read files without the click field.  There is no CPU parsing path.
 
 The field grammar is deliberately stricter than Python's int(): `-?[0-9]{1,18}` for integers (no '+', blanks,
 '_', decimal point), `[0-9a-f]{1,14}` for hash strings, exactly eight digits of a valid date and hour for Avazu's
@@ -102,6 +103,20 @@ CRITEO = Schema("criteo", "\t", False,
                 [("click", INT)] + [(f"I{i}", BUCKET) for i in range(1, 14)] + [(f"C{i}", HEX) for i in range(1, 27)],
                 feat_types=lambda n: "<cat>" if "C" in n else "<num>", shuffle=False)
 SCHEMAS = {"avazu": AVAZU, "criteo": CRITEO}
+
+
+def _without_label(schema, name):
+    """The schema of the same file without its label field (a file to be scored): label=None, labels come back None."""
+    fields = [(n, k) for n, k in zip(schema.source_names, schema.kinds) if n != schema.label]
+    return Schema(name, schema.delimiter, schema.header, fields, feat_types=lambda n: schema.feat_types[n],
+                  shuffle=schema.shuffle, label=None)
+
+
+# Avazu's test.gz (`id`, then hour, C1, ... — no `click`) and Criteo's test.txt (39 fields, no click): the same
+# columns, kinds and codes as the labelled files, so a vocabulary saved from those applies as it is.
+AVAZU_UNLABELED = _without_label(AVAZU, "avazu-unlabeled")
+CRITEO_UNLABELED = _without_label(CRITEO, "criteo-unlabeled")
+UNLABELED = {"avazu": AVAZU_UNLABELED, "criteo": CRITEO_UNLABELED}
 
 
 def bucket_of(v):
@@ -263,13 +278,14 @@ class _Columns:
         self.t = new
 
 
-def _read_stream(stream_, schema, where, device, chunk_bytes, mode, size_hint=0, timing=None):
+def _iter_stream(stream_, schema, where, device, chunk_bytes, mode, place, timing=None):
+    """The chunk loop: copy, index, check the header, parse.  place(n_lines, n_bytes) -> (out, row0): where the chunk's
+    lines go (parse_lines); yields (out, row0, n_lines) per chunk that holds lines.  `timing` is filled at the end."""
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise MapxError("mapx.rawtext parses on the device (HIP); there is no CPU path")
     if chunk_bytes is not None and not (1 <= chunk_bytes <= MAX_CHUNK):
         raise ValueError("chunk_bytes must lie in [1, 2^30]")
-    cols = _Columns(len(schema.columns), dev)
     header_pending = schema.header
     pinned = dbuf = None
     t_read = t_copy = t_dev = 0.0
@@ -297,29 +313,71 @@ def _read_stream(stream_, schema, where, device, chunk_bytes, mode, size_hint=0,
             first_no = int(line_no[0].item())
             check_header(where, schema, head, line0 + first_no + 1)
             line_start, line_no, n_lines, header_pending = line_start[1:], line_no[1:], n_lines - 1, False
+        out = None
         if n_lines:
-            guess = 0
-            if cols.t is None and size_hint > n:                       # a plain file: rows of this chunk, scaled
-                guess = int(n_lines * (size_hint / n) * 1.02) + 64
-            cols.reserve(n_lines, guess)
-            bad = parse_lines(dbuf, n, line_start, line_no, schema, cols.t, row0=cols.rows, mode=mode)
+            out, row0 = place(n_lines, n)
+            bad = parse_lines(dbuf, n, line_start, line_no, schema, out, row0=row0, mode=mode)
             if bad is not None:
                 raise _error(where, schema, line0 + bad[0] + 1, bad[1], bad[2])
-            cols.rows += n_lines
         if timing is not None:
             torch.cuda.synchronize(dev)
+        t3 = clock()
+        t_dev += t3 - t2
+        if out is not None:
+            yield out, row0, n_lines               # (the consumer's time is nobody's share)
         t0 = clock()
-        t_dev += t0 - t2
     if header_pending:
         raise ValueError(f"{where}: no header line")
     if timing is not None:
         timing.update(read_s=t_read, copy_s=t_copy, device_s=t_dev)
+
+
+def _read_stream(stream_, schema, where, device, chunk_bytes, mode, size_hint=0, timing=None):
+    """The whole stream in one [n_columns, N] matrix: every chunk is parsed straight into its place."""
+    cols = _Columns(len(schema.columns), torch.device(device))
+
+    def place(n_lines, n_bytes):
+        guess = 0
+        if cols.t is None and size_hint > n_bytes:                     # a plain file: rows of this chunk, scaled
+            guess = int(n_lines * (size_hint / n_bytes) * 1.02) + 64
+        cols.reserve(n_lines, guess)
+        return cols.t, cols.rows
+    for _out, _row0, n_lines in _iter_stream(stream_, schema, where, device, chunk_bytes, mode, place, timing):
+        cols.rows += n_lines
     cols.reserve(0)
     N = cols.rows
     columns = {name: cols.t[j, :N] for j, name in enumerate(schema.columns)}
-    labels = columns.pop(schema.label)
+    labels = columns.pop(schema.label) if schema.label is not None else None
     decode = {name: schema.decoder(name) for name in columns}
     return labels, columns, decode, set(schema.string_columns)
+
+
+def _open(path):
+    path = os.fspath(path)
+    return gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+
+
+def iter_columns(path, schema, device="cuda", chunk_bytes=256 << 20, mode=0, timing=None):
+    """read_columns one chunk at a time, for files that need not fit the device: yields, per chunk that holds lines,
+    (labels int64 [n] | None for a schema without a label, int64 [n_columns, n] = the feature columns in the
+    schema's order, a matrix of the chunk's own), the chunks in file order.  `path`: a file's path (`.gz` streamed
+    through gzip) or an open binary stream.  Device memory in use is one chunk's text and columns."""
+    stream_ = path if hasattr(path, "read") else _open(path)
+    where = getattr(path, "name", "<stream>") if hasattr(path, "read") else os.fspath(path)
+    dev = torch.device(device)
+    n_cols = len(schema.columns)
+    li = schema.columns.index(schema.label) if schema.label is not None else None
+    feat = [j for j in range(n_cols) if j != li]
+    try:
+        place = lambda n_lines, _n: (torch.empty(n_cols, n_lines, dtype=torch.int64, device=dev), 0)
+        for out, _row0, _n in _iter_stream(stream_, schema, where, dev, chunk_bytes, mode, place, timing):
+            if li is None:
+                yield None, out
+            else:
+                yield out[li], (out[1:] if li == 0 else out[feat])
+    finally:
+        if stream_ is not path:
+            stream_.close()
 
 
 def read_columns(path, schema, device="cuda", chunk_bytes=256 << 20, mode=0, timing=None):
@@ -328,9 +386,8 @@ def read_columns(path, schema, device="cuda", chunk_bytes=256 << 20, mode=0, tim
     mode: 0 = every wave stages its lines in LDS when they fit, 1 = every wave reads global memory.
     timing: a dict that receives the seconds spent reading the file, copying to the device and on the device."""
     path = os.fspath(path)
-    gz = path.endswith(".gz")
-    with (gzip.open(path, "rb") if gz else open(path, "rb")) as f:
-        size = 0 if gz else os.fstat(f.fileno()).st_size
+    with _open(path) as f:
+        size = 0 if path.endswith(".gz") else os.fstat(f.fileno()).st_size
         return _read_stream(f, schema, path, device, chunk_bytes, mode, size_hint=size, timing=timing)
 
 
