@@ -535,6 +535,19 @@ int mapx_bce_with_logits(const float* logits, const float* labels, int64_t n, fl
 size_t mapx_eval_metrics_workspace_bytes(int64_t n);
 int mapx_eval_metrics(const float* logits, const float* labels, int64_t n, double* out6, void* ws,
                       size_t ws_bytes, hipStream_t stream);
+/* Sliced evaluation (csrc/slice_metrics.hip): the same quantities per group of a column of group ids.
+ * groups [n] int32 with values in [0, n_groups); the five outputs (device, n_groups elements each, zeroed by the call
+ * for empty groups): rows, positives, u2 = twice the group's U statistic on the fp32 sigmoid (a positive above a
+ * negative counts 2, a tie 1: AUC_g = u2 / (2 * positives * negatives)), sum_prob = the sum of the fp32 sigmoid in
+ * f64, sum_loss = the sum of mapx_eval_metrics' log-loss row terms (clip eps = 2^-52).  The integers are exact; the
+ * f64 sums are bitwise reproducible and do not depend on the order of the input rows.  A NaN logit ranks as p = 1.
+ * status2 (device, written by the call): {rows whose group id lies outside [0, n_groups), the first such row or -1};
+ * such rows are filed under group 0 and nothing is indexed with them: the caller reads status2 and refuses.
+ * 1 <= n < 2^31, 1 <= n_groups < 2^31. */
+size_t mapx_slice_metrics_workspace_bytes(int64_t n, int64_t n_groups);
+int mapx_slice_metrics(const float* logits, const float* labels, const int32_t* groups, int64_t n, int64_t n_groups,
+                       int64_t* rows, int64_t* positives, uint64_t* u2, double* sum_prob, double* sum_loss,
+                       int64_t* status2, void* ws, size_t ws_bytes, hipStream_t stream);
 /* trainer.py:217-232 (MFP): masked_index_in NULL -> Philox, keyed by (seed, offset + *offset_dev).
  * draw (ignored when masked_index_in is given; the same in mapx_dynamic_mask_mfp_rows and mapx_dynamic_mask_rfd):
  *   0  with replacement (sampling_method="randint"): masked_index[b,l] = word x of Philox(counter b*L + l) scaled to

@@ -2242,6 +2242,57 @@ def eval_metrics(logits, labels):
     return dict(auc=auc, logloss=ll, avg_logits=ml, avg_probs=mp, positives=int(npos), negatives=int(nneg))
 
 
+SLICE_OUTPUTS = (("rows", torch.int64), ("positives", torch.int64), ("u2", torch.int64),
+                 ("sum_prob", torch.float64), ("sum_loss", torch.float64))
+
+
+def slice_metrics(logits, labels, groups, n_groups, out=None):
+    """eval_metrics' quantities per group of a column (include/mapx_hip.h: mapx_slice_metrics).
+    groups: int32 or int64 [n] with values in [0, n_groups).  -> (rows i64, positives i64, u2, sum_prob f64,
+    sum_loss f64), device tensors of n_groups elements; u2 (twice the group's U statistic, < 2^62) is held as int64.
+    AUC_g = u2 / (2 * positives * (rows - positives)); the integers are exact, the sums bitwise reproducible.
+    out: the five tensors to write (contiguous, these element types).  A group id outside the range raises ValueError
+    naming the first one; one host read of two words."""
+    require_gpu(logits, labels, groups)
+    G = int(n_groups)
+    if not 1 <= G < 2 ** 31:
+        raise ValueError(f"slice_metrics: 1 <= n_groups < 2^31 (got {n_groups})")
+    if groups.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"slice_metrics: groups is int32 or int64, got {groups.dtype}")
+    logits = logits.contiguous().view(-1).float()
+    labels = labels.contiguous().view(-1).float()
+    groups = groups.contiguous().view(-1)
+    n = logits.numel()
+    if labels.numel() != n or groups.numel() != n:
+        raise ValueError(f"slice_metrics: {n} logits, {labels.numel()} labels, {groups.numel()} group ids")
+    if not n < 2 ** 31:
+        raise ValueError(f"slice_metrics: at most 2^31 - 1 rows (got {n})")
+    dev = logits.device
+    if out is None:
+        out = tuple(torch.empty(G, dtype=dt, device=dev) for _, dt in SLICE_OUTPUTS)
+    out = tuple(out)
+    require_gpu(*out)
+    if len(out) != 5 or any(o.dtype != dt or o.numel() != G or not o.is_contiguous()
+                            for o, (_, dt) in zip(out, SLICE_OUTPUTS)):
+        raise TypeError(f"slice_metrics: out is five contiguous tensors of {G} elements: "
+                        + ", ".join(f"{k} {str(dt)[6:]}" for k, dt in SLICE_OUTPUTS))
+    if n == 0:
+        for o in out:
+            o.zero_()
+        return out
+    # (an int64 id beyond int32 stays outside [0, G) when narrowed: G < 2^31)
+    g32 = groups if groups.dtype == torch.int32 else groups.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = scratch(lib.mapx_slice_metrics_workspace_bytes(n, G), dev)
+    check(lib.mapx_slice_metrics(ptr(logits), ptr(labels), ptr(g32), n, G, *(ptr(o) for o in out), ptr(status),
+                                 ptr(ws), ws.numel(), stream()))
+    bad, first = status.tolist()
+    if bad:
+        raise ValueError(f"slice_metrics: {bad} group id(s) outside [0, {G}); the first is {int(groups[first])} "
+                         f"at row {first}")
+    return out
+
+
 def _check_distinct(name, L, F):
     if L > F:
         raise ValueError(f"{name}: distinct=True draws L distinct fields per row and needs L <= F (L = {L}, F = {F})")

@@ -4,6 +4,7 @@
                          [--unlabeled] --out SDIR [--batch_size 4096] [--chunk_mb 256] <run.py's model flags>
     python -m mapx.score --model OUT/1234.model --data_dir DIR --dataset_name avazu [--split test|valid|train|all]
                          --out SDIR <run.py's model flags>
+    either form: [--group_by C1,site_id,@oov [--top 20]]   sliced evaluation (labels of both classes needed)
 
 writes SDIR/probs.npy (f32 [N]), logits.npy (f32 [N]), oov_fields.npy (u8 [N]: the fields of a row that took their
 field's <oov> id) and score.json, rows in file order.  One device; no optimizer, no labels needed.
@@ -12,7 +13,11 @@ A scoring step is  mapx_score_block -> the model's forward -> mapx_score_sink ->
 captured as one hipGraph after a few eager steps and replayed with nothing but the device-side cursor changing
 (`Scorer`; MAPX_GRAPH=0 keeps the eager loop).  Batches are ALWAYS the rows [kB, (k+1)B) of the input stream, however
 the caller cuts the stream into pieces: fp32-mode products cut their activations at a per-batch magnitude, so a
-row's bits depend on its batch mates."""
+row's bits depend on its batch mates.
+
+--group_by adds, per named field (and '@oov': the rows by their count of <oov> fields), AUC / log-loss / CTR /
+calibration per value and GAUC, the rows-weighted mean of the per-value AUCs: slices.json, slices_<name>.npz and
+score.json's "slices" (ops.slice_metrics, csrc/slice_metrics.hip: one launch sequence per column)."""
 import argparse
 import json
 import logging
@@ -239,6 +244,83 @@ def metrics_of(logits, labels):
         return None, str(e)
 
 
+# ------------------------------------------------------------------------------- slices of a column
+OOV_COLUMN = "@oov"                 # the pseudo-column of --group_by: a row's count of fields that took their <oov> id
+SLICE_ARRAYS = tuple(k for k, _ in ops.SLICE_OUTPUTS)
+
+GroupColumn = namedtuple("GroupColumn", "name column base groups")
+
+
+def group_columns(group_by, names, oov_ids, first_base):
+    """The columns of --group_by -> [GroupColumn(name, column, base, groups)].  names / oov_ids: the fields in order and
+    the <oov> id of each; first_base: the first id of the first field.  A field's ids are [base, <oov> id], base the id
+    behind the previous field's <oov>: the group of a row is id - base, `groups` = <oov> id - base + 1 of them.
+    '@oov': column None, base 0, the group is the row's oov_fields count, F + 1 groups.  ValueError names an unknown
+    or repeated column."""
+    out, seen = [], set()
+    for g in group_by:
+        if g in seen:
+            raise ValueError(f"group_by: {g!r} twice")
+        seen.add(g)
+        if g == OOV_COLUMN:
+            out.append(GroupColumn(g, None, 0, len(names) + 1))
+            continue
+        if g not in names:
+            raise ValueError(f"group_by: {g!r} is not a field ({', '.join(names)}) or {OOV_COLUMN}")
+        c = list(names).index(g)
+        base = int(first_base) if c == 0 else int(oov_ids[c - 1]) + 1
+        if int(oov_ids[c]) < base or (c > 0 and int(oov_ids[c - 1]) < 0):
+            raise ValueError(f"group_by: field {g!r} has no id range ending at its <oov> id in this vocabulary")
+        out.append(GroupColumn(g, c, base, int(oov_ids[c]) - base + 1))
+    return out
+
+
+def group_names(col, feat_map):
+    """The labels of a column's groups: the raw value strings of feat_map ('<oov>' the last), the counts for @oov."""
+    if col.column is None:
+        return [str(k) for k in range(col.groups)]
+    out, cut = [None] * col.groups, len(col.name) + 1
+    for key, i in feat_map.items():
+        if col.base <= i < col.base + col.groups:
+            out[i - col.base] = key[cut:]
+    return out
+
+
+def slice_report(rows, positives, u2, sum_prob, sum_loss, top=20, names=None):
+    """ops.slice_metrics' five arrays (host) -> the report of one column, in float64:
+         gauc       sum(rows_g * auc_g) / sum(rows_g) over the groups that hold both classes (None when there is none)
+         gauc_rows  the rows those groups hold;   groups: the non-empty groups
+         top        the `top` groups by rows (ties by group id): group, name, rows, positives, auc = u2 / (2 pos neg)
+                    (NaN where a class is missing), logloss, ctr, mean_prob, calibration = mean_prob / ctr (NaN at ctr 0)."""
+    rows, positives = np.asarray(rows, dtype=np.int64), np.asarray(positives, dtype=np.int64)
+    u2 = np.asarray(u2).astype(np.uint64).astype(np.float64)
+    r, p = rows.astype(np.float64), positives.astype(np.float64)
+    both = (positives > 0) & (positives < rows)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        auc = np.where(both, (u2 * 0.5) / (p * (r - p)), np.nan)
+        ctr = p / r
+        mean_prob = np.asarray(sum_prob, dtype=np.float64) / r
+        logloss = np.asarray(sum_loss, dtype=np.float64) / r
+        calibration = np.where(p > 0, mean_prob / ctr, np.nan)
+    gauc_rows = int(rows[both].sum())
+    gauc = float((r[both] * auc[both]).sum() / gauc_rows) if gauc_rows else None
+    order = np.lexsort((np.arange(len(rows)), -rows))[:max(int(top), 0)]
+    order = order[rows[order] > 0]
+    listed = [dict(group=int(g), name=None if names is None else names[g], rows=int(rows[g]),
+                   positives=int(positives[g]), auc=float(auc[g]), logloss=float(logloss[g]), ctr=float(ctr[g]),
+                   mean_prob=float(mean_prob[g]), calibration=float(calibration[g])) for g in order.tolist()]
+    return dict(gauc=gauc, gauc_rows=gauc_rows, groups=int((rows > 0).sum()), top=listed)
+
+
+def _json_safe(x):
+    """NaN / inf -> null: what a strict JSON reader takes."""
+    if isinstance(x, dict):
+        return {k: _json_safe(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_json_safe(v) for v in x]
+    return None if isinstance(x, float) and not np.isfinite(x) else x
+
+
 # ------------------------------------------------------------------------------- checkpoints
 PRETRAIN_KEYS = ("feat_encoder.", "mfp_criterion.", "pred_rfd.")
 
@@ -285,18 +367,38 @@ def _to_host(parts, s):
             parts[k].append(t.cpu().numpy())
 
 
-def _result(parts, labels, names, oov_rows, scorer, extra):
+def _no_slices(why):
+    return ValueError(f"group_by needs the labels of both classes: {why}")
+
+
+def _result(parts, labels, names, oov_rows, scorer, extra, slices=None):
+    """slices: None, or [(GroupColumn, its group ids as int32 pieces on the host | None for @oov, group names)]: the
+    columns go to the device once, with the logits."""
     dts = (np.float32, np.float32, np.uint8)
     logits, probs, oov_fields = (np.concatenate(p) if p else np.empty(0, dtype=dt) for p, dt in zip(parts, dts))
-    metrics, why = None, "no labels"
+    metrics, why, dev_logits, dev_y = None, "no labels", None, None
     if labels is not None:
         y = np.concatenate(labels) if labels else np.empty(0, dtype=np.int64)
         dev = scorer.device
-        metrics, why = metrics_of(torch.from_numpy(logits).to(dev), torch.from_numpy(y).to(dev))
+        dev_logits, dev_y = torch.from_numpy(logits).to(dev), torch.from_numpy(y).to(dev)
+        metrics, why = metrics_of(dev_logits, dev_y)
     info = dict(rows=int(logits.shape[0]), batch_size=scorer.B, graph=scorer.graph is not None,
                 oov_rows={n: int(c) for n, c in zip(names, oov_rows)}, metrics=metrics, metrics_reason=why)
     info.update(extra)
-    return dict(logits=logits, probs=probs, oov_fields=oov_fields, info=info)
+    res = dict(logits=logits, probs=probs, oov_fields=oov_fields, info=info)
+    if slices:
+        if metrics is None:
+            raise _no_slices(why)
+        res["slices"], info["slices"] = {}, {}
+        for col, pieces, gnames in slices:
+            g = oov_fields.astype(np.int32) if pieces is None else np.concatenate(pieces)
+            out = ops.slice_metrics(dev_logits, dev_y, torch.from_numpy(g).to(scorer.device), col.groups)
+            arrays = {k: t.cpu().numpy() for k, t in zip(SLICE_ARRAYS, out)}
+            arrays["u2"] = arrays["u2"].view(np.uint64)
+            rep = slice_report(**arrays, top=0)
+            info["slices"][col.name] = {k: rep[k] for k in ("gauc", "gauc_rows", "groups")}
+            res["slices"][col.name] = dict(arrays, base=col.base, names=gnames)
+    return res
 
 
 def oov_ids_of(meta, names):
@@ -304,14 +406,23 @@ def oov_ids_of(meta, names):
     return [int(meta["feat_map"].get(f"{n}-<oov>", -1)) for n in names]
 
 
-def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None):
+def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None, group_by=None):
     """Raw text -> scores, chunk by chunk: rawtext.iter_columns -> Vocabulary.encode -> Scorer.push, the results to
     the host per chunk; device memory holds one chunk and the scorer's staging area whatever the file's size.
     schema: rawtext.SCHEMAS[...] or rawtext.UNLABELED[...] (no label field: metrics null).  `path`: a path or an open
     binary stream.  timing: a dict that receives read_s / copy_s / device_s (parse) of iter_columns and encode_s,
-    score_s, host_s (results to the host).  -> dict(logits, probs, oov_fields: numpy [N]; info: score.json's content)."""
+    score_s, host_s (results to the host).  -> dict(logits, probs, oov_fields: numpy [N]; info: score.json's content).
+    group_by: field names and '@oov' (group_columns): the result gains 'slices' {name: ops.slice_metrics' five arrays
+    over the whole file, base, names} and info 'slices' {name: gauc, gauc_rows, groups}; the requested columns are
+    kept per chunk as int32 on the host, as the labels are.  ValueError without labels of both classes."""
     from . import rawtext
     names, F = voc.field_names, len(voc.fields)
+    slices = None
+    if group_by:
+        if schema.label is None:
+            raise _no_slices("no labels")
+        cols = group_columns(group_by, names, [f.oov for f in voc.fields], voc.fields[0].base)
+        slices = [(c, None if c.column is None else [], group_names(c, voc.feat_map)) for c in cols]
     parts, labels, oov_rows = ([], [], []), ([] if schema.label is not None else None), [0] * F
     t_enc = t_score = t_host = 0.0
     clock, sync = time.perf_counter, (lambda: torch.cuda.synchronize(scorer.device)) if timing is not None else (lambda: None)
@@ -325,6 +436,9 @@ def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None
         _to_host(parts, s)
         if labels is not None:
             labels.append(y.cpu().numpy())
+        for c, pieces, _ in slices or ():
+            if pieces is not None:
+                pieces.append((ids[:, c.column] - c.base).to(torch.int32).cpu().numpy())
         t3 = clock()
         t_enc, t_score, t_host = t_enc + t1 - t0, t_score + t2 - t1, t_host + t3 - t2
     t0 = clock()
@@ -333,7 +447,7 @@ def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None
     _to_host(parts, s)
     if timing is not None:
         timing.update(encode_s=t_enc, score_s=t_score + t1 - t0, host_s=t_host + clock() - t1)
-    return _result(parts, labels, names, oov_rows, scorer, dict(source=str(getattr(path, "name", path))))
+    return _result(parts, labels, names, oov_rows, scorer, dict(source=str(getattr(path, "name", path))), slices)
 
 
 def read_dataset(data_dir, dataset_name, split="test"):
@@ -353,9 +467,18 @@ def read_dataset(data_dir, dataset_name, split="test"):
     return meta, np.ascontiguousarray(feat_ids, dtype=np.int64), np.asarray(labels)
 
 
-def score_dataset(scorer, meta, feat_ids, labels=None, names=None):
-    """A table on the host -> scores, one staging area of rows on the device at a time.  -> as score_raw_file."""
+def score_dataset(scorer, meta, feat_ids, labels=None, names=None, group_by=None):
+    """A table on the host -> scores, one staging area of rows on the device at a time.  -> as score_raw_file; the id
+    ranges of group_by's fields come from the meta's feat_map."""
     names = names if names is not None else [n for n in meta["field_names"] if n != "<rsv>"]
+    slices = None
+    if group_by:
+        if labels is None:
+            raise _no_slices("no labels")
+        oov = oov_ids_of(meta, names)
+        first = min((i for k, i in meta["feat_map"].items() if k.startswith(names[0] + "-")), default=0)
+        slices = [(c, None if c.column is None else [(feat_ids[:, c.column] - c.base).astype(np.int32)],
+                   group_names(c, meta["feat_map"])) for c in group_columns(group_by, names, oov, first)]
     oov_id = scorer.oov_id
     parts, oov_rows = ([], [], []), torch.zeros(feat_ids.shape[1], dtype=torch.int64, device=scorer.device)
     for r in range(0, feat_ids.shape[0], scorer.cap):
@@ -364,13 +487,23 @@ def score_dataset(scorer, meta, feat_ids, labels=None, names=None):
         _to_host(parts, scorer.push(ids))
     _to_host(parts, scorer.finish())
     y = None if labels is None else [np.asarray(labels).astype(np.int64)]
-    return _result(parts, y, names, oov_rows.tolist(), scorer, {})
+    return _result(parts, y, names, oov_rows.tolist(), scorer, {}, slices)
 
 
-def write_scores(out_dir, res, **info):
+def write_scores(out_dir, res, top=20, **info):
+    """probs.npy, logits.npy, oov_fields.npy, score.json; with slices (group_by) also slices_<name>.npz (the five
+    arrays and base) per column and slices.json {name: slice_report(top)}."""
     os.makedirs(out_dir, exist_ok=True)
     for k in ("probs", "logits", "oov_fields"):
         np.save(os.path.join(out_dir, f"{k}.npy"), res[k])
+    if "slices" in res:
+        reports = {}
+        for name, s in res["slices"].items():
+            arrays = {k: s[k] for k in SLICE_ARRAYS}
+            np.savez(os.path.join(out_dir, f"slices_{name}.npz"), base=np.int64(s["base"]), **arrays)
+            reports[name] = slice_report(**arrays, top=top, names=s["names"])
+        with open(os.path.join(out_dir, "slices.json"), "w") as f:
+            json.dump(_json_safe(reports), f, indent=1, allow_nan=False)
     doc = dict(res["info"], **info)
     with open(os.path.join(out_dir, "score.json"), "w") as f:
         json.dump(doc, f, indent=1)
@@ -393,6 +526,10 @@ def parser():
                    help="rows of --data_dir to score (all: the whole table, no split.pkl needed)")
     p.add_argument("--batch_size", type=_positive, default=4096, help="rows per scoring step")
     p.add_argument("--chunk_mb", type=_positive, default=256, help="bytes of the raw file on the device at a time (<= 1024)")
+    p.add_argument("--group_by", metavar="NAME[,NAME...]", type=lambda s: [x for x in s.split(",") if x],
+                   help=f"sliced evaluation: AUC, GAUC, log-loss and calibration per value of these fields ({OOV_COLUMN}: "
+                        "per count of <oov> fields) -> slices.json, slices_<name>.npz; needs labels of both classes")
+    p.add_argument("--top", type=_positive, default=20, help="groups listed per column in slices.json, by rows")
     add_flags(p, MODEL_FLAGS + EXTENSION_MODEL_FLAGS)
     return p
 
@@ -406,6 +543,18 @@ def parse_args(argv=None):
         p.error("--vocab / --unlabeled go with --raw")
     if args.chunk_mb > 1024:
         p.error("--chunk_mb: at most 1024")
+    if args.group_by:
+        if args.unlabeled:
+            p.error("--group_by needs labels: it does not go with --unlabeled")
+        if len(set(args.group_by)) != len(args.group_by):
+            p.error(f"--group_by: a column twice in {args.group_by}")
+        if args.raw is not None:                  # (the fields of --data_dir are known when its meta is read)
+            from . import rawtext
+            schema = rawtext.SCHEMAS[args.dataset]
+            known = [c for c in schema.columns if c != schema.label] + [OOV_COLUMN]
+            for g in args.group_by:
+                if g not in known:
+                    p.error(f"--group_by: {g!r} is not a field of {args.dataset} ({', '.join(known)})")
     return args
 
 
@@ -434,14 +583,14 @@ def main(argv=None):
         voc = vocab.Vocabulary.from_meta(args.vocab, schema, device=device)
         model = build_model(args, voc.input_size, len(voc.fields), device)
         scorer = Scorer(model, args.batch_size, device, oov_id=[f.oov for f in voc.fields])
-        res = score_raw_file(scorer, args.raw, schema, voc, chunk_bytes=args.chunk_mb << 20)
+        res = score_raw_file(scorer, args.raw, schema, voc, chunk_bytes=args.chunk_mb << 20, group_by=args.group_by)
     else:
         meta, feat_ids, labels = read_dataset(args.data_dir, args.dataset_name, args.split)
         names = [n for n in meta["field_names"] if n != "<rsv>"]
         model = build_model(args, len(meta["feat_map"]), len(meta["field_map"]) - 1, device)
         scorer = Scorer(model, args.batch_size, device, oov_id=oov_ids_of(meta, names))
-        res = score_dataset(scorer, meta, feat_ids, labels, names=names)
-    doc = write_scores(args.out, res, model=args.model, compute_dtype=args.compute_dtype,
+        res = score_dataset(scorer, meta, feat_ids, labels, names=names, group_by=args.group_by)
+    doc = write_scores(args.out, res, top=args.top, model=args.model, compute_dtype=args.compute_dtype,
                        seconds=round(time.time() - t0, 3))
     m = doc["metrics"]
     print(f"{args.out}: {doc['rows']} rows, batch {doc['batch_size']}, {args.compute_dtype}, "
