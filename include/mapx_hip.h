@@ -831,6 +831,34 @@ int mapx_vocab_apply(const int64_t* const* columns, int64_t n, int n_fields, con
                      const int64_t* base, const int64_t* flag, const int64_t* field_type, int64_t missing_type,
                      int64_t* feat_ids, int64_t ld_ids, int64_t* type_ids_opt, int64_t ld_types, int64_t* oov_rows,
                      int32_t* err, int mode, hipStream_t stream);
+/* A saved vocabulary GROWN on a later file, and a checkpoint's [V, W] tables moved to the grown id space.
+ * (Added inside ABI 49: purely additive, no existing entry changed; a binding that needs them finds them by name.)
+ *  count_missing  mapx_vocab_count behind a lookup: only the rows of `keys` [n] whose value is NOT among the saved
+ *          field's keys are counted into the fresh count table (table_keys / table_count / table_first [capacity], as
+ *          mapx_vocab_table_init leaves them); compact / rank_keys / assign then rank the misses as they rank a fit.
+ *          The saved field is the slice [slot0, slot0 + slots) of mapx_vocab_apply_load's two arrays
+ *          [n_slots_total], holding n_saved keys (0: nothing is probed, the arrays may be NULL).
+ *          *err_flag (set by the entry) |= 1: a value equals INT64_MIN (not counted); |= 2: count table full.
+ *          *missing_rows (set by the entry) = rows whose value the saved field does not hold: ballot + popcount per
+ *          wave, one integer atomic per workgroup.  Integer atomics only: no result depends on arrival order.
+ *  table_migrate  dst [v_new, width] f32 (row pitch ld_dst) from src [v_old, width] (row pitch ld_src) in one launch.
+ *          n_old, added, base_old, base_new: device i64 [n_fields] (n_fields <= MAPX_RT_MAX_FIELDS), field f owning
+ *          the new ids [base_new[f], base_new[f] + n_old[f] + added[f]] (the last one its <oov>), base_new ascending.
+ *          Source of new row r: r < base_new[0] (reserved) -> row r; rank = r - base_new[f] < n_old[f] ->
+ *          row base_old[f] + rank; otherwise the old <oov> row base_old[f] + n_old[f] — except that with fresh_opt
+ *          [n_fresh, width] (row pitch ld_fresh) the j-th added row counted over all fields reads fresh[j].
+ *          16-byte accesses when width % 4 == 0 and all bases and pitches are multiples of 16 bytes, single
+ *          elements otherwise.  Nothing outside [v_new, width] of dst is written; src and dst must not overlap.
+ *          *err (set by the entry) = 1 when the plan puts a row outside src / fresh or behind the last field: such
+ *          rows are written as zeros, nothing is read out of bounds.  A pure gather: bitwise reproducible. */
+int mapx_vocab_count_missing(const int64_t* keys, int64_t n, const int64_t* saved_table_keys,
+                             const int32_t* saved_table_rank, int64_t slot0, int64_t slots, int64_t n_slots_total,
+                             int64_t n_saved, int64_t* table_keys, int32_t* table_count, int32_t* table_first,
+                             int64_t capacity, int* err_flag, int64_t* missing_rows, hipStream_t stream);
+int mapx_table_migrate(const float* src, int64_t ld_src, int64_t v_old, float* dst, int64_t ld_dst, int64_t v_new,
+                       int width, int n_fields, const int64_t* n_old, const int64_t* added, const int64_t* base_old,
+                       const int64_t* base_new, const float* fresh_opt, int64_t ld_fresh, int64_t n_fresh,
+                       int32_t* err, hipStream_t stream);
 
 /* ------------------------------------------------------------------ raw delimited text -> int64 columns
  * read_feat of data_preprocess/proc_avazu.py:26-85 and proc_criteo.py:24-88: one chunk of the raw file, cut at a

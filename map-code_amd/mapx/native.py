@@ -162,6 +162,8 @@ SIGNATURES = {
     "mapx_vocab_apply_table_slots": (_sz, [_i64]),
     "mapx_vocab_apply_load": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _p, _p]),
     "mapx_vocab_apply": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _p]),
+    "mapx_vocab_count_missing": (_i, [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p]),
+    "mapx_table_migrate": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "mapx_rawtext_index_workspace_bytes": (_sz, [_i64]),
     "mapx_rawtext_index": (_i, [_p, _i64, _p, _sz, _p, _p, _i64, _p, _p]),
     "mapx_rawtext_parse": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _i, _p, _i64, _i64, _i, _p, _i, _p]),

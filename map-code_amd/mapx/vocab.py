@@ -86,6 +86,15 @@ def fit_field(keys, n_core, base, name="", capacity=None):
     tcount, tfirst, err = torch.empty(cap, **i32), torch.empty(cap, **i32), torch.zeros(1, **i32)
     check(lib.mapx_vocab_table_init(ptr(tkey), ptr(tcount), ptr(tfirst), cap, stream()))
     check(lib.mapx_vocab_count(ptr(keys), N, ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(err), stream()))
+    ranked_keys, ranked_counts, U = _rank_counted(name, tkey, tcount, tfirst, cap, N, err, n_core)
+    return FieldVocab(name, ranked_keys, ranked_counts, base, U)
+
+
+def _rank_counted(name, tkey, tcount, tfirst, cap, N, err, n_core):
+    """A filled count table (mapx_vocab_count, or mapx_vocab_count_missing for the values a saved field lacks) of a
+    column of N rows -> (kept keys in id order, their counts, number of distinct values counted): compact, the two
+    stable sorts, the n-core cut.  `err`: the counting launch's error word."""
+    dev, i32 = tkey.device, dict(dtype=torch.int32, device=tkey.device)
     ent_cap = min(N, cap)
     ekey = torch.empty(ent_cap, dtype=torch.int64, device=dev)
     ecount, efirst, nm = torch.empty(ent_cap, **i32), torch.empty(ent_cap, **i32), torch.zeros(2, **i32)
@@ -96,6 +105,8 @@ def fit_field(keys, n_core, base, name="", capacity=None):
         raise ValueError(f"field {name!r}: the value -2^63 is reserved by the vocabulary builder")
     if e & 2:
         raise MapxError(f"field {name!r}: hash table of {cap} slots is full")
+    if U == 0:                                                   # (a grown field none of whose rows is missing)
+        return ekey[:0], ecount[:0], 0
     # rank = (count descending, first occurrence ascending): stable sort by first position, then by max - count
     by_first = ops.SegPlan(efirst[:U].contiguous(), N).perm
     keys2 = torch.empty(U, **i32)
@@ -106,7 +117,7 @@ def fit_field(keys, n_core, base, name="", capacity=None):
     check(lib.mapx_vocab_assign(ptr(by_first), ptr(by_count), ptr(ecount), ptr(ekey), U, int(n_core),
                                 ptr(ranked_keys), ptr(ranked_counts), ptr(n_kept), stream()))
     k = int(n_kept.item())
-    return FieldVocab(name, ranked_keys[:k], ranked_counts[:k], base, U)
+    return ranked_keys[:k], ranked_counts[:k], U
 
 
 def build_field(keys, n_core, base, out_col, name="", capacity=None):
@@ -457,6 +468,82 @@ class Vocabulary:
             raise TypeError(f"field {f.name!r}: dtype {a.dtype} (integers or hash strings)")
         return torch.from_numpy(np.ascontiguousarray(codes)).to(self.device)
 
+    def _columns(self, columns, who):
+        """The F input columns of encode / grow as contiguous device int64 vectors of one length.  -> (columns, N)."""
+        F = len(self.fields)
+        if isinstance(columns, dict):
+            if list(columns) != self.field_names:
+                raise ValueError(f"{who}: columns {list(columns)} are not the vocabulary's fields {self.field_names}")
+            columns = list(columns.values())
+        if len(columns) != F:
+            raise ValueError(f"{who}: {len(columns)} columns for {F} fields")
+        cols = [self._column(f, c) for f, c in zip(self.fields, columns)]
+        N = cols[0].numel()
+        if any(c.numel() != N for c in cols):
+            raise ValueError(f"{who}: columns of different lengths")
+        return cols, N
+
+    def grow(self, columns, n_core, capacities=None):
+        """The vocabulary extended by the values of `columns` (as encode takes them) that it does not hold: per field
+        the misses are counted behind a lookup in the field's table slice (mapx_vocab_count_missing), ranked by the
+        fit's own rule — descending count, ties by first occurrence, i.e. Counter(misses).most_common() — through
+        fit_field's compact / sort / assign steps, and those seen at least n_core times are appended behind the
+        field's keys; every old key keeps its rank, ids stay consecutive (base'_f = 10 + sum_{g<f} (n_g + a_g + 1)).
+        -> (grown Vocabulary, added: keys appended per field, missing_before: rows per field that take <oov> under
+        this vocabulary, missing_after: ... under the grown one) — F host ints each.  The grown feat_map keeps the
+        old keys' strings and order and prints the added keys with this vocabulary's decoders.  capacities: count
+        table slots per field (each a power of two >= 64 and more than the field's distinct misses) instead of the
+        fit's default.  ValueError, naming the field, when a column holds -2^63."""
+        F, dev = len(self.fields), self.device
+        cols, N = self._columns(columns, "grow")
+        if capacities is not None and len(capacities) != F:
+            raise ValueError(f"grow: {len(capacities)} capacities for {F} fields")
+        i32 = dict(dtype=torch.int32, device=dev)
+        tab_off, n_keys = self._par_host[1], self._par_host[2]
+        grown_fields, added, before, after, base = [], [], [], [], self.fields[0].base
+        with torch.cuda.device(dev):
+            for f, (fld, keys) in enumerate(zip(self.fields, cols)):
+                new_keys, miss, kept_rows = np.empty(0, dtype=np.int64), 0, 0
+                if N:
+                    cap = int(capacities[f]) if capacities is not None else \
+                        max(64, 1 << int(np.ceil(np.log2(2 * N + 1))))
+                    tkey = torch.empty(cap, dtype=torch.int64, device=dev)
+                    tcount, tfirst, err = torch.empty(cap, **i32), torch.empty(cap, **i32), torch.zeros(1, **i32)
+                    missing = torch.zeros(1, dtype=torch.int64, device=dev)
+                    check(lib.mapx_vocab_table_init(ptr(tkey), ptr(tcount), ptr(tfirst), cap, stream()))
+                    check(lib.mapx_vocab_count_missing(ptr(keys), N, ptr(self._tkey), ptr(self._trank), int(tab_off[f]),
+                                                       int(tab_off[f + 1] - tab_off[f]), self.n_slots, int(n_keys[f]),
+                                                       ptr(tkey), ptr(tcount), ptr(tfirst), cap, ptr(err), ptr(missing),
+                                                       stream()))
+                    rk, rc, _ = _rank_counted(fld.name, tkey, tcount, tfirst, cap, N, err, n_core)
+                    new_keys, miss, kept_rows = rk.cpu().numpy(), int(missing.item()), int(rc.sum().item())
+                old = fld.keys.cpu().numpy() if torch.is_tensor(fld.keys) else np.asarray(fld.keys)
+                grown_fields.append(FieldKeys(fld.name, np.concatenate([old.astype(np.int64), new_keys]), base))
+                base = grown_fields[-1].oov + 1
+                added.append(len(new_keys))
+                before.append(miss)
+                after.append(miss - kept_rows)
+        old_items = list(self.feat_map)
+        feat_map = {tok: i for i, tok in enumerate(old_items[:self.fields[0].base])}
+        for fld, g, a in zip(self.fields, grown_fields, added):
+            for key in old_items[fld.base:fld.oov]:
+                feat_map[key] = len(feat_map)
+            dec = self.decoders.get(fld.name, lambda v: str(int(v)))
+            for v in g.keys[len(g.keys) - a:].tolist():
+                key = f"{fld.name}-{dec(v)}"
+                if key in feat_map:
+                    raise ValueError(f"grow: the added value {v} of field {fld.name!r} prints as {key!r}, a key the "
+                                     f"vocabulary holds already")
+                feat_map[key] = len(feat_map)
+            feat_map[f"{fld.name}-<oov>"] = len(feat_map)
+            assert feat_map[f"{fld.name}-<oov>"] == g.oov
+        meta = dict(self.meta if self.meta is not None else {"field_names": ["<rsv>"] + self.field_names},
+                    feat_map=feat_map)
+        par = self._par_host
+        grown = Vocabulary(grown_fields, device=dev, flags=par[4, :F].tolist(), field_types=par[5, :F].tolist(),
+                           missing_type=self.missing_type, decoders=self.decoders, meta=meta)
+        return grown, added, before, after
+
     def encode(self, columns, type_ids=False, feat_ids_out=None, type_ids_out=None, mode=0):
         """columns: {field name: column} in the vocabulary's field order, or a sequence of F columns; each a device
         int64 vector or a host array (integers as they are; hash strings through rawtext.encode_hex).
@@ -466,16 +553,7 @@ class Vocabulary:
         pitch to write into.  mode: see mapx_vocab_apply (0: row-contiguous stores through LDS, 1: strided stores).
         ValueError, naming the field, when a column holds -2^63."""
         F = len(self.fields)
-        if isinstance(columns, dict):
-            if list(columns) != self.field_names:
-                raise ValueError(f"encode: columns {list(columns)} are not the vocabulary's fields {self.field_names}")
-            columns = list(columns.values())
-        if len(columns) != F:
-            raise ValueError(f"encode: {len(columns)} columns for {F} fields")
-        cols = [self._column(f, c) for f, c in zip(self.fields, columns)]
-        N = cols[0].numel()
-        if any(c.numel() != N for c in cols):
-            raise ValueError("encode: columns of different lengths")
+        cols, N = self._columns(columns, "encode")
         dev = self.device
 
         def out(t, what):
@@ -519,6 +597,12 @@ def encode_dataset_from_text(path, schema, meta_path, data_dir, dataset_name, ch
         saved = json.load(f)
     voc = Vocabulary.from_meta(saved, schema, device=device)
     labels, columns, _decode, _strings = rawtext.read_columns(path, schema, device=device, chunk_bytes=chunk_bytes)
+    return _encode_and_write(voc, saved, schema, columns, labels, data_dir, dataset_name, split, seed, {})
+
+
+def _encode_and_write(voc, saved, schema, columns, labels, data_dir, dataset_name, split, seed, extra):
+    """The columns of a file through `voc` into a dataset directory, rows in file order; the meta takes field_names /
+    field_map / feat_type_map from the saved meta, feat_map from the vocabulary, and `extra`."""
     feat_ids, oov_rows, type_ids = voc.encode(columns, type_ids=True)
     labels = labels.cpu().numpy()
     N, names = len(labels), voc.field_names
@@ -526,8 +610,27 @@ def encode_dataset_from_text(path, schema, meta_path, data_dir, dataset_name, ch
     feat_type_map = saved.get("feat_type_map") or _feat_type_map(names, schema.feat_types)
     meta = {"index": list(range(N)), "num_pos": int(labels.sum()), "num_neg": int(N - labels.sum()),
             "avg_ctr": float(labels.mean()) if N else 0.0, "field_names": saved["field_names"], "field_map": field_map,
-            "feat_type_map": feat_type_map, "feat_map": saved["feat_map"],
+            "feat_type_map": feat_type_map, "feat_map": voc.feat_map,
             "oov_rows": {n: int(c) for n, c in zip(names, oov_rows)}}
+    meta.update(extra)
     _write_dataset(data_dir, dataset_name, meta, feat_ids, _field_ids(field_map, names, N), type_ids, labels, split,
                    seed)
     return meta, voc.input_size
+
+
+def grow_dataset_from_text(path, schema, meta_path, n_core, data_dir, dataset_name, chunk_bytes=256 << 20, split=None,
+                           seed=42, device="cuda"):
+    """encode_dataset_from_text with the SAVED vocabulary grown on the file first: the file is read once
+    (mapx.rawtext.read_columns), its values the saved feat_map lacks and that occur at least n_core times are appended
+    per field (Vocabulary.grow: old ids keep their meaning, ids stay consecutive), and the file is encoded with the
+    grown vocabulary.  The meta carries the grown feat_map, `oov_rows` under the grown vocabulary and
+    `grown` {field: keys added}; rows stay in file order.  mapx.grow moves a checkpoint trained on the saved
+    vocabulary, or a dataset encoded with it, to the grown id space.  -> (meta, input_size)."""
+    from . import rawtext
+    with open(os.fspath(meta_path)) as f:
+        saved = json.load(f)
+    voc = Vocabulary.from_meta(saved, schema, device=device)
+    labels, columns, _decode, _strings = rawtext.read_columns(path, schema, device=device, chunk_bytes=chunk_bytes)
+    grown, added, _before, _after = voc.grow(columns, n_core)
+    return _encode_and_write(grown, saved, schema, columns, labels, data_dir, dataset_name, split, seed,
+                             {"grown": {n: int(a) for n, a in zip(voc.field_names, added)}})
