@@ -1,7 +1,6 @@
 """DCNv2 building blocks over the gfx950 kernels (host mirror of reference code/layers.py:
 Embeddings :83-102, MLPBlock :173-188, CrossNetV2 :191-201).  autograd.Function = glue only:
 every forward/backward body is a C-ABI call (mapx.ops)."""
-import contextlib
 import copy
 import math
 import os
@@ -137,19 +136,13 @@ class PlanSlot:
             return
         keys, self.keys = self.keys, None
         side = _side_stream(keys.device, self.table.name)
-        forked = ops.stream_wait_event(side, self.ready, self.origin)
-        if after is not None:            # (see start_many: left to itself the graph runtime runs the chain LAST)
-            with torch.cuda.stream(after):
-                ev = ops.record_event()
-            ops.stream_wait_event(side, ev, after)
-        with torch.cuda.stream(side):
+        # (after: see start_many: left to itself the graph runtime runs the chain LAST)
+        with ops.Fork(side, self.origin, event=self.ready, after=after) as fork:
             self.value = ops.SegPlan(keys, self.table.num_rows)
             for observe in plan_observers:
                 observe(self.table, self.value)
-        if forked:
-            keys.record_stream(side)
-            for t in self.value.tensors():
-                t.record_stream(self.origin)
+        fork.reads(keys)
+        fork.produces(*self.value.tensors())
 
     MAX_PER_CHAIN = 2       # key lists one chain of launches sorts (csrc/radixsort.h kMaxSortProbs)
 
@@ -172,25 +165,21 @@ class PlanSlot:
         # `implied`: slots whose keys are known to be final once the OTHER slots' events have fired (the
         # caller's stream order guarantees it): the side stream then forks from one point of the step
         # instead of joining two streams (measured: no difference, 0.756 vs 0.757 ms in bf16 mode)
-        forked = [(s not in implied) and ops.stream_wait_event(side, s.ready, s.origin) for s in slots]
-        if after is not None:
-            # also behind what `after` (a stream) has enqueued so far: the graph runtime runs a side chain
-            # AHEAD of later-captured work of the queue it lands on, so the caller names the kernels the
-            # chain must not delay (bf16 mode: the deep tower's GEMMs waited 140 us behind the sort)
-            with torch.cuda.stream(after):
-                ev = ops.record_event()
-            ops.stream_wait_event(side, ev, after)
-        with torch.cuda.stream(side):
+        # `after`, on the last fork: also behind what that stream has enqueued so far: the graph runtime runs a
+        # side chain AHEAD of later-captured work of the queue it lands on, so the caller names the kernels the
+        # chain must not delay (bf16 mode: the deep tower's GEMMs waited 140 us behind the sort)
+        waited = [(s, k) for s, k in zip(slots, keys) if s not in implied]
+        forks = [ops.Fork(side, s.origin, event=s.ready, after=after if s is waited[-1][0] else None)
+                 for s, _ in waited]
+        with forks[-1]:
             plans = ops.SegPlan.build_many(keys, [s.table.num_rows for s in slots])
             for s, plan in zip(slots, plans):
                 s.value, s.keys = plan, None
                 for observe in plan_observers:
                     observe(s.table, plan)
-        for s, k, f in zip(slots, keys, forked):
-            if f:
-                k.record_stream(side)
-                for t in s.value.tensors():
-                    t.record_stream(s.origin)
+        for fork, (s, k) in zip(forks, waited):
+            fork.reads(k)
+            fork.produces(*s.value.tensors())
 
     def get(self):
         """The plan, usable on the current stream."""
@@ -582,14 +571,12 @@ def join_bwd_input(dz, w, final, link):
     # chain: the deep tower's product, the longer backward chain's first link, is enqueued first)
     ops.dbg_sleep("join_deep")
     dzr = ops.linear_bwd_input(dz, ops.cols(w, D, None), relu_of=final[:, D:], colsum_to=link.relu.sb)
-    forked = ops.stream_wait(side, main) if dz.is_cuda else False
-    with (torch.cuda.stream(side) if forked else contextlib.nullcontext()):
+    with ops.Fork(side, main) as fork:
         ops.dbg_sleep("join_cross")
         g, t, dx0, part = ops.gemm_bwd_fused(dz, ops.cols(w, 0, D), D, x0=link.x0, u=link.u, plus_v=link.plus_v)
         ops.defer_part_rows(link.sb_cross, part, 0, D)
-    if forked:
-        dz.record_stream(side)
-        ops.pending_joins.append((main, side))
+    fork.reads(dz)
+    fork.leave_open()
     link.relu.premasked = True
     link.t, link.dx0, link.g, link.dz = t, dx0, g, dzr
     return torch.empty(1, 1, dtype=final.dtype, device=final.device).expand(final.shape[0], Nn)    # never read

@@ -110,39 +110,34 @@ class BaseModel(nn.Module):
     def _sample_early(self, labels, masked_index, noise_samples):
         """MFP over a single-stream trunk (DNN, DeepFM, xDeepFM, AutoInt, trans, FGCNN): the NCE head's sampling and the lazy
         catch-up of the sampled rows need only the targets — they run on the tower stream beside the trunk instead of
-        between the trunk and the loss (as DCNV2.forward does by hand).  -> (ids | None, join state)."""
+        between the trunk and the loss (as DCNV2.forward does by hand).  -> (ids | None, the open fork | None)."""
         if not (self.config.pretrain and self.config.pt_type == "MFP" and masked_index is not None
                 and labels is not None and labels.is_cuda):
             return None, None
-        main = torch.cuda.current_stream()
-        tower = ops.aux_stream("tower", labels.device)
-        forked = ops.stream_wait(tower, main)
-        with torch.cuda.stream(tower):
+        with ops.Fork(ops.aux_stream("tower", labels.device), torch.cuda.current_stream()) as fork:
             idx = self.mfp_criterion.sample_ids(labels, noise_samples)
-        return idx, (main, tower, forked, labels)
+        fork.reads(labels)
+        return idx, fork
 
-    def _plans_and_join(self, idx, state):
+    def _plans_and_join(self, idx, fork):
         """Behind the trunk: the tables' segment plans from ONE chain of launches per two tables (behind what the main
         stream holds), then the main stream takes the sampled ids over.  The trunk's tables: `embed`, and FGCNN's second
         embedding `fg_embed`."""
         trunk = [self.embed.table]
         if getattr(self, "fg_embed", None) is not None:
             trunk.append(self.fg_embed.table)
-        if state is None:
+        if fork is None:
             for tb in trunk:
                 tb.start_plan()
             return
-        main, tower, forked, labels = state
         from .layers import PlanSlot
         if self.mfp_criterion.table.plan is not None and all(tb.plan is not None for tb in trunk):
-            PlanSlot.start_many([tb.plan for tb in trunk] + [self.mfp_criterion.table.plan], after=main)
+            PlanSlot.start_many([tb.plan for tb in trunk] + [self.mfp_criterion.table.plan], after=fork.origin)
         else:
             for tb in trunk:
                 tb.start_plan()
-        ops.stream_wait(main, tower)
-        if forked:
-            labels.record_stream(tower)
-            idx.record_stream(main)
+        fork.join()
+        fork.produces(idx)
 
     def get_outputs(self, inputs, labels=None, masked_index=None, is_pretrain=None, noise_samples=None,
                     groups=None, nce_idx=None, join=None):
@@ -265,7 +260,7 @@ class DCNV2(BaseModel):
             # the other queues (measured: the trunk's first GEMM started 150 us late).
             main = torch.cuda.current_stream()
             tower = ops.aux_stream("tower", feat_embed.device)
-            forked = ops.stream_wait(tower, main)
+            fork = ops.Fork(tower, main)
 
             # both towers write their last layer straight into the concatenated buffer
             D, H = feat_embed.shape[1], self.config.hidden_size
@@ -289,7 +284,7 @@ class DCNV2(BaseModel):
                 # the grouped encoder's slot layout (one 15-us launch) ahead of the deep tower, which by now
                 # has ~45 us of slack against the cross tower's stream (round 1 had it the other way round)
                 groups = ops.EncGroups(masked_index, self.config.num_fields)
-            with torch.cuda.stream(tower):
+            with fork:
                 if self._grouped_head(masked_index) and groups is None:
                     # the cross tower has ~70 us of slack against the deep one: the slot layout of
                     # the grouped encoder (one single-workgroup launch) rides on its stream
@@ -318,17 +313,14 @@ class DCNV2(BaseModel):
                 # (RFD / finetune steps: one table, one chain)
                 f32_trunk = self.embed.compute_dtype == torch.float32
                 self.embed.table.start_plan(after=main if plan_after_main(self.config.pretrain, f32_trunk, D) else tower)
-            ops.stream_wait(main, tower)
-            if forked:
-                feat_embed.record_stream(tower)
-                final_buf.record_stream(tower)
-                if groups is not None:
-                    masked_index.record_stream(tower)
-                    for t in groups.tensors():
-                        t.record_stream(main)
-                if nce_idx is not None:
-                    labels.record_stream(tower)
-                    nce_idx.record_stream(main)
+            fork.join()
+            fork.reads(feat_embed, final_buf)
+            if groups is not None:
+                fork.reads(masked_index)
+                fork.produces(*groups.tensors())
+            if nce_idx is not None:
+                fork.reads(labels)
+                fork.produces(nce_idx)
             final_output = ops.carry(_JoinColumns.apply(cross_output, dnn_output, final_buf, join), final_buf) if direct \
                 else torch.cat([cross_output, dnn_output], dim=-1)
             if self._mfp_head(masked_index):

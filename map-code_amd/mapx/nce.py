@@ -59,6 +59,18 @@ class AliasMultinomial(nn.Module):
         return ops.alias_draw(self.packed(), targets, K, seed, offset, offset_dev)
 
 
+def _table_grad(crit, plan, dlogit, h, K, P, gl, late=False):
+    """The table's row-sparse gradient, on the current stream -> (ge, gb), also left in crit.table.sparse_grad.
+    `late`: run as a late task, on whatever stream drains the queue: what it reads is kept for that stream."""
+    ge, gb = ops.nce_table_grad(plan, dlogit, h, K, P, gscale=gl)
+    crit.table.sparse_grad = (plan, ge, gb)
+    if late:
+        cur = torch.cuda.current_stream()
+        for t in (dlogit, h, gl) + tuple(plan.tensors()):
+            t.record_stream(cur)
+    return ge, gb
+
+
 class _NceLoss(Function):
     @staticmethod
     def forward(ctx, enc, emb_w, bias_w, logq, masked_index, idx, crit, F, P, want_logits):
@@ -96,18 +108,10 @@ class _NceLoss(Function):
             holder = {}
             ops.add_main_task(lambda: holder.__setitem__("plan", slot.get()))
 
-            def table_work():
-                plan = holder.get("plan") or slot.get()
-                ge, gb = ops.nce_table_grad(plan, dlogit, h, K, P, gscale=gl)
-                crit.table.sparse_grad = (plan, ge, gb)
-                cur = torch.cuda.current_stream()
-                for t in (dlogit, h, gl) + tuple(plan.tensors()):
-                    t.record_stream(cur)
-            ops.add_late_task(table_work)
+            ops.add_late_task(lambda: _table_grad(crit, holder.get("plan") or slot.get(), dlogit, h, K, P, gl,
+                                                  late=True))
             return denc, None, None, None, None, None, None, None, None, None
-        plan = ctx.plan.get()
-        ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
-        ctx.crit.table.sparse_grad = (plan, ge, gb)
+        _table_grad(ctx.crit, ctx.plan.get(), dlogit, h, ctx.K, ctx.P, gl)
         return denc, None, None, None, None, None, None, None, None, None
 
 
@@ -187,15 +191,12 @@ class _EncNceLoss(Function):
             # for the sort chain: 20-29 us of both queues on round 4's timelines).  The plan stream waits for this point
             # of the main stream (dlogit, h and the loss scale are final) and is joined by optimizer.step().
             from .layers import _side_stream
-            main, pst = torch.cuda.current_stream(), _side_stream(final.device)
-            plan = ctx.plan.value
-            if ops.stream_wait(pst, main):
-                with torch.cuda.stream(pst):
-                    ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
-                    ctx.crit.table.sparse_grad = (plan, ge, gb)
-                for t in (ge, gb, dlogit, h, gl):
-                    t.record_stream(pst)
-                ops.pending_joins.append((main, pst))
+            fork = ops.Fork(_side_stream(final.device), torch.cuda.current_stream())
+            if fork.forked:
+                with fork:
+                    ge, gb = _table_grad(ctx.crit, ctx.plan.value, dlogit, h, ctx.K, ctx.P, gl)
+                fork.reads(ge, gb, dlogit, h, gl)      # (the plan's tensors live on this stream)
+                fork.leave_open()
                 table_done = True
         elif aside and joined:
             # with one product per tower the cross tower's chain starts at once on the tower stream; the table's
@@ -204,14 +205,7 @@ class _EncNceLoss(Function):
             crit, K, P = ctx.crit, ctx.K, ctx.P
             plan = ctx.plan.get()        # (joined here, on the main stream: a tower <- plan join inside a capture
                                          # is the one that crashed hipStreamEndCapture in round 1)
-
-            def table_work():
-                ge, gb = ops.nce_table_grad(plan, dlogit, h, K, P, gscale=gl)
-                crit.table.sparse_grad = (plan, ge, gb)
-                cur = torch.cuda.current_stream()
-                for t in (dlogit, h, gl) + tuple(plan.tensors()):
-                    t.record_stream(cur)
-            ops.add_late_task(table_work)
+            ops.add_late_task(lambda: _table_grad(crit, plan, dlogit, h, K, P, gl, late=True))
             table_done = True
         elif aside:
             # The table's gradient reduction needs nothing of this backward pass but the loss
@@ -220,14 +214,12 @@ class _EncNceLoss(Function):
             # for it on the main stream.  (The encoder's dW / db there as well, or on the plan stream: 0.888 /
             # 0.883 vs 0.873 ms — the cross tower's backward queues behind whatever this stream holds.)
             plan = ctx.plan.get()
-            main, side = torch.cuda.current_stream(), ops.aux_stream("tower", final.device)
-            if ops.stream_wait(side, main):
-                with torch.cuda.stream(side):
-                    ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
-                    ctx.crit.table.sparse_grad = (plan, ge, gb)
-                for t in (ge, gb, dlogit, h, gl) + tuple(plan.tensors()):
-                    t.record_stream(side)
-                ops.pending_joins.append((main, side))
+            fork = ops.Fork(ops.aux_stream("tower", final.device), torch.cuda.current_stream())
+            if fork.forked:
+                with fork:
+                    ge, gb = _table_grad(ctx.crit, plan, dlogit, h, ctx.K, ctx.P, gl)
+                fork.reads(ge, gb, dlogit, h, gl, *plan.tensors())
+                fork.leave_open()
                 table_done = True
         if joined and sw is not None and sb is not None:
             # nothing but the optimizer waits for the encoder's own gradients, and both towers' backward passes
@@ -246,9 +238,7 @@ class _EncNceLoss(Function):
             dw = ops.enc_grouped_dw(dh_slots, final, ctx.groups, out=sw, gscale=gl)
             db = ops.colsum(denc, out=sb, defer=True)      # second stage with the other deferred partial sums
         if not table_done:
-            plan = ctx.plan.get()
-            ge, gb = ops.nce_table_grad(plan, dlogit, h, ctx.K, ctx.P, gscale=gl)
-            ctx.crit.table.sparse_grad = (plan, ge, gb)
+            _table_grad(ctx.crit, ctx.plan.get(), dlogit, h, ctx.K, ctx.P, gl)
         return (dfinal, None if sw is not None else dw, None if sb is not None else db,
                 None, None, None, None, None, None, None, None, None, None, None)
 

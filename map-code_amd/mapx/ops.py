@@ -243,6 +243,52 @@ def stream_wait_event(waiter, event, origin):
     return False
 
 
+class Fork:
+    """Work on the stream `side` beside the stream `origin`: fork, the allocator's record_stream rule and join, once.
+        fork = Fork(side, origin)                # side waits for origin's tail; event=: for that event of origin's
+        with fork: ...                           # side is the current stream
+        fork.reads(...); fork.produces(...)      # tensors the side work reads / leaves for origin
+        fork.join()  or  fork.leave_open()       # origin waits for side now / optimizer.step() joins (join_pending)
+    `forked` is False when no edge was made (side IS origin: serialize_streams, or side is None: no device): the
+    body then runs in place, nothing is recorded and nothing is left to join.  `after`: side also waits for what
+    that stream has enqueued so far."""
+
+    def __init__(self, side, origin, event=None, after=None):
+        self.side, self.origin = side, origin
+        self.forked = side is not None and (stream_wait(side, origin) if event is None
+                                            else stream_wait_event(side, event, origin))
+        if after is not None:
+            with torch.cuda.stream(after):
+                ev = record_event()
+            stream_wait_event(side, ev, after)
+
+    def __enter__(self):
+        self._ctx = torch.cuda.stream(self.side)        # (None: a context that does nothing)
+        self._ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        return self._ctx.__exit__(*exc)
+
+    def reads(self, *tensors):
+        if self.forked:
+            for t in tensors:
+                t.record_stream(self.side)
+
+    def produces(self, *tensors):
+        if self.forked:
+            for t in tensors:
+                t.record_stream(self.origin)
+
+    def join(self):
+        if self.forked:
+            stream_wait(self.origin, self.side)
+
+    def leave_open(self):
+        if self.forked:
+            pending_joins.append((self.origin, self.side))
+
+
 # --------------------------------------------------------------------------- deferred sums
 # Split-K slabs (weight gradients) and row-chunk partials (bias gradients) of a backward pass
 # are summed by ONE kernel launch right before their consumer (optimizer / gradient exchange)

@@ -304,15 +304,12 @@ class MapxOptimizer:
             # The dense half (partial sums + dense AdamW, HBM-bound, ~30 us) beside the tables' half (the
             # embedding gradient's reduction + row updates, ~30 us) instead of behind it: it forks from the
             # point where the dense gradients were final, on the tower stream, which is idle by then.
-            side = ops.aux_stream("tower", self.done.device)
-            forked = ops.stream_wait_event(side, ev, main)
-            with torch.cuda.stream(side):
+            with ops.Fork(ops.aux_stream("tower", self.done.device), main, event=ev) as fork:
                 ops.flush_deferred()
                 self._dense_update()
             for t in self.tables:
                 t.update()
-            if forked:
-                ops.stream_wait(main, side)
+            fork.join()
         else:
             ops.flush_deferred()            # split-K slabs / colsum partials of this backward pass
             if self.max_grad_norm > 0:

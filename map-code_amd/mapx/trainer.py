@@ -397,14 +397,12 @@ class GraphedExchangeTail:
                 # dense AdamW as a third branch was measured slower)
                 main = torch.cuda.current_stream()
                 order = sorted(range(len(tables)), key=lambda i: -sizes[i])
-                side = [ops.aux_stream(f"merge{j}", main.device) for j in range(len(order) - 1)]
-                for st in side:
-                    ops.stream_wait(st, main)
+                forks = [ops.Fork(ops.aux_stream(f"merge{j}", main.device), main) for j in range(len(order) - 1)]
                 for j, i in enumerate(order):
-                    with torch.cuda.stream(main if (j == 0 or not side) else side[j - 1]):
+                    with (contextlib.nullcontext() if j == 0 else forks[j - 1]):
                         parallel.merge_table(tables[i], *self.gathered[i])
-                for st in side:
-                    ops.stream_wait(main, st)
+                for fork in forks:
+                    fork.join()
                 opt.step()
         finally:
             opt.steps_done = sd                         # the capture ran the bookkeeping but no kernel
