@@ -3,19 +3,15 @@ csrc/attn.hip) at model level: graph replay == eager over Trainer steps, bit-exa
 the rate, and run.py at the flag default (0.1) from pretraining to finetuning."""
 import math
 import os
-import re
-import subprocess
-import sys
 
-import numpy as np
 import pytest
 import torch
 
+import model_harness as H
 from util import make_config
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = dict(F=23, V=300, E=16, H=16, NL=0, NC=0, P=32, K=25)
 B = 64
 
@@ -28,34 +24,11 @@ def _config(mode, cnt=None, rate=0.1):
     return c
 
 
-def _trainer(mode, ids, labels, cnt, out_dir, seed=5, rate=0.1):
-    from mapx.arguments import TrainingArguments
-    from mapx.dataset import OurDataset
+def _start(mode, data, out_dir, seed=5):
     from mapx.models import BaseModel
-    from mapx.trainer import Trainer
     torch.manual_seed(seed)
-    config = _config(mode, cnt, rate)
-    model = BaseModel.from_config(config)
-    targs = TrainingArguments(output_dir=out_dir, per_gpu_train_batch_size=B, per_gpu_eval_batch_size=B,
-                              learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2, num_train_epochs=1,
-                              pretrain=mode != "CTR", pt_type="MFP", sampling_method="randint", mask_ratio=0.3,
-                              logging_steps=7, seed=11, patience=100)
-    targs._device = torch.device(DEV)
-    os.makedirs(out_dir, exist_ok=True)
-    return Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:B], labels[:B])), model
-
-
-def _data(steps, seed):
-    from mapx.dataset import synth_table
-    ids, labels, _, _ = synth_table(B * steps, CFG["F"], CFG["V"], seed=seed)
-    return ids, labels, np.bincount(ids.reshape(-1), minlength=CFG["V"]).astype(np.float32)
-
-
-def _start(mode, data, out_dir, **kw):
-    tr, model = _trainer(mode, *data, out_dir, **kw)
-    train = tr._begin("test")
-    model.train()
-    return tr, model, list(train.batches(B, True, tr._generator(), (0, 1)))
+    config = _config(mode, data[2])
+    return H.make_trainer(config, BaseModel.from_config(config), mode, data, out_dir, B, 1, B, begin=True)
 
 
 @pytest.mark.parametrize("mode", ["MFP", "CTR"])
@@ -63,9 +36,9 @@ def test_graph_replay_equals_eager_bitwise(mode, tmp_path):
     """8 steps: 3 eager, then the captured step.  The captured step draws the masks of the eager one (the sites read
     the optimizer's device-side step counter), and the masks advance: every step has another loss."""
     from mapx.layers import MhaDropout
-    data = _data(8, seed=3)
-    runs = []
-    for use_graph in (True, False):
+    data = H.synth_data(B * 8, CFG["F"], CFG["V"], seed=3)
+
+    def run(use_graph):
         tr, model, batches = _start(mode, data, str(tmp_path / str(use_graph)))
         tr.use_graph = use_graph
         sites = [m for m in model.modules() if isinstance(m, MhaDropout)]
@@ -73,42 +46,24 @@ def test_graph_replay_equals_eager_bitwise(mode, tmp_path):
         assert len({m.site for m in sites}) == 4 and all(m.seed == 11 for m in sites)
         losses = [float(tr.run_step(mode.lower(), X, Y)[0]) for X, Y in batches]
         assert len(losses) == 8 and tr.global_step == 8
-        assert bool([g for g in tr._graphs.values() if not isinstance(g, int)]) == use_graph
+        assert bool(H.captured(tr)) == use_graph
         tr.optimizer.flush()
-        runs.append((losses, {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}))
-    (la, sa), (lb, sb) = runs
-    assert la == lb, (la, lb)
+        return losses, H.model_state(model)
+
+    (la, _), _ = H.graph_vs_eager(run)
     assert len(set(la)) == len(la) and all(math.isfinite(x) for x in la), la
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
 
 
 def test_resume_state_continues_bit_exactly(tmp_path):
     """6 steps == 3 steps + save_training_state + fresh trainer + load_training_state + 3 steps."""
-    data = _data(6, seed=4)
+    data = H.synth_data(B * 6, CFG["F"], CFG["V"], seed=4)
 
     def make():
         tr, _, batches = _start("MFP", data, str(tmp_path), seed=9)
         tr.use_graph = False
         return tr, batches
 
-    tr_a, batches = make()
-    for X, Y in batches:
-        tr_a.run_step("mfp", X, Y)
-    tr_a.optimizer.flush()
-    ref = {k: v.detach().cpu().clone() for k, v in tr_a.model.state_dict().items()}
-    tr_b, batches_b = make()
-    for X, Y in batches_b[:3]:
-        tr_b.run_step("mfp", X, Y)
-    tr_b.save_training_state(str(tmp_path / "state.pt"))
-    tr_c, batches_c = make()
-    tr_c.load_training_state(str(tmp_path / "state.pt"))
-    assert tr_c.global_step == 3 and tr_c.optimizer.steps_done == 3
-    for X, Y in batches_c[3:]:
-        tr_c.run_step("mfp", X, Y)
-    tr_c.optimizer.flush()
-    for k, v in tr_c.model.state_dict().items():
-        assert torch.equal(v.detach().cpu(), ref[k]), k
+    H.resume_roundtrip(make, 6, 3, str(tmp_path / "state.pt"))
 
 
 def test_evaluation_does_not_depend_on_the_rate():
@@ -117,7 +72,7 @@ def test_evaluation_does_not_depend_on_the_rate():
     m1 = BaseModel.from_config(_config("CTR", rate=0.1)).to(DEV)
     m0 = BaseModel.from_config(_config("CTR", rate=0.0)).to(DEV)
     m0.load_state_dict(m1.state_dict())
-    ids = torch.from_numpy(_data(1, seed=8)[0]).to(DEV)
+    ids = torch.from_numpy(H.synth_data(B, CFG["F"], CFG["V"], seed=8)[0]).to(DEV)
     m0.eval()
     m1.eval()
     with torch.no_grad():
@@ -125,38 +80,17 @@ def test_evaluation_does_not_depend_on_the_rate():
     assert torch.equal(l0, l1) and bool(torch.isfinite(l1).all())
 
 
-def _run_py(args, cwd):
-    cmd = [sys.executable, os.path.join(ROOT, "map-code_amd", "run.py")] + args
-    return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=600)
-
-
 def test_run_py_autoint_at_the_default_rate_pretrain_then_finetune(tmp_path):
     """--attn_probs_dropout_rate is not passed: the reference's default 0.1 applies."""
-    from mapx.dataset import write_synth_dataset
-    data = write_synth_dataset(str(tmp_path / "data" / "avazu"), num_rows=4000, num_fields=23, vocab=2000)
-    common = ["--dataset_name=avazu", f"--data_dir={data}", "--per_gpu_train_batch_size=512",
-              "--per_gpu_eval_batch_size=512", "--learning_rate=1e-3", "--model_name=autoint", "--embed_size=16",
-              "--num_attn_layers=2", "--num_attn_heads=2", "--attn_size=8", "--res_conn=True", "--logging_steps=3"]
-    assert not any("attn_probs_dropout_rate" in a for a in common)
-    out = str(tmp_path / "out" / "mfp")
-    r = _run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=1", "--lr_sched=cosine",
-                 "--weight_decay=5e-2", "--pt_type=MFP", "--sampling_method=randint", "--mask_ratio=0.3",
-                 "--pt_neg_num=25", "--proj_size=32"] + common, str(tmp_path))
-    assert r.returncode == 0, r.stderr[-3000:]
-    ckpt = os.path.join(out, f"{(3200 + 511) // 512}.model")
-    sd = torch.load(ckpt)
+    common = ["--model_name=autoint", "--embed_size=16", "--num_attn_layers=2", "--num_attn_heads=2", "--attn_size=8",
+              "--res_conn=True", "--logging_steps=3"]
+    pretrain, finetune = ["--pt_type=MFP", "--pt_neg_num=25"], ["--use_lr=True"]
+    assert not any("attn_probs_dropout_rate" in a for a in common + pretrain + finetune)
+    sd, log = H.pretrain_then_finetune(tmp_path, common, pretrain, finetune)
     attn = sorted(k for k in sd if k.startswith("self_attention."))
     assert len(attn) == 2 * 3 and "self_attention.1.W_v.weight" in attn          # (width 16 = 2 x 8: no W_res)
-    log = open(os.path.join(out, "results.log")).read()
-    assert "attn_probs_dropout_rate = 0.1" in log
-    fo = str(tmp_path / "out" / "finetune")
-    r2 = _run_py(["--finetune", f"--pretrained_model_path={ckpt}", f"--output_dir={fo}", "--num_train_epochs=1",
-                  "--lr_sched=const", "--weight_decay=1e-1", "--use_lr=True"] + common, str(tmp_path))
-    assert r2.returncode == 0, r2.stderr[-3000:]
-    assert [f for f in os.listdir(fo) if f.endswith(".model")]
-    log = open(os.path.join(fo, "results.log")).read()
+    assert "attn_probs_dropout_rate = 0.1" in open(tmp_path / "out" / "pretrain" / "results.log").read()
+    assert [f for f in os.listdir(tmp_path / "out" / "finetune") if f.endswith(".model")]
     for k in attn:
         assert f"Load tensor: {k}," in log, k
-    for key in ("eval_auc", "eval_loss"):          # (eval_loss: the log-loss)
-        vals = [float(v) for v in re.findall(rf"{key}\W+([-+0-9.eE]+|nan|inf)", log)]
-        assert vals and all(math.isfinite(v) for v in vals), (key, vals)
+    H.finite_metrics(log)          # (eval_loss: the log-loss)

@@ -14,110 +14,43 @@ per consumer (MLP and FM term; attention and tower) before autograd adds the pie
 sum once.  Each case prints measured error, e_emul and bound of its worst tensor."""
 import math
 import os
-import re
-import subprocess
-import sys
 
-import numpy as np
 import pytest
 import torch
 
 import bf16_backbones_ref as BR
+import model_harness as H
 import paramgen as pg
 from test_bf16_backbones_host import CASE, CASES, IDS, family, reference
-from util import build_model, check_pattern, hook_relu_pattern, load_case, make_config, t
+from util import build_model, hook_relu_pattern, load_case, make_config
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _hooks(model):
-    """-> (ReLU masks by layer, dtypes of the trunk tensors, the heads' logits), all filled by forward hooks."""
-    from mapx.layers import MLPBlock, MultiHeadSelfAttention
-    masks, dtypes, logits = hook_relu_pattern(model), {}, {}
+def _masks(model):
+    """The ReLU masks by layer; the attention layers' outputs (ReLU inside the kernel) are part of the pattern."""
+    from mapx.layers import MultiHeadSelfAttention
+    masks = hook_relu_pattern(model)
     for name, mod in model.named_modules():
         if isinstance(mod, MultiHeadSelfAttention):
             def attn_hook(m, i, o, name=name):          # (a hook that returns a value would replace the output)
                 masks[name] = (o.detach() > 0).cpu()
-                dtypes[name] = o.dtype
             mod.register_forward_hook(attn_hook)
-        elif isinstance(mod, MLPBlock):
-            mod.register_forward_hook(lambda m, i, o, name=name: dtypes.__setitem__(name, o.dtype))
-    if hasattr(model, "mfp_criterion"):
-        model.mfp_criterion.return_logits = True
-        model.mfp_criterion.register_forward_hook(lambda m, i, o: logits.__setitem__("out", o[1].detach()))
-    if hasattr(model, "pred_rfd"):
-        model.pred_rfd["2"].register_forward_hook(lambda m, i, o: logits.__setitem__("out", o.detach()))
-    return masks, dtypes, logits
+    return masks
 
 
-def _all_grads(model):
-    tab = model.table_parameter_ids()
-    names = {id(p): n for n, p in model.named_parameters()}
-    out = {n: p.grad for n, p in model.named_parameters() if id(p) not in tab}
-    for table in model.row_tables():
-        g0, g1 = table.dense_grad()
-        out[names[id(table.p0)]] = g0
-        if g1 is not None:
-            out[names[id(table.p1)]] = g1
-    return out
-
-
-def _forward(model, mode, batch):
-    ids = batch["ids"].to(DEV)
-    if mode == "MFP":
-        return model(input_ids=ids, labels=batch["labels"].to(DEV), masked_index=batch["masked_index"].to(DEV),
-                     noise_samples=batch["noise"].to(DEV))
-    if mode == "RFD":
-        return model(input_ids=ids, labels=batch["labels"].to(DEV))
-    return model(input_ids=ids, labels=batch["y"].to(DEV))
+def _is_trunk(name, mod):
+    from mapx.layers import MLPBlock, MultiHeadSelfAttention
+    return isinstance(mod, (MultiHeadSelfAttention, MLPBlock))
 
 
 def _compare(what, model, fam, mode, params, batch, num_hidden, ai, exact, fixture=None):
-    """Runs the bf16 step and the checks of the module docstring.  exact = (loss, logits, preacts) of the float64
-    restatement on its own pattern; fixture = (loss, logits | None) of the reference, when there is one."""
-    masks, dtypes, logits = _hooks(model)
-    model.train()
-    out = _forward(model, mode, batch)
-    loss = out[0]
-    got_logits = out[1] if mode == "CTR" else logits["out"]
-    # what is bf16 and what is not
-    assert dtypes and all(d == BF for d in dtypes.values()), dtypes
-    assert model.embed.compute_dtype == BF
-    assert loss.dtype == torch.float32 and got_logits.dtype == torch.float32
-    loss.backward()
-    grads = _all_grads(model)
-    assert all(g is not None and g.dtype == torch.float32 for g in grads.values()), \
-        {n: None if g is None else g.dtype for n, g in grads.items()}
-    # loss and logits
-    loss_x, logits_x, pre = exact
-    loss_f, logits_f = fixture if fixture is not None else (loss_x, None)
-    logits_f = logits_x if logits_f is None else logits_f
-    e_loss = abs(float(loss.detach()) - loss_f) / abs(loss_f)
-    e_logits = BR.rel(got_logits.detach().cpu().numpy(), logits_f)
-    print(f"[{what}] loss {float(loss.detach()):.6f} vs {loss_f:.6f} ({e_loss:.2e}); logits {e_logits:.2e} of scale")
-    assert e_loss <= 1e-2 and e_logits <= 1e-2
-    # the step's own ReLU pattern, then every gradient on that pattern
-    flips = check_pattern(masks, pre, what)
-    _, _, ref = BR.step(fam, mode, params, batch, num_hidden=num_hidden, ai=ai, relu_masks=masks)
-    _, _, emu = BR.step(fam, mode, params, batch, num_hidden=num_hidden, ai=ai, relu_masks=masks, emulate=True)
-    assert set(ref) == set(grads), (sorted(ref), sorted(grads))
-    rows, fails = [], []
-    for n, g in grads.items():
-        e, e_emul = BR.rel(g.cpu().numpy(), ref[n]), BR.rel(emu[n], ref[n])
-        bound = max(1e-2, 2 * e_emul)
-        rows.append((e / bound, n, e, e_emul, bound))
-        if not e <= bound:
-            fails.append(f"{n}: {e:.3e} of scale > {bound:.3e} (e_emul {e_emul:.3e})")
-    rows.sort(reverse=True)
-    worst_e = max(r[2] for r in rows)
-    worst_emul = max(r[3] for r in rows)
-    print(f"[{what}] {flips} of {sum(v.numel() for v in pre.values())} ReLU units on the other side of the kink; "
-          f"worst gradient error {worst_e:.2e} of scale, worst e_emul {worst_emul:.2e}; closest to its bound: "
-          f"{rows[0][1]} measured {rows[0][2]:.2e} e_emul {rows[0][3]:.2e} bound {rows[0][4]:.2e}")
-    assert not fails, fails
+    """The checks of the module docstring (model_harness.compare_bf16_step) against bf16_backbones_ref.step."""
+    def restate(relu_masks, emulate):
+        return BR.step(fam, mode, params, batch, num_hidden=num_hidden, ai=ai, relu_masks=relu_masks, emulate=emulate)[2]
+    H.compare_bf16_step(what, model, mode, batch, _masks(model), restate, H.rel_err, exact, fixture, is_trunk=_is_trunk)
 
 
 @pytest.mark.parametrize("backbone,mode", CASES, ids=IDS)
@@ -205,36 +138,16 @@ def _config(backbone, mode, cnt=None, rate=0.0, compute_dtype="bf16"):
     return c
 
 
-def _data(steps, seed):
-    from mapx.dataset import synth_table
-    ids, labels, _, _ = synth_table(B * steps, CFG["F"], CFG["V"], seed=seed)
-    return ids, labels, np.bincount(ids.reshape(-1), minlength=CFG["V"]).astype(np.float32)
-
-
 def _start(backbone, mode, data, out_dir, rate=0.0, seed=5):
-    from mapx.arguments import TrainingArguments
-    from mapx.dataset import OurDataset
     from mapx.models import BaseModel
-    from mapx.trainer import Trainer
-    ids, labels, cnt = data
     torch.manual_seed(seed)
-    config = _config(backbone, mode, cnt, rate)
-    model = BaseModel.from_config(config)
-    targs = TrainingArguments(output_dir=out_dir, per_gpu_train_batch_size=B, per_gpu_eval_batch_size=B,
-                              learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2, num_train_epochs=1,
-                              pretrain=mode != "CTR", pt_type="MFP", sampling_method="randint", mask_ratio=0.3,
-                              logging_steps=7, seed=11, patience=100)
-    targs._device = torch.device(DEV)
-    os.makedirs(out_dir, exist_ok=True)
-    tr = Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:B], labels[:B]))
-    train = tr._begin("test")
-    model.train()
-    return tr, model, list(train.batches(B, True, tr._generator(), (0, 1)))
+    config = _config(backbone, mode, data[2], rate)
+    return H.make_trainer(config, BaseModel.from_config(config), mode, data, out_dir, B, 1, B, begin=True)
 
 
 def test_bf16_autoint_dropout_eval_is_the_rate_zero_model_and_replays_draw_new_masks(tmp_path):
     from mapx.models import BaseModel
-    data = _data(4, seed=8)
+    data = H.synth_data(B * 4, CFG["F"], CFG["V"], seed=8)
     torch.manual_seed(2)
     m1 = BaseModel.from_config(_config("AutoInt", "MFP", data[2], rate=0.1)).to(DEV)
     m0 = BaseModel.from_config(_config("AutoInt", "MFP", data[2], rate=0.0)).to(DEV)
@@ -250,7 +163,7 @@ def test_bf16_autoint_dropout_eval_is_the_rate_zero_model_and_replays_draw_new_m
     tr.use_graph = True
     X, Y = batches[0]
     losses = [float(tr.run_step("mfp", X, Y)[0]) for _ in range(tr.GRAPH_AFTER + 3)]      # eager, capture, two replays
-    assert [g for g in tr._graphs.values() if not isinstance(g, int)], "no step was captured"
+    assert H.captured(tr), "no step was captured"
     assert all(math.isfinite(x) for x in losses) and len(set(losses[-2:])) == 2, losses
 
 
@@ -261,15 +174,15 @@ def test_bf16_graph_replay_equals_eager_bitwise_and_the_checkpoint_is_fp32(backb
     holds fp32 tensors only under the keys of the fp32 model (the reference's manifest) and loads into one; every
     dense weight's bf16 shadow is the rounded master weight."""
     from mapx.models import BaseModel
-    data = _data(6, seed=3)
-    runs = []
-    for use_graph in (True, False):
+    data = H.synth_data(B * 6, CFG["F"], CFG["V"], seed=3)
+
+    def run(use_graph):
         tr, model, batches = _start(backbone, mode, data, str(tmp_path / str(use_graph)))
         tr.use_graph = use_graph
         assert tr.optimizer.bf16
         losses = [float(tr.run_step(mode.lower(), X, Y)[0]) for X, Y in batches]
         assert len(losses) == 6 and all(math.isfinite(x) for x in losses)
-        assert bool([g for g in tr._graphs.values() if not isinstance(g, int)]) == use_graph
+        assert bool(H.captured(tr)) == use_graph
         tr.optimizer.flush()
         for p in tr.optimizer.dense_params:
             if p.dim() == 2:
@@ -278,50 +191,22 @@ def test_bf16_graph_replay_equals_eager_bitwise_and_the_checkpoint_is_fp32(backb
             assert all(getattr(m.weight, "_mapx_bf16", None) is not None
                        for layer in model.self_attention for m in (layer.W_q, layer.W_k, layer.W_v))
         tr.save_model(str(tmp_path / str(use_graph)))
-        runs.append((losses, {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}))
-    (la, sa), (lb, sb) = runs
-    assert la == lb, (la, lb)
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
+        return losses, H.model_state(model)
+
+    H.graph_vs_eager(run)
     ck = torch.load(os.path.join(str(tmp_path / "True"), "6.model"))
-    fp32_model = BaseModel.from_config(_config(backbone, mode, data[2], compute_dtype="fp32"))
-    assert set(ck) == set(fp32_model.state_dict())
-    assert all(v.dtype != BF and (not v.dtype.is_floating_point or v.dtype == torch.float32) for v in ck.values())
-    fp32_model.load_state_dict(ck)
-
-
-def _run_py(args, cwd):
-    cmd = [sys.executable, os.path.join(ROOT, "map-code_amd", "run.py")] + args
-    return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=600)
+    H.assert_checkpoint_is_fp32(ck, BaseModel.from_config(_config(backbone, mode, data[2], compute_dtype="fp32")))
 
 
 def test_run_py_autoint_bf16_pretrain_then_finetune(tmp_path):
     """--model_name=autoint --compute_dtype bf16 at the reference's default attention dropout (0.1, not passed)."""
-    from mapx.dataset import write_synth_dataset
-    data = write_synth_dataset(str(tmp_path / "data" / "avazu"), num_rows=4000, num_fields=23, vocab=2000)
-    common = ["--dataset_name=avazu", f"--data_dir={data}", "--per_gpu_train_batch_size=512",
-              "--per_gpu_eval_batch_size=512", "--learning_rate=1e-3", "--model_name=autoint", "--embed_size=16",
-              "--num_attn_layers=2", "--num_attn_heads=2", "--attn_size=8", "--res_conn=True", "--logging_steps=3",
-              "--compute_dtype", "bf16"]
-    out = str(tmp_path / "out" / "mfp")
-    r = _run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=1", "--lr_sched=cosine",
-                 "--weight_decay=5e-2", "--pt_type=MFP", "--sampling_method=randint", "--mask_ratio=0.3",
-                 "--pt_neg_num=25", "--proj_size=32"] + common, str(tmp_path))
-    assert r.returncode == 0, r.stderr[-3000:]
-    ckpt = os.path.join(out, f"{(3200 + 511) // 512}.model")
-    sd = torch.load(ckpt)
+    common = ["--model_name=autoint", "--embed_size=16", "--num_attn_layers=2", "--num_attn_heads=2", "--attn_size=8",
+              "--res_conn=True", "--logging_steps=3", "--compute_dtype", "bf16"]
+    sd, log = H.pretrain_then_finetune(tmp_path, common, ["--pt_type=MFP", "--pt_neg_num=25"], ["--use_lr=True"])
     assert all(v.dtype != BF for v in sd.values())
     attn = sorted(k for k in sd if k.startswith("self_attention."))
     assert len(attn) == 2 * 3
-    log = open(os.path.join(out, "results.log")).read()
-    assert "attn_probs_dropout_rate = 0.1" in log
-    fo = str(tmp_path / "out" / "finetune")
-    r2 = _run_py(["--finetune", f"--pretrained_model_path={ckpt}", f"--output_dir={fo}", "--num_train_epochs=1",
-                  "--lr_sched=const", "--weight_decay=1e-1", "--use_lr=True"] + common, str(tmp_path))
-    assert r2.returncode == 0, r2.stderr[-3000:]
-    log = open(os.path.join(fo, "results.log")).read()
+    assert "attn_probs_dropout_rate = 0.1" in open(tmp_path / "out" / "pretrain" / "results.log").read()
     for k in attn:
         assert f"Load tensor: {k}," in log, k
-    for key in ("eval_auc", "eval_loss"):
-        vals = [float(v) for v in re.findall(rf"{key}\W+([-+0-9.eE]+|nan|inf)", log)]
-        assert vals and all(math.isfinite(v) for v in vals), (key, vals)
+    H.finite_metrics(log)

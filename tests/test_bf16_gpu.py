@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import model_harness
 import paramgen as pg
 from util import build_model, check_pattern as _check_pattern, hook_relu_pattern as _hook_relu_pattern, load_case, \
     oracle_case_grads as _oracle_grads, t
@@ -408,8 +409,8 @@ def test_bf16_graph_replay_equals_eager_bitwise_and_checkpoint_is_fp32():
     cfg = dict(F=23, V=3000, E=16, H=64, NL=3, NC=3, P=32, K=25)
     ids, labels, _, _ = synth_table(512 * 5 + 100, 23, cfg["V"], seed=3)
     cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
-    out = []
-    for use_graph in (True, False):
+
+    def run(use_graph):
         torch.manual_seed(5)
         config = make_config(cfg, "MFP", cnt, compute_dtype="bf16")
         model = BaseModel.from_config(config)
@@ -422,12 +423,13 @@ def test_bf16_graph_replay_equals_eager_bitwise_and_checkpoint_is_fp32():
         tr = Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:600], labels[:600]))
         tr.use_graph = use_graph
         tr.MFP_pretrain()
-        assert (len(tr._graphs) == 1 and not isinstance(next(iter(tr._graphs.values())), int)) == use_graph
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
+        assert (len(tr._graphs) == 1 and len(model_harness.captured(tr)) == 1) == use_graph
+        state = model_harness.model_state(model)
         ck = torch.load(os.path.join(targs.output_dir, f"{tr.global_step}.model"))
-        assert all(v.dtype != BF for v in ck.values()) and set(ck) == set(out[-1])
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
+        assert all(v.dtype != BF for v in ck.values()) and set(ck) == set(state)
+        return state
+
+    model_harness.graph_vs_eager(run)
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 1000, 1000), (300, 368, 200)])

@@ -3,36 +3,20 @@
 Trainer steps, bit-exact resume, run.py pretraining followed by finetuning, and a short AdamW trajectory."""
 import math
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import fignn_params as fp
+import model_harness as H
 import paramgen as pg
-from util import assert_digest, t
+from util import GOLD, assert_digest, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 FIXTURES = [(m, v) for v in fp.VARIANTS for m in fp.modes_of(v)]
 SMALL = dict(F=23, V=3000, E=16, H=16, NL=2, NC=0, P=32, K=25)
-
-
-def _all_grads(model):
-    tab = model.table_parameter_ids()
-    out = {n: p.grad for n, p in model.named_parameters() if id(p) not in tab}
-    names = {id(p): n for n, p in model.named_parameters()}
-    for table in model.row_tables():
-        g0, g1 = table.dense_grad()
-        out[names[id(table.p0)]] = g0
-        if g1 is not None:
-            out[names[id(table.p1)]] = g1
-    return out
 
 
 @pytest.mark.parametrize("mode,variant", FIXTURES)
@@ -49,15 +33,7 @@ def test_reference_fixture(mode, variant):
     hook = model.fignn.register_forward_hook(lambda m, i, o: seen.update(x=i[0].detach(), h=o.detach()))
     if mode == "MFP":
         ids_in, labels, _ = ops.dynamic_mask_mfp(ids, mi.shape[1], masked_index=mi)
-        crit = model.mfp_criterion
-        crit.return_logits = True
-        for name in ("forward", "forward_with_encoder"):            # whichever form of the head the model takes
-
-            def keep(*a, _orig=getattr(crit, name), **k):
-                out = _orig(*a, **k)
-                seen["logits"] = out[1].detach()
-                return out
-            setattr(crit, name, keep)
+        H.capture_mfp_logits(model.mfp_criterion, seen)
         loss, count, acc = model(input_ids=ids_in, labels=labels, masked_index=mi, noise_samples=t(inp["noise"], DEV))
         assert count == int(z["out/count"]) and int(acc) == int(z["out/total_acc"])
         np.testing.assert_allclose(seen["logits"].cpu().numpy(), z["out/logits"], rtol=1e-5, atol=1e-5)
@@ -80,118 +56,65 @@ def test_reference_fixture(mode, variant):
     g, _, _ = ops.fignn_graph_fwd(seen["x"].contiguous(), model.fignn.W_attn.weight.detach())
     np.testing.assert_allclose(g[:rows].cpu().numpy(), z["mid/graph"], rtol=1e-5, atol=1e-6)
     loss.backward()
-    grads = _all_grads(model)
+    grads = H.all_grads(model)
     assert set(grads) == set(params)
     for n, gr in grads.items():
         assert gr is not None, n
         assert_digest(z, "grad", n, gr.cpu().numpy())
 
 
-def _trainer(mode, ids, labels, cnt, out_dir, epochs=2, seed=5, variant="FiGNN", **over):
-    from mapx.arguments import TrainingArguments
-    from mapx.dataset import OurDataset
+def _trainer(mode, data, out_dir, epochs=2, seed=5, variant="FiGNN", begin=False):
     from mapx.models import build_backbone
-    from mapx.trainer import Trainer
     torch.manual_seed(seed)
-    config = fp.make_config(SMALL, mode, variant, cnt, **over)
-    model = build_backbone(config)
-    targs = TrainingArguments(output_dir=out_dir, per_gpu_train_batch_size=512, per_gpu_eval_batch_size=512,
-                              learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2, num_train_epochs=epochs,
-                              pretrain=mode != "CTR", pt_type="MFP", sampling_method="randint", mask_ratio=0.3,
-                              logging_steps=7, seed=11, patience=100)
-    targs._device = torch.device(DEV)
-    os.makedirs(out_dir, exist_ok=True)
-    return Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:600], labels[:600])), model
-
-
-def _data(rows, seed):
-    from mapx.dataset import synth_table
-    ids, labels, _, _ = synth_table(rows, SMALL["F"], SMALL["V"], seed=seed)
-    return ids, labels, np.bincount(ids.reshape(-1), minlength=SMALL["V"]).astype(np.float32)
+    config = fp.make_config(SMALL, mode, variant, data[2])
+    return H.make_trainer(config, build_backbone(config), mode, data, out_dir, 512, epochs, 600, begin=begin)
 
 
 @pytest.mark.parametrize("mode,variant", [("MFP", "FiGNN"), ("CTR", "FiGNNShare")])
 def test_graph_replay_equals_eager_bitwise(mode, variant, tmp_path):
     """Identical parameters after two epochs with a ragged last batch, bit for bit; and the optimizer keeps no weight
     planes and attaches no magnitude record for the parameters that only the FiGNN kernels read."""
-    ids, labels, cnt = _data(512 * 4 + 100, 3)
-    out = []
-    for use_graph in (True, False):
-        tr, model = _trainer(mode, ids, labels, cnt, str(tmp_path / str(use_graph)), variant=variant)
+    data = H.synth_data(512 * 4 + 100, SMALL["F"], SMALL["V"], 3)
+
+    def run(use_graph):
+        tr, model = _trainer(mode, data, str(tmp_path / str(use_graph)), variant=variant)
         tr.use_graph = use_graph
         tr.MFP_pretrain() if mode == "MFP" else tr.train()
         assert tr.global_step == 2 * 5
-        graphs = [g for g in tr._graphs.values() if not isinstance(g, int)]
-        assert bool(graphs) == use_graph
+        assert bool(H.captured(tr)) == use_graph
         for n, p in model.fignn.named_parameters():
             assert getattr(p, "_planes", None) is None and getattr(p, "_amax", None) is None, n
             assert getattr(p, "_mapx_grad", None) is not None, n
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
-        assert bool(torch.isfinite(out[0][k]).all()), k
+        return H.model_state(model)
+
+    state, _ = H.graph_vs_eager(run)
+    for k in state:
+        assert bool(torch.isfinite(state[k]).all()), k
 
 
 def test_resume_state_continues_bit_exactly(tmp_path):
     """6 steps == 3 steps + save_training_state + fresh trainer + load_training_state + 3 steps."""
-    ids, labels, cnt = _data(512 * 6, 4)
+    data = H.synth_data(512 * 6, SMALL["F"], SMALL["V"], 4)
 
     def make():
-        tr, model = _trainer("MFP", ids, labels, cnt, str(tmp_path), epochs=1, seed=9)
+        tr, _, batches = _trainer("MFP", data, str(tmp_path), epochs=1, seed=9, begin=True)
         tr.use_graph = False
-        train = tr._begin("test")
-        model.train()
-        return tr, list(train.batches(512, True, tr._generator(), (0, 1)))
+        assert sorted(tb.table.name for tb in tr.optimizer.tables) == ["embed.embedding", "mfp_criterion"]
+        return tr, batches
 
-    tr_a, batches = make()
-    assert sorted(tb.table.name for tb in tr_a.optimizer.tables) == ["embed.embedding", "mfp_criterion"]
-    for X, Y in batches:
-        tr_a.run_step("mfp", X, Y)
-    tr_a.optimizer.flush()
-    ref = {k: v.detach().cpu().clone() for k, v in tr_a.model.state_dict().items()}
-    tr_b, batches_b = make()
-    for X, Y in batches_b[:3]:
-        tr_b.run_step("mfp", X, Y)
-    tr_b.save_training_state(str(tmp_path / "state.pt"))
-    tr_c, batches_c = make()
-    tr_c.load_training_state(str(tmp_path / "state.pt"))
-    assert tr_c.global_step == 3 and tr_c.optimizer.steps_done == 3
-    for X, Y in batches_c[3:]:
-        tr_c.run_step("mfp", X, Y)
-    tr_c.optimizer.flush()
-    for k, v in tr_c.model.state_dict().items():
-        assert torch.equal(v.detach().cpu(), ref[k]), k
+    H.resume_roundtrip(make, 6, 3, str(tmp_path / "state.pt"))
 
 
 def test_run_py_fignn_pretrain_then_finetune(tmp_path):
-    from mapx.dataset import write_synth_dataset
-    data = write_synth_dataset(str(tmp_path / "data" / "avazu"), num_rows=4000, num_fields=23, vocab=2000)
-    common = ["--dataset_name=avazu", f"--data_dir={data}", "--per_gpu_train_batch_size=512",
-              "--per_gpu_eval_batch_size=512", "--learning_rate=1e-3", "--model_name=fignn", "--embed_size=16",
-              "--hidden_size=16", "--num_hidden_layers=2", "--res_conn=True", "--logging_steps=3"]
-    out = str(tmp_path / "out" / "mfp")
-    cmd = [sys.executable, os.path.join(ROOT, "map-code_amd", "run.py")]
-    r = subprocess.run(cmd + ["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=1", "--lr_sched=cosine",
-                              "--weight_decay=5e-2", "--pt_type=MFP", "--sampling_method=randint", "--mask_ratio=0.3",
-                              "--pt_neg_num=25", "--proj_size=32"] + common, cwd=str(tmp_path), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    ckpt = os.path.join(out, f"{(3200 + 511) // 512}.model")
-    sd = torch.load(ckpt)
+    common = ["--model_name=fignn", "--embed_size=16", "--hidden_size=16", "--num_hidden_layers=2", "--res_conn=True",
+              "--logging_steps=3"]
+    sd, log = H.pretrain_then_finetune(tmp_path, common, ["--pt_type=MFP", "--pt_neg_num=25"], [])
     trunk = sorted(k for k in sd if k.startswith(("fignn.", "embed.")))
     assert "fignn.gnn.1.W_out" in trunk and "fignn.gru.bias_hh" in trunk and "fignn.W_attn.weight" in trunk
-    fo = str(tmp_path / "out" / "finetune")
-    r2 = subprocess.run(cmd + ["--finetune", f"--pretrained_model_path={ckpt}", f"--output_dir={fo}",
-                               "--num_train_epochs=1", "--lr_sched=const", "--weight_decay=1e-1"] + common,
-                        cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert r2.returncode == 0, r2.stderr[-3000:]
-    log = open(os.path.join(fo, "results.log")).read()
     for k in trunk:
         assert f"Load tensor: {k}," in log, k
     assert "Unmatched tensor in the target model: feat_encoder.weight" in log
-    for key in ("eval_auc", "eval_loss"):
-        vals = [float(v) for v in re.findall(rf"{key}\W+([-+0-9.eE]+|nan|inf)", log)]
-        assert vals and all(math.isfinite(v) for v in vals), (key, vals)
+    H.finite_metrics(log)
 
 
 def test_adamw_trajectory_lowers_the_loss_of_a_fixed_batch():
@@ -199,7 +122,7 @@ def test_adamw_trajectory_lowers_the_loss_of_a_fixed_batch():
     from mapx.arguments import TrainingArguments
     from mapx.models import build_backbone
     from mapx.optim import MapxOptimizer
-    ids, labels, _ = _data(256, 6)
+    ids, labels, _ = H.synth_data(256, SMALL["F"], SMALL["V"], 6)
     torch.manual_seed(2)
     model = build_backbone(fp.make_config(SMALL, "CTR", "FiGNN", None, res_conn=True)).to(DEV).train()
     targs = TrainingArguments(output_dir="unused", learning_rate=1e-2, weight_decay=0.0, lr_sched="const")

@@ -9,28 +9,13 @@ import torch
 
 import paramgen as pg
 import row_widths_ref as RW
+from model_harness import all_grads, load_params
 from util import assert_digest, build_model, load_case, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CASES = list(pg.CASES)
 OTHER = [("B_f25_b64", b) for b in pg.BACKBONES[1:]]      # DNN, DeepFM
-
-
-def _dense_named_grads(model):
-    tab = model.table_parameter_ids()
-    return {n: p.grad for n, p in model.named_parameters() if id(p) not in tab}
-
-
-def _all_grads(model):
-    out = dict(_dense_named_grads(model))
-    names = {id(p): n for n, p in model.named_parameters()}
-    for table in model.row_tables():
-        g0, g1 = table.dense_grad()
-        out[names[id(table.p0)]] = g0
-        if g1 is not None:
-            out[names[id(table.p1)]] = g1
-    return out
 
 
 def _check_grads(z, model, pattern=None, tag=None):
@@ -43,7 +28,7 @@ def _check_grads(z, model, pattern=None, tag=None):
     falls back to the oracle (pinned to the same fixture, tests/test_oracle_golden.py) re-run on the
     step's own activation pattern, after checking that the patterns differ only at such units."""
     from util import fallback_allowed, note_golden
-    grads = _all_grads(model)
+    grads = all_grads(model)
     try:
         for n, g in grads.items():
             assert g is not None, n
@@ -307,17 +292,7 @@ def _full_batch_vs_fp64_oracle(mode, B, F, E=16, H=1000):
         assert abs(acc - acc64) <= 2                      # exact ties aside
     elif mode == "RFD":
         assert abs(float(acc) - float(acc64)) <= 2.0 / out64.numel()
-    names = {id(p): n for n, p in model.named_parameters()}
-    report = {}
-    for n, g in _dense_named_grads(model).items():
-        report[n] = _three_way(n, g, g32[n], g64[n])
-    for table in model.row_tables():
-        g0, g1 = table.dense_grad()
-        n0 = names[id(table.p0)]
-        report[n0] = _three_way(n0, g0, g32[n0], g64[n0])
-        if g1 is not None:
-            n1 = names[id(table.p1)]
-            report[n1] = _three_way(n1, g1, g32[n1], g64[n1])
+    report = {n: _three_way(n, g, g32[n], g64[n]) for n, g in all_grads(model).items()}
     worst = max(report, key=lambda k: report[k][0])
     print(f"[{tag}] worst gradient error vs fp64 / scale: hip {report[worst][0]:.2e} at {worst}; "
           f"cpu fp32 oracle on its own pattern: {max(v[1] for v in report.values()):.2e}")
@@ -429,7 +404,7 @@ def test_other_backbones_at_narrow_embed_sizes_vs_float64(backbone, mode, E):
     loss_ref, logits_ref, ref = BR.step(backbone, mode, params, batch, num_hidden=cfg["NL"], ai=ai, relu_masks=masks)
     np.testing.assert_allclose(float(loss.detach()), loss_ref, rtol=1e-5)
     np.testing.assert_allclose(logits["out"].cpu().numpy().ravel(), logits_ref.ravel(), rtol=1e-5, atol=1e-6)
-    grads = _all_grads(model)
+    grads = all_grads(model)
     assert set(grads) == set(ref), (sorted(grads), sorted(ref))
     worst = max((BR.rel(grads[n].cpu().numpy(), ref[n]), n) for n in grads)
     print(f"[{backbone} {mode} B={B} F={F} E={E}] {flips} ReLU units on the other side of the kink; worst gradient error "
@@ -605,12 +580,7 @@ def test_dcnv2_step_with_another_hidden_act_vs_oracle(kind):
     cfg, z, inp, params = load_case(case, "MFP")
     config = make_config(cfg, "MFP", inp["feat_count"])
     config.hidden_act = kind
-    model = BaseModel.from_config(config)
-    with torch.no_grad():
-        sd = model.state_dict()
-        for k, v in params.items():
-            sd[k].copy_(torch.from_numpy(v))
-    model = model.to(DEV)
+    model = load_params(BaseModel.from_config(config), params).to(DEV)
     model.mfp_criterion.return_logits = True
     ids, mi = t(inp["input_ids"], DEV), t(inp["masked_index"], DEV)
     masked, labels, _ = ops.dynamic_mask_mfp(ids, mi.shape[1], masked_index=mi)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import model_harness as H
 import paramgen as pg
 from util import build_model, load_case, t
 
@@ -266,11 +267,6 @@ def test_dynamic_mask_normal_mode_has_distinct_fields():
         tr.dynamic_mask({"input_ids": t(inp["input_ids"], DEV)}, "bogus")
 
 
-def _run_py(args, cwd):
-    cmd = [sys.executable, os.path.join(ROOT, "map-code_amd", "run.py")] + args
-    return subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, timeout=600)
-
-
 def test_run_py_pretrain_then_finetune(tmp_path):
     """The four run scripts' flow on a small synthetic dataset in the reference's on-disk layout."""
     from mapx.dataset import write_synth_dataset
@@ -281,7 +277,7 @@ def test_run_py_pretrain_then_finetune(tmp_path):
               "--logging_steps=5"]
     for pt in ("MFP", "RFD"):
         out = str(tmp_path / "out" / pt)
-        r = _run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=2", "--lr_sched=cosine",
+        r = H.run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=2", "--lr_sched=cosine",
                      "--weight_decay=5e-2", f"--pt_type={pt}", "--sampling_method=randint", "--mask_ratio=0.3",
                      "--pt_neg_num=25", "--proj_size=32"] + common, str(tmp_path))
         assert r.returncode == 0, r.stderr[-3000:]
@@ -293,10 +289,10 @@ def test_run_py_pretrain_then_finetune(tmp_path):
         assert set(sd) == set(gold) and all(v.dtype in (torch.float32, torch.int64) for v in sd.values())
         log = open(os.path.join(out, "train.log")).read()
         assert "window_" in log and "eval_" in log
-    r2 = _run_py(["--pretrain=True", f"--output_dir={tmp_path / 'out' / 'MFP'}", "--pt_type=MFP"] + common, str(tmp_path))
+    r2 = H.run_py(["--pretrain=True", f"--output_dir={tmp_path / 'out' / 'MFP'}", "--pt_type=MFP"] + common, str(tmp_path))
     assert r2.returncode == 0 and "job already finished" in r2.stdout
     fo = str(tmp_path / "out" / "finetune")
-    r3 = _run_py(["--finetune", f"--pretrained_model_path={tmp_path / 'out' / 'MFP' / f'{steps}.model'}",
+    r3 = H.run_py(["--finetune", f"--pretrained_model_path={tmp_path / 'out' / 'MFP' / f'{steps}.model'}",
                   f"--output_dir={fo}", "--num_train_epochs=1", "--lr_sched=const", "--weight_decay=1e-1"] + common,
                  str(tmp_path))
     assert r3.returncode == 0, r3.stderr[-3000:]
@@ -445,14 +441,13 @@ def _graph_equals_eager(max_grad_norm, backbone, full, epochs, tail=100, arms=((
         tr.use_graph = use_graph
         tr.MFP_pretrain()
         assert tr.global_step == epochs * (full + (1 if tail else 0))
-        assert (len(tr._graphs) == 1 and not isinstance(next(iter(tr._graphs.values())), int)) == use_graph
+        assert (len(tr._graphs) == 1 and len(H.captured(tr)) == 1) == use_graph
         if use_graph:
-            kind = type(next(iter(tr._graphs.values()))).__name__
+            kind = type(H.captured(tr)[0]).__name__
             assert kind == ("GraphedBackward" if max_grad_norm > 0 else "GraphedStep")
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
+        out.append(H.model_state(model))
     nce.LAZY_FOLD, _layers.EMB_LAZY_FOLD = fold_default, emb_default
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
+    H.assert_same_state(out[0], out[1])
 
 
 @pytest.mark.gpu
@@ -470,8 +465,8 @@ def test_rfd_and_finetune_steps_walk_row_references_like_the_eager_loop(pt, max_
     cfg = dict(F=23, V=3000, E=16, H=64, NL=3, NC=3, P=32, K=25)
     ids, labels, _, _ = synth_table(512 * 9 + 100, 23, cfg["V"], seed=3)
     cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
-    out = []
-    for use_graph in (True, False):
+
+    def run(use_graph):
         torch.manual_seed(5)
         config = make_config(cfg, pt, cnt)
         model = BaseModel.from_config(config)
@@ -487,15 +482,15 @@ def test_rfd_and_finetune_steps_walk_row_references_like_the_eager_loop(pt, max_
         tr.use_graph = use_graph
         tr.RFD_pretrain() if pt == "RFD" else tr.train()
         assert tr.global_step == 2 * 10
-        graphs = [g for g in tr._graphs.values() if not isinstance(g, int)]
+        graphs = H.captured(tr)
         assert bool(graphs) == use_graph
         if use_graph and max_grad_norm > 0:
             assert type(graphs[0]).__name__ == "GraphedBackward"
         elif use_graph:
             assert isinstance(graphs[0], GraphedStep) and graphs[0].walk
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
+        return H.model_state(model)
+
+    H.graph_vs_eager(run)
 
 
 def test_resume_state_continues_bit_exactly(tmp_path):
@@ -525,49 +520,17 @@ def test_resume_state_continues_bit_exactly(tmp_path):
         model.train()
         return tr, list(train.batches(512, True, tr._generator(), (0, 1)))
 
-    tr_a, batches = make()
-    for X, Y in batches:
-        tr_a.run_step("mfp", X, Y)
-    tr_a.optimizer.flush()
-    ref = {k: v.detach().cpu().clone() for k, v in tr_a.model.state_dict().items()}
-
-    tr_b, batches_b = make()
-    for X, Y in batches_b[:3]:
-        tr_b.run_step("mfp", X, Y)
-    tr_b.save_training_state(str(tmp_path / "state.pt"))
-    tr_c, batches_c = make()
-    tr_c.load_training_state(str(tmp_path / "state.pt"))
-    assert tr_c.global_step == 3 and tr_c.optimizer.steps_done == 3
-    for X, Y in batches_c[3:]:
-        tr_c.run_step("mfp", X, Y)
-    tr_c.optimizer.flush()
-    for k, v in tr_c.model.state_dict().items():
-        assert torch.equal(v.detach().cpu(), ref[k]), k
+    H.resume_roundtrip(make, 6, 3, str(tmp_path / "state.pt"))
 
 
 def test_run_py_deepfm_pretrain_then_finetune(tmp_path):
     """run.py --model_name=DeepFM: MFP pretraining, then finetune from that checkpoint (LR / FM /
     MLP weights are loaded by name, the pretraining head is reported as unmatched)."""
-    from mapx.dataset import write_synth_dataset
-    data = write_synth_dataset(str(tmp_path / "data" / "avazu"), num_rows=4000, num_fields=23, vocab=2000)
-    common = ["--dataset_name=avazu", f"--data_dir={data}", "--per_gpu_train_batch_size=512",
-              "--per_gpu_eval_batch_size=512", "--learning_rate=1e-3", "--model_name=DeepFM", "--embed_size=16",
-              "--hidden_size=64", "--num_hidden_layers=2", "--hidden_dropout_rate=0.0", "--logging_steps=3"]
-    out = str(tmp_path / "out" / "mfp")
-    r = _run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=1", "--lr_sched=cosine",
-                 "--weight_decay=5e-2", "--pt_type=MFP", "--sampling_method=randint", "--mask_ratio=0.3",
-                 "--pt_neg_num=25", "--proj_size=32"] + common, str(tmp_path))
-    assert r.returncode == 0, r.stderr[-3000:]
-    steps = (3200 + 511) // 512
-    ckpt = os.path.join(out, f"{steps}.model")
-    sd = torch.load(ckpt)
+    common = ["--model_name=DeepFM", "--embed_size=16", "--hidden_size=64", "--num_hidden_layers=2",
+              "--hidden_dropout_rate=0.0", "--logging_steps=3"]
+    sd, log = H.pretrain_then_finetune(tmp_path, common, ["--pt_type=MFP", "--pt_neg_num=25"], [])
     assert {"lr_layer.embed_w.weight", "lr_layer.bias", "ip_layer.field_p", "dnn.dnn.0.weight",
             "feat_encoder.weight", "mfp_criterion.emb.weight"} <= set(sd)
-    fo = str(tmp_path / "out" / "finetune")
-    r2 = _run_py(["--finetune", f"--pretrained_model_path={ckpt}", f"--output_dir={fo}", "--num_train_epochs=1",
-                  "--lr_sched=const", "--weight_decay=1e-1"] + common, str(tmp_path))
-    assert r2.returncode == 0, r2.stderr[-3000:]
-    log = open(os.path.join(fo, "results.log")).read()
     assert "Load tensor: lr_layer.embed_w.weight" in log and "Unmatched tensor in the target model: feat_encoder.weight" in log
     assert "eval_auc" in log
 
@@ -575,29 +538,13 @@ def test_run_py_deepfm_pretrain_then_finetune(tmp_path):
 def test_run_py_xdeepfm_pretrain_then_finetune(tmp_path):
     """run.py --model_name=xDeepFM: RFD pretraining (graph replay of the CIN step), then finetune with
     use_lr from that checkpoint (CIN / MLP weights loaded by name, the LR term starts fresh)."""
-    from mapx.dataset import write_synth_dataset
-    data = write_synth_dataset(str(tmp_path / "data" / "avazu"), num_rows=4000, num_fields=23, vocab=2000)
-    common = ["--dataset_name=avazu", f"--data_dir={data}", "--per_gpu_train_batch_size=512",
-              "--per_gpu_eval_batch_size=512", "--learning_rate=1e-3", "--model_name=xDeepFM", "--embed_size=16",
-              "--hidden_size=64", "--num_hidden_layers=2", "--hidden_dropout_rate=0.0", "--logging_steps=3",
-              "--cin_layer_units=16,8"]
-    out = str(tmp_path / "out" / "rfd")
-    r = _run_py(["--pretrain=True", f"--output_dir={out}", "--num_train_epochs=1", "--lr_sched=cosine",
-                 "--weight_decay=5e-2", "--pt_type=RFD", "--sampling_method=randint", "--mask_ratio=0.3",
-                 "--RFD_replace=Unigram", "--proj_size=32"] + common, str(tmp_path))
-    assert r.returncode == 0, r.stderr[-3000:]
-    steps = (3200 + 511) // 512
-    ckpt = os.path.join(out, f"{steps}.model")
-    sd = torch.load(ckpt)
+    common = ["--model_name=xDeepFM", "--embed_size=16", "--hidden_size=64", "--num_hidden_layers=2",
+              "--hidden_dropout_rate=0.0", "--logging_steps=3", "--cin_layer_units=16,8"]
+    sd, log = H.pretrain_then_finetune(tmp_path, common, ["--pt_type=RFD", "--RFD_replace=Unigram"], ["--use_lr=True"])
     assert {"cin.cin_layer.layer_1.weight", "cin.cin_layer.layer_2.bias", "dnn.dnn.0.weight",
             "pred_rfd.0.weight"} <= set(sd)
     assert tuple(sd["cin.cin_layer.layer_1.weight"].shape) == (16, 23 * 23, 1)
     assert tuple(sd["cin.cin_layer.layer_2.weight"].shape) == (8, 23 * 16, 1)
-    fo = str(tmp_path / "out" / "finetune")
-    r2 = _run_py(["--finetune", f"--pretrained_model_path={ckpt}", f"--output_dir={fo}", "--num_train_epochs=1",
-                  "--lr_sched=const", "--weight_decay=1e-1", "--use_lr=True"] + common, str(tmp_path))
-    assert r2.returncode == 0, r2.stderr[-3000:]
-    log = open(os.path.join(fo, "results.log")).read()
     assert "Load tensor: cin.cin_layer.layer_2.weight" in log and "Unmatched tensor in the target model: pred_rfd.0.weight" in log
     assert "eval_auc" in log
 
@@ -687,8 +634,7 @@ def test_full_vocabulary_step_properties(F, V, pt, dtype):
         finals.append({n: p.detach().clone() for n, p in model.named_parameters()})
         del tr, model
         torch.cuda.empty_cache()
-    for n in finals[0]:                                                   # (1)
-        assert torch.equal(finals[0][n], finals[1][n]), n
+    H.assert_same_state(finals[0], finals[1])                             # (1)
     # (3) rows whose value equals "zero-gradient AdamW from the initial value" must be exactly the
     # untouched ones; check the prediction on the probe rows that stayed untouched in every table
     lambdas = [R.lr_lambda("cosine", s, steps, 0) for s in range(steps)]
@@ -815,8 +761,8 @@ def test_graph_replay_equals_eager_bitwise_with_dropout():
     cfg = dict(F=23, V=3000, E=16, H=64, NL=3, NC=3, P=32, K=25)
     ids, labels, _, _ = synth_table(512 * 6, 23, cfg["V"], seed=3)
     cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
-    out = []
-    for use_graph in (True, False):
+
+    def run(use_graph):
         torch.manual_seed(5)
         config = make_config(cfg, "MFP", cnt)
         config.hidden_dropout_rate, config.embed_dropout_rate = 0.2, 0.1
@@ -830,10 +776,10 @@ def test_graph_replay_equals_eager_bitwise_with_dropout():
         tr = Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:600], labels[:600]))
         tr.use_graph = use_graph
         tr.MFP_pretrain()
-        assert (len(tr._graphs) == 1 and not isinstance(next(iter(tr._graphs.values())), int)) == use_graph
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
+        assert (len(tr._graphs) == 1 and len(H.captured(tr)) == 1) == use_graph
+        return H.model_state(model)
+
+    H.graph_vs_eager(run)
 
 
 def test_capture_refuses_a_join_with_a_stream_outside_the_capture():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import model_harness as H
 import paramgen as pg
 import trans_params as tp
 from util import assert_digest, t
@@ -15,18 +16,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = [(m, v) for v in tp.VARIANTS for m in tp.modes_of(v)]
-
-
-def _all_grads(model):
-    tab = model.table_parameter_ids()
-    out = {n: p.grad for n, p in model.named_parameters() if id(p) not in tab}
-    names = {id(p): n for n, p in model.named_parameters()}
-    for table in model.row_tables():
-        g0, g1 = table.dense_grad()
-        out[names[id(table.p0)]] = g0
-        if g1 is not None:
-            out[names[id(table.p1)]] = g1
-    return out
+TCFG = dict(F=23, V=3000, E=16, H=16, NL=2, NC=0, P=32, K=25)
 
 
 @pytest.mark.parametrize("mode,variant", FIXTURES)
@@ -55,7 +45,7 @@ def test_reference_fixture(mode, variant):
         np.testing.assert_allclose(logits.detach().cpu().numpy(), z["out/logits"], rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(float(loss.detach()), float(z["out/loss"]), rtol=1e-5)
     loss.backward()
-    for n, g in _all_grads(model).items():
+    for n, g in H.all_grads(model).items():
         assert g is not None, n
         assert_digest(z, "grad", n, g.cpu().numpy())
     with torch.no_grad():
@@ -128,21 +118,11 @@ def test_full_batch_trunk_vs_float64_torch_encoder(norm_first, act, heads):
         close(p.grad, refp[n].grad, n)
 
 
-def _trainer(cfg, mode, ids, labels, cnt, out_dir, epochs=2, seed=5, **over):
-    from mapx.arguments import TrainingArguments
-    from mapx.dataset import OurDataset
+def _trainer(mode, data, out_dir, epochs=2, seed=5, begin=False, **over):
     from mapx.models import BaseModel
-    from mapx.trainer import Trainer
     torch.manual_seed(seed)
-    config = tp.make_config(cfg, mode, "Trans", cnt, **over)
-    model = BaseModel.from_config(config)
-    targs = TrainingArguments(output_dir=out_dir, per_gpu_train_batch_size=512, per_gpu_eval_batch_size=512,
-                              learning_rate=1e-3, lr_sched="cosine", weight_decay=5e-2, num_train_epochs=epochs,
-                              pretrain=mode != "CTR", pt_type="MFP", sampling_method="randint", mask_ratio=0.3,
-                              logging_steps=7, seed=11, patience=100)
-    targs._device = torch.device(DEV)
-    os.makedirs(out_dir, exist_ok=True)
-    return Trainer(model, config, targs, OurDataset(ids, labels), OurDataset(ids[:600], labels[:600])), model
+    config = tp.make_config(TCFG, mode, "Trans", data[2], **over)
+    return H.make_trainer(config, BaseModel.from_config(config), mode, data, out_dir, 512, epochs, 600, begin=begin)
 
 
 @pytest.mark.parametrize("mode,p", [("MFP", 0.0), ("MFP", 0.1), ("CTR", 0.0)])
@@ -150,58 +130,33 @@ def test_graph_replay_equals_eager_bitwise(mode, p, tmp_path):
     """The captured step draws the Philox streams of the eager step (the attention-probability site included: a
     HipDropout the Trainer gives its seed, site and device-side step counter): identical parameters after two epochs
     with a ragged last batch, bit for bit."""
-    from mapx.dataset import synth_table
-    cfg = dict(F=23, V=3000, E=16, H=16, NL=2, NC=0, P=32, K=25)
-    ids, labels, _, _ = synth_table(512 * 4 + 100, 23, cfg["V"], seed=3)
-    cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
-    out = []
-    for use_graph in (True, False):
-        tr, model = _trainer(cfg, mode, ids, labels, cnt, str(tmp_path / str(use_graph)), hidden_dropout_rate=p)
+    data = H.synth_data(512 * 4 + 100, TCFG["F"], TCFG["V"], seed=3)
+
+    def run(use_graph):
+        tr, model = _trainer(mode, data, str(tmp_path / str(use_graph)), hidden_dropout_rate=p)
         tr.use_graph = use_graph
         tr.MFP_pretrain() if mode == "MFP" else tr.train()
         assert tr.global_step == 2 * 5
-        graphs = [g for g in tr._graphs.values() if not isinstance(g, int)]
-        assert bool(graphs) == use_graph
+        assert bool(H.captured(tr)) == use_graph
         if p > 0:
             from mapx.layers import MhaDropout
             sites = [m for m in model.modules() if isinstance(m, MhaDropout)]
             assert len(sites) == 2 and all(m.step_counter is not None for m in sites)
-        out.append({k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
-    for k in out[0]:
-        assert torch.equal(out[0][k], out[1][k]), k
+        return H.model_state(model)
+
+    H.graph_vs_eager(run)
 
 
 def test_resume_state_continues_bit_exactly(tmp_path):
     """6 steps == 3 steps + save_training_state + fresh trainer + load_training_state + 3 steps (dropout on)."""
-    from mapx.dataset import synth_table
-    cfg = dict(F=23, V=3000, E=16, H=16, NL=2, NC=0, P=32, K=25)
-    ids, labels, _, _ = synth_table(512 * 6, 23, cfg["V"], seed=4)
-    cnt = np.bincount(ids.reshape(-1), minlength=cfg["V"]).astype(np.float32)
+    data = H.synth_data(512 * 6, TCFG["F"], TCFG["V"], seed=4)
 
     def make():
-        tr, model = _trainer(cfg, "MFP", ids, labels, cnt, str(tmp_path), epochs=1, seed=9, hidden_dropout_rate=0.1)
+        tr, _, batches = _trainer("MFP", data, str(tmp_path), epochs=1, seed=9, begin=True, hidden_dropout_rate=0.1)
         tr.use_graph = False
-        train = tr._begin("test")
-        model.train()
-        return tr, list(train.batches(512, True, tr._generator(), (0, 1)))
+        return tr, batches
 
-    tr_a, batches = make()
-    for X, Y in batches:
-        tr_a.run_step("mfp", X, Y)
-    tr_a.optimizer.flush()
-    ref = {k: v.detach().cpu().clone() for k, v in tr_a.model.state_dict().items()}
-    tr_b, batches_b = make()
-    for X, Y in batches_b[:3]:
-        tr_b.run_step("mfp", X, Y)
-    tr_b.save_training_state(str(tmp_path / "state.pt"))
-    tr_c, batches_c = make()
-    tr_c.load_training_state(str(tmp_path / "state.pt"))
-    assert tr_c.global_step == 3 and tr_c.optimizer.steps_done == 3
-    for X, Y in batches_c[3:]:
-        tr_c.run_step("mfp", X, Y)
-    tr_c.optimizer.flush()
-    for k, v in tr_c.model.state_dict().items():
-        assert torch.equal(v.detach().cpu(), ref[k]), k
+    H.resume_roundtrip(make, 6, 3, str(tmp_path / "state.pt"))
 
 
 @pytest.mark.parametrize("M,N,K", [(94208, 1, 16), (94208, 16, 128), (94208, 16, 16)])

@@ -59,12 +59,9 @@ def make_config(cfg, mode, feat_count=None, data_dir=None, seed=42, backbone="DC
 def build_model(cfg, mode, params, feat_count, device="cuda", backbone="DCNv2", compute_dtype="fp32"):
     """The backbone with the fixture's reproducible parameters loaded."""
     from mapx.models import BaseModel
+    from model_harness import load_params
     model = BaseModel.from_config(make_config(cfg, mode, feat_count, backbone=backbone, compute_dtype=compute_dtype))
-    with torch.no_grad():
-        sd = model.state_dict()
-        for k, v in params.items():
-            sd[k].copy_(torch.from_numpy(v))
-    return model.to(device)
+    return load_params(model, params).to(device)
 
 
 # ----------------------------------------------------------------------------- ReLU pattern of a step
