@@ -548,6 +548,23 @@ size_t mapx_slice_metrics_workspace_bytes(int64_t n, int64_t n_groups);
 int mapx_slice_metrics(const float* logits, const float* labels, const int32_t* groups, int64_t n, int64_t n_groups,
                        int64_t* rows, int64_t* positives, uint64_t* u2, double* sum_prob, double* sum_loss,
                        int64_t* status2, void* ws, size_t ws_bytes, hipStream_t stream);
+/* Poisson bootstrap of the two metrics (csrc/bootstrap.hip): `replicates` resamples of the rows.  Replicate
+ * r gives unit u the weight  #{k in 0..11 : word >= T[k]},  word = element r % 4 of Philox4x32-10(key = seed, counter =
+ * {u, 'BOOT' << 32 | r / 4}),  T[k] = floor(2^32 * P(Poisson(1) <= k)) (csrc/bootstrap.hip: boot_weight), so 0..12.
+ * units [n] int64: the unit of each row (rows of one unit share a weight); NULL: the row number.  The weight depends
+ * on (seed, unit, r) alone, so two calls on the same rows with other logits see the same resample.
+ * Outputs (device, `replicates` elements each): pos_w = sum w y, neg_w = sum w (1 - y), u2 = twice the weighted U
+ * statistic on the fp32 sigmoid (AUC_r = u2 / (2 pos_w neg_w); ties count half; a NaN logit ranks as p = 1), sum_loss =
+ * sum of w * mapx_eval_metrics' log-loss row term in f64.  The integers are exact, sum_loss is bitwise reproducible and
+ * the same on every device (its order of additions depends on n alone).  1 <= n <= 2^28, 1 <= replicates <= 65536.
+ * mapx_bootstrap_weights writes the weights themselves, w [replicates, n] row-major, from the same device function
+ * (test entry, and the host reference's input). */
+size_t mapx_bootstrap_workspace_bytes(int64_t n, int replicates);
+int mapx_bootstrap_metrics(const float* logits, const float* labels, const int64_t* units, int64_t n, int replicates,
+                           uint64_t seed, uint64_t* u2, uint64_t* pos_w, uint64_t* neg_w, double* sum_loss, void* ws,
+                           size_t ws_bytes, hipStream_t stream);
+int mapx_bootstrap_weights(const int64_t* units, int64_t n, int replicates, uint64_t seed, uint8_t* w,
+                           hipStream_t stream);
 /* trainer.py:217-232 (MFP): masked_index_in NULL -> Philox, keyed by (seed, offset + *offset_dev).
  * draw (ignored when masked_index_in is given; the same in mapx_dynamic_mask_mfp_rows and mapx_dynamic_mask_rfd):
  *   0  with replacement (sampling_method="randint"): masked_index[b,l] = word x of Philox(counter b*L + l) scaled to

@@ -149,6 +149,16 @@ __device__ inline float dot4(const float4& a, const float4& b, float s) {
 // (metrics.hip) is what a scoring run writes out (score.hip), bit for bit.
 __device__ inline float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// THE log-loss row term on that probability: the clipped probability of the row's own class, in fp64 with sklearn's
+// clip to [eps, 1 - eps], eps = 2^-52 (log_loss on a float64 array); the term is -log of it.  What metrics.hip sums
+// per row, bootstrap.hip sums with weights.
+__device__ inline double logloss_clipped(double p, bool y) {
+  const double eps = 2.220446049250313e-16;
+  const double q = y ? p : 1.0 - p;
+  return q < eps ? eps : (q > 1.0 - eps ? 1.0 - eps : q);
+}
+__device__ inline double logloss_term(float p32, bool y) { return -log(logloss_clipped((double)p32, y)); }
+
 // ---------------------------------------------------------------- bf16 I/O (bf16 compute mode)
 // Kernels templated on an element type T = float | bf16_t differ only here: a load widens to fp32 (exact), all
 // arithmetic is fp32, a store rounds to nearest even once (v_cvt_pk_bf16_f32).

@@ -58,7 +58,6 @@ __global__ void __launch_bounds__(kEvalBlock) eval_prepare_kernel(
     const float* __restrict__ logits, const float* __restrict__ labels, int64_t n,
     uint32_t* __restrict__ keys, uint8_t* __restrict__ pos, double* __restrict__ partial) {
   __shared__ double smem[kEvalBlock / 64];
-  const double eps = 2.220446049250313e-16;
   double ll = 0.0, sx = 0.0, sp = 0.0, np = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kEvalBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kEvalBlock) {
     const float x = logits[i];
@@ -67,9 +66,7 @@ __global__ void __launch_bounds__(kEvalBlock) eval_prepare_kernel(
     keys[i] = __float_as_uint(p32);
     pos[i] = y ? 1 : 0;
     const double p = (double)p32;
-    double q = y ? p : 1.0 - p;
-    q = q < eps ? eps : (q > 1.0 - eps ? 1.0 - eps : q);
-    ll -= log(q);
+    ll += logloss_term(p32, y);
     sx += (double)x;
     sp += p;
     np += y ? 1.0 : 0.0;

@@ -133,6 +133,9 @@ SIGNATURES = {
     "mapx_eval_metrics": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),
     "mapx_slice_metrics_workspace_bytes": (_sz, [_i64, _i64]),
     "mapx_slice_metrics": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mapx_bootstrap_workspace_bytes": (_sz, [_i64, _i]),
+    "mapx_bootstrap_metrics": (_i, [_p, _p, _p, _i64, _i, _u64, _p, _p, _p, _p, _p, _sz, _p]),
+    "mapx_bootstrap_weights": (_i, [_p, _i64, _i, _u64, _p, _p]),
     "mapx_dynamic_mask_mfp": (_i, [_p, _i64, _i, _i, _p, _u64, _u64, _p, _p, _p, _p, _p, _i, _p]),
     "mapx_dynamic_mask_mfp_rows": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _i, _p, _u64, _u64, _p, _p, _p, _p, _p, _i,
                                         _p]),

@@ -2339,6 +2339,92 @@ def slice_metrics(logits, labels, groups, n_groups, out=None):
     return out
 
 
+# floor(2^32 * P(Poisson(1) <= k)), k = 0..11: a 32-bit word's weight is the number of these it reaches
+# (csrc/bootstrap.hip: boot_weight; tests/test_bootstrap_host.py recomputes them with 60-digit decimals)
+BOOT_POISSON_T = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291,
+                  4294609777, 4294923276, 4294962463, 4294966817, 4294967252, 4294967292)
+BOOT_MAX_ROWS, BOOT_MAX_REPLICATES = 2 ** 28, 65536
+BOOT_OUTPUTS = (("u2", torch.int64), ("pos_w", torch.int64), ("neg_w", torch.int64), ("sum_loss", torch.float64))
+
+
+def _boot_sizes(name, n, replicates, seed):
+    R, seed = int(replicates), int(seed)
+    if not 1 <= R <= BOOT_MAX_REPLICATES:
+        raise ValueError(f"{name}: 1 <= replicates <= {BOOT_MAX_REPLICATES} (got {replicates})")
+    if not n <= BOOT_MAX_ROWS:
+        raise ValueError(f"{name}: at most 2^28 rows (got {n})")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{name}: the seed is an unsigned 64-bit integer (got {seed})")
+    return R, seed
+
+
+def _boot_units(name, units, n):
+    if units is None:
+        return None
+    require_gpu(units)
+    if units.dtype != torch.int64:
+        raise TypeError(f"{name}: units is int64, got {units.dtype}")
+    units = units.contiguous().view(-1)
+    if units.numel() != n:
+        raise ValueError(f"{name}: {n} rows, {units.numel()} units")
+    return units
+
+
+def bootstrap_metrics(logits, labels, replicates, seed=0, units=None, out=None):
+    """Poisson bootstrap of eval_metrics' AUC and log-loss (include/mapx_hip.h: mapx_bootstrap_metrics).
+    units: int64 [n], the resampling unit of each row (rows of one unit share a weight); None: every row its own.
+    -> (u2, pos_w, neg_w i64, sum_loss f64), device tensors of `replicates` elements: per replicate the weighted
+    positives and negatives, twice the weighted U statistic (AUC_r = u2 / (2 pos_w neg_w), u2 < 2^63) and the weighted
+    sum of the log-loss row terms.  The resample depends on (seed, units) alone, not on the logits: two models scored
+    on the same rows with one seed are compared on the same resamples.  The integers are exact, sum_loss bitwise
+    reproducible.  out: the four tensors to write (contiguous, these element types).  n = 0 gives zeros."""
+    require_gpu(logits, labels)
+    logits = logits.contiguous().view(-1).float()
+    labels = labels.contiguous().view(-1).float()
+    n = logits.numel()
+    if labels.numel() != n:
+        raise ValueError(f"bootstrap_metrics: {n} logits, {labels.numel()} labels")
+    R, seed = _boot_sizes("bootstrap_metrics", n, replicates, seed)
+    units = _boot_units("bootstrap_metrics", units, n)
+    dev = logits.device
+    if out is None:
+        out = tuple(torch.empty(R, dtype=dt, device=dev) for _, dt in BOOT_OUTPUTS)
+    out = tuple(out)
+    require_gpu(*out)
+    if len(out) != 4 or any(o.dtype != dt or o.numel() != R or not o.is_contiguous()
+                            for o, (_, dt) in zip(out, BOOT_OUTPUTS)):
+        raise TypeError(f"bootstrap_metrics: out is four contiguous tensors of {R} elements: "
+                        + ", ".join(f"{k} {str(dt)[6:]}" for k, dt in BOOT_OUTPUTS))
+    if n == 0:
+        for o in out:
+            o.zero_()
+        return out
+    ws = scratch(lib.mapx_bootstrap_workspace_bytes(n, R), dev)
+    check(lib.mapx_bootstrap_metrics(ptr(logits), ptr(labels), ptr(units), n, R, seed, *(ptr(o) for o in out),
+                                     ptr(ws), ws.numel(), stream()))
+    return out
+
+
+def bootstrap_weights(n_or_units, replicates, seed=0, device="cuda"):
+    """-> uint8 [replicates, n]: the weights bootstrap_metrics gives the rows, from the device function its replicate
+    kernel calls.  n_or_units: a row count (every row its own unit) or the int64 [n] units.  Test entry, and what a
+    host restatement of the resample starts from."""
+    if torch.is_tensor(n_or_units):
+        n = n_or_units.numel()
+        units = _boot_units("bootstrap_weights", n_or_units, n)
+        device = units.device
+    else:
+        n, units = int(n_or_units), None
+        if n < 0:
+            raise ValueError(f"bootstrap_weights: {n} rows")
+    R, seed = _boot_sizes("bootstrap_weights", n, replicates, seed)
+    w = torch.empty(R, n, dtype=torch.uint8, device=device)
+    require_gpu(w)
+    if n:
+        check(lib.mapx_bootstrap_weights(ptr(units), n, R, seed, ptr(w), stream()))
+    return w
+
+
 def _check_distinct(name, L, F):
     if L > F:
         raise ValueError(f"{name}: distinct=True draws L distinct fields per row and needs L <= F (L = {L}, F = {F})")

@@ -5,6 +5,7 @@
     python -m mapx.score --model OUT/1234.model --data_dir DIR --dataset_name avazu [--split test|valid|train|all]
                          --out SDIR <run.py's model flags>
     either form: [--group_by C1,site_id,@oov [--top 20]]   sliced evaluation (labels of both classes needed)
+    either form: [--bootstrap 1000 [--bootstrap_seed 0] [--bootstrap_level 0.95] [--bootstrap_by device_id|@row]]
 
 writes SDIR/probs.npy (f32 [N]), logits.npy (f32 [N]), oov_fields.npy (u8 [N]: the fields of a row that took their
 field's <oov> id) and score.json, rows in file order.  One device; no optimizer, no labels needed.
@@ -17,7 +18,12 @@ row's bits depend on its batch mates.
 
 --group_by adds, per named field (and '@oov': the rows by their count of <oov> fields), AUC / log-loss / CTR /
 calibration per value and GAUC, the rows-weighted mean of the per-value AUCs: slices.json, slices_<name>.npz and
-score.json's "slices" (ops.slice_metrics, csrc/slice_metrics.hip: one launch sequence per column)."""
+score.json's "slices" (ops.slice_metrics, csrc/slice_metrics.hip: one launch sequence per column).
+
+--bootstrap R adds Poisson-bootstrap intervals of AUC and log-loss from R resamples of the rows (or of the values of a
+field: --bootstrap_by, the cluster bootstrap): bootstrap.json, bootstrap.npz, labels.npy[, boot_units.npy], score.json's
+"bootstrap", and with --group_by the listed groups' intervals (ops.bootstrap_metrics, csrc/bootstrap.hip; DESIGN
+§4.17).  python -m mapx.compare compares two such directories on the same resamples."""
 import argparse
 import json
 import logging
@@ -312,6 +318,107 @@ def slice_report(rows, positives, u2, sum_prob, sum_loss, top=20, names=None):
     return dict(gauc=gauc, gauc_rows=gauc_rows, groups=int((rows > 0).sum()), top=listed)
 
 
+# ------------------------------------------------------------------------------- bootstrap intervals
+ROW_UNITS = "@row"                  # --bootstrap_by's default: every row is its own resampling unit
+BOOT_ARRAYS = tuple(k for k, _ in ops.BOOT_OUTPUTS)
+BOOT_METRICS = ("auc", "logloss")
+
+Bootstrap = namedtuple("Bootstrap", "replicates seed level by", defaults=(0, 0.95, ROW_UNITS))
+
+
+def boot_values(arrays):
+    """ops.bootstrap_metrics' four arrays (host) -> {auc, logloss}: float64 [R], NaN where the replicate leaves the
+    metric undefined (AUC: a class without weight; log-loss: no weight at all)."""
+    u2 = np.asarray(arrays["u2"]).astype(np.uint64).astype(np.float64)
+    pw, nw = (np.asarray(arrays[k]).astype(np.uint64).astype(np.float64) for k in ("pos_w", "neg_w"))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        auc = np.where((pw > 0) & (nw > 0), (u2 * 0.5) / (pw * nw), np.nan)
+        logloss = np.where(pw + nw > 0, np.asarray(arrays["sum_loss"], dtype=np.float64) / (pw + nw), np.nan)
+    return dict(auc=auc, logloss=logloss)
+
+
+def _quantiles(v, level):
+    if not len(v):
+        return float("nan"), float("nan")
+    lo, hi = np.quantile(v, [(1.0 - level) / 2, (1.0 + level) / 2])
+    return float(lo), float(hi)
+
+
+def bootstrap_report(arrays, point, level=0.95, other=None, other_point=None):
+    """The replicates of one model -> per metric of BOOT_METRICS: point (point[metric], the estimate on the rows as
+    they are), mean and std (ddof 1; 0 for a single replicate) over the defined replicates, lo / hi = the
+    (1 -/+ level) / 2 quantiles of the defined replicates (numpy's linear method), replicates, undefined (left out,
+    never counted as 0).  Floats, the two counts ints.
+    other / other_point: a second model's arrays and estimates on the same resamples (equal pos_w and neg_w, else
+    ValueError) -> also 'delta': per metric point (this - other), lo, hi, frac_positive and frac_zero (the shares of
+    the replicates defined for both with this - other > 0 / == 0), replicates, undefined."""
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"bootstrap_report: 0 < level < 1 (got {level})")
+    mine = boot_values(arrays)
+    out = {}
+    for k in BOOT_METRICS:
+        v = mine[k][np.isfinite(mine[k])]
+        lo, hi = _quantiles(v, level)
+        out[k] = dict(point=float(point[k]), mean=float(v.mean()) if len(v) else float("nan"),
+                      std=float(v.std(ddof=1)) if len(v) > 1 else (0.0 if len(v) else float("nan")), lo=lo, hi=hi,
+                      replicates=int(len(mine[k])), undefined=int(len(mine[k]) - len(v)))
+    if other is not None:
+        same = all(np.asarray(arrays[k]).shape == np.asarray(other[k]).shape
+                   and np.array_equal(np.asarray(arrays[k]).astype(np.uint64), np.asarray(other[k]).astype(np.uint64))
+                   for k in ("pos_w", "neg_w"))
+        if not same:
+            raise ValueError("bootstrap_report: pos_w / neg_w of the two models differ: they were not scored on the "
+                             "same resample (same rows, labels, units, seed and replicates)")
+        theirs, out["delta"] = boot_values(other), {}
+        for k in BOOT_METRICS:
+            d = mine[k] - theirs[k]
+            v = d[np.isfinite(d)]
+            lo, hi = _quantiles(v, level)
+            out["delta"][k] = dict(point=float(point[k]) - float(other_point[k]), lo=lo, hi=hi,
+                                   frac_positive=float((v > 0).mean()) if len(v) else float("nan"),
+                                   frac_zero=float((v == 0).mean()) if len(v) else float("nan"),
+                                   replicates=int(len(d)), undefined=int(len(d) - len(v)))
+    return out
+
+
+def boot_arrays(out):
+    """ops.bootstrap_metrics' tensors -> host arrays by name, the three integers as uint64."""
+    arrays = {k: t.cpu().numpy() for k, t in zip(BOOT_ARRAYS, out)}
+    return {k: (a if k == "sum_loss" else a.view(np.uint64)) for k, a in arrays.items()}
+
+
+def boot_unit_column(boot, names):
+    """The column of --bootstrap_by among the fields (None for @row); ValueError names an unknown one."""
+    if boot is None or boot.by == ROW_UNITS:
+        return None
+    if boot.by not in names:
+        raise ValueError(f"bootstrap_by: {boot.by!r} is not a field ({', '.join(names)}) or {ROW_UNITS}")
+    return list(names).index(boot.by)
+
+
+def _no_bootstrap(why):
+    return ValueError(f"bootstrap needs the labels of both classes: {why}")
+
+
+def slice_intervals(res, name, listed):
+    """The groups a slices.json lists for column `name` gain auc_lo, auc_hi, logloss_lo, logloss_hi and
+    boot_undefined (the replicates without both classes in the group): one ops.bootstrap_metrics call on the group's
+    rows with their units of the whole input, so a row has the weight it has in the global resample.  A host loop over
+    the listed groups, composition of the global pieces."""
+    b, s = res["bootstrap"], res["slices"][name]
+    boot, dev = b["boot"], b["device"]
+    for entry in listed:
+        idx = np.flatnonzero(s["groups"] == entry["group"])
+        units = idx.astype(np.int64) if b["units"] is None else b["units"][idx]
+        out = ops.bootstrap_metrics(torch.from_numpy(res["logits"][idx]).to(dev),
+                                    torch.from_numpy(b["labels"][idx]).to(dev), boot.replicates, seed=boot.seed,
+                                    units=torch.from_numpy(units).to(dev))
+        rep = bootstrap_report(boot_arrays(out), entry, boot.level)
+        entry.update(auc_lo=rep["auc"]["lo"], auc_hi=rep["auc"]["hi"], logloss_lo=rep["logloss"]["lo"],
+                     logloss_hi=rep["logloss"]["hi"], boot_undefined=rep["auc"]["undefined"])
+    return listed
+
+
 def _json_safe(x):
     """NaN / inf -> null: what a strict JSON reader takes."""
     if isinstance(x, dict):
@@ -371,9 +478,10 @@ def _no_slices(why):
     return ValueError(f"group_by needs the labels of both classes: {why}")
 
 
-def _result(parts, labels, names, oov_rows, scorer, extra, slices=None):
+def _result(parts, labels, names, oov_rows, scorer, extra, slices=None, boot=None, unit_pieces=None):
     """slices: None, or [(GroupColumn, its group ids as int32 pieces on the host | None for @oov, group names)]: the
-    columns go to the device once, with the logits."""
+    columns go to the device once, with the logits.  boot: None or a Bootstrap; unit_pieces: its unit column as int64
+    pieces on the host (None: every row its own unit)."""
     dts = (np.float32, np.float32, np.uint8)
     logits, probs, oov_fields = (np.concatenate(p) if p else np.empty(0, dtype=dt) for p, dt in zip(parts, dts))
     metrics, why, dev_logits, dev_y = None, "no labels", None, None
@@ -398,6 +506,19 @@ def _result(parts, labels, names, oov_rows, scorer, extra, slices=None):
             rep = slice_report(**arrays, top=0)
             info["slices"][col.name] = {k: rep[k] for k in ("gauc", "gauc_rows", "groups")}
             res["slices"][col.name] = dict(arrays, base=col.base, names=gnames)
+            if boot is not None:
+                res["slices"][col.name]["groups"] = g                    # (slice_intervals picks a group's rows)
+    if boot is not None:
+        if metrics is None:
+            raise _no_bootstrap(why)
+        units = None if unit_pieces is None else np.concatenate(unit_pieces).astype(np.int64)
+        out = ops.bootstrap_metrics(dev_logits, dev_y, boot.replicates, seed=boot.seed,
+                                    units=None if units is None else torch.from_numpy(units).to(scorer.device))
+        arrays = boot_arrays(out)
+        report = bootstrap_report(arrays, metrics, boot.level)
+        res["bootstrap"] = dict(arrays=arrays, report=report, boot=boot, units=units, labels=(y > 0.5).astype(np.uint8),
+                                device=scorer.device)
+        info["bootstrap"] = {k: dict(lo=report[k]["lo"], hi=report[k]["hi"]) for k in BOOT_METRICS}
     return res
 
 
@@ -406,7 +527,7 @@ def oov_ids_of(meta, names):
     return [int(meta["feat_map"].get(f"{n}-<oov>", -1)) for n in names]
 
 
-def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None, group_by=None):
+def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None, group_by=None, bootstrap=None):
     """Raw text -> scores, chunk by chunk: rawtext.iter_columns -> Vocabulary.encode -> Scorer.push, the results to
     the host per chunk; device memory holds one chunk and the scorer's staging area whatever the file's size.
     schema: rawtext.SCHEMAS[...] or rawtext.UNLABELED[...] (no label field: metrics null).  `path`: a path or an open
@@ -414,10 +535,17 @@ def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None
     score_s, host_s (results to the host).  -> dict(logits, probs, oov_fields: numpy [N]; info: score.json's content).
     group_by: field names and '@oov' (group_columns): the result gains 'slices' {name: ops.slice_metrics' five arrays
     over the whole file, base, names} and info 'slices' {name: gauc, gauc_rows, groups}; the requested columns are
-    kept per chunk as int32 on the host, as the labels are.  ValueError without labels of both classes."""
+    kept per chunk as int32 on the host, as the labels are.  ValueError without labels of both classes.
+    bootstrap: a Bootstrap (replicates, seed, level, by): the result gains 'bootstrap' {arrays: ops.bootstrap_metrics'
+    four, report: bootstrap_report's, units, labels} and info 'bootstrap' {auc: {lo, hi}, logloss: {lo, hi}}; the unit
+    column of `by` is kept per chunk as int64 on the host.  The same ValueError."""
     from . import rawtext
     names, F = voc.field_names, len(voc.fields)
     slices = None
+    if bootstrap is not None and schema.label is None:
+        raise _no_bootstrap("no labels")
+    unit_col = boot_unit_column(bootstrap, names)
+    unit_pieces = None if unit_col is None else []
     if group_by:
         if schema.label is None:
             raise _no_slices("no labels")
@@ -439,6 +567,8 @@ def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None
         for c, pieces, _ in slices or ():
             if pieces is not None:
                 pieces.append((ids[:, c.column] - c.base).to(torch.int32).cpu().numpy())
+        if unit_pieces is not None:
+            unit_pieces.append(ids[:, unit_col].cpu().numpy())
         t3 = clock()
         t_enc, t_score, t_host = t_enc + t1 - t0, t_score + t2 - t1, t_host + t3 - t2
     t0 = clock()
@@ -447,7 +577,8 @@ def score_raw_file(scorer, path, schema, voc, chunk_bytes=256 << 20, timing=None
     _to_host(parts, s)
     if timing is not None:
         timing.update(encode_s=t_enc, score_s=t_score + t1 - t0, host_s=t_host + clock() - t1)
-    return _result(parts, labels, names, oov_rows, scorer, dict(source=str(getattr(path, "name", path))), slices)
+    return _result(parts, labels, names, oov_rows, scorer, dict(source=str(getattr(path, "name", path))), slices,
+                   bootstrap, unit_pieces)
 
 
 def read_dataset(data_dir, dataset_name, split="test"):
@@ -467,11 +598,15 @@ def read_dataset(data_dir, dataset_name, split="test"):
     return meta, np.ascontiguousarray(feat_ids, dtype=np.int64), np.asarray(labels)
 
 
-def score_dataset(scorer, meta, feat_ids, labels=None, names=None, group_by=None):
+def score_dataset(scorer, meta, feat_ids, labels=None, names=None, group_by=None, bootstrap=None):
     """A table on the host -> scores, one staging area of rows on the device at a time.  -> as score_raw_file; the id
-    ranges of group_by's fields come from the meta's feat_map."""
+    ranges of group_by's fields come from the meta's feat_map; bootstrap's unit column is the field's ids."""
     names = names if names is not None else [n for n in meta["field_names"] if n != "<rsv>"]
     slices = None
+    if bootstrap is not None and labels is None:
+        raise _no_bootstrap("no labels")
+    unit_col = boot_unit_column(bootstrap, names)
+    unit_pieces = None if unit_col is None else [np.ascontiguousarray(feat_ids[:, unit_col], dtype=np.int64)]
     if group_by:
         if labels is None:
             raise _no_slices("no labels")
@@ -487,12 +622,14 @@ def score_dataset(scorer, meta, feat_ids, labels=None, names=None, group_by=None
         _to_host(parts, scorer.push(ids))
     _to_host(parts, scorer.finish())
     y = None if labels is None else [np.asarray(labels).astype(np.int64)]
-    return _result(parts, y, names, oov_rows.tolist(), scorer, {}, slices)
+    return _result(parts, y, names, oov_rows.tolist(), scorer, {}, slices, bootstrap, unit_pieces)
 
 
 def write_scores(out_dir, res, top=20, **info):
     """probs.npy, logits.npy, oov_fields.npy, score.json; with slices (group_by) also slices_<name>.npz (the five
-    arrays and base) per column and slices.json {name: slice_report(top)}."""
+    arrays and base) per column and slices.json {name: slice_report(top)}; with a bootstrap also bootstrap.json (the
+    report, replicates, seed, level, units), bootstrap.npz (the four arrays, seed, level, units), labels.npy (u8 [N]),
+    boot_units.npy (int64 [N], when the units are a field's ids), and the listed groups' intervals (slice_intervals)."""
     os.makedirs(out_dir, exist_ok=True)
     for k in ("probs", "logits", "oov_fields"):
         np.save(os.path.join(out_dir, f"{k}.npy"), res[k])
@@ -502,8 +639,21 @@ def write_scores(out_dir, res, top=20, **info):
             arrays = {k: s[k] for k in SLICE_ARRAYS}
             np.savez(os.path.join(out_dir, f"slices_{name}.npz"), base=np.int64(s["base"]), **arrays)
             reports[name] = slice_report(**arrays, top=top, names=s["names"])
+            if "bootstrap" in res:
+                slice_intervals(res, name, reports[name]["top"])
         with open(os.path.join(out_dir, "slices.json"), "w") as f:
             json.dump(_json_safe(reports), f, indent=1, allow_nan=False)
+    if "bootstrap" in res:
+        b = res["bootstrap"]
+        boot = b["boot"]
+        np.savez(os.path.join(out_dir, "bootstrap.npz"), seed=np.uint64(boot.seed), level=np.float64(boot.level),
+                 units=np.array(boot.by), **b["arrays"])
+        np.save(os.path.join(out_dir, "labels.npy"), b["labels"])
+        if b["units"] is not None:
+            np.save(os.path.join(out_dir, "boot_units.npy"), b["units"])
+        with open(os.path.join(out_dir, "bootstrap.json"), "w") as f:
+            json.dump(_json_safe(dict(b["report"], replicates=boot.replicates, seed=boot.seed, level=boot.level,
+                                      units=boot.by)), f, indent=1, allow_nan=False)
     doc = dict(res["info"], **info)
     with open(os.path.join(out_dir, "score.json"), "w") as f:
         json.dump(doc, f, indent=1)
@@ -530,6 +680,14 @@ def parser():
                    help=f"sliced evaluation: AUC, GAUC, log-loss and calibration per value of these fields ({OOV_COLUMN}: "
                         "per count of <oov> fields) -> slices.json, slices_<name>.npz; needs labels of both classes")
     p.add_argument("--top", type=_positive, default=20, help="groups listed per column in slices.json, by rows")
+    p.add_argument("--bootstrap", metavar="R", type=_positive, default=None,
+                   help="Poisson-bootstrap intervals of AUC and log-loss from R replicates (<= 65536) -> bootstrap.json, "
+                        "bootstrap.npz, labels.npy; needs labels of both classes")
+    p.add_argument("--bootstrap_seed", metavar="S", type=int, default=None, help="seed of the resamples (default 0)")
+    p.add_argument("--bootstrap_level", metavar="L", type=float, default=None, help="coverage of the intervals (default 0.95)")
+    p.add_argument("--bootstrap_by", metavar="NAME", default=None,
+                   help=f"resampling unit: a field (its rows share a weight: the cluster bootstrap; -> boot_units.npy) "
+                        f"or {ROW_UNITS}, every row alone (default)")
     add_flags(p, MODEL_FLAGS + EXTENSION_MODEL_FLAGS)
     return p
 
@@ -543,6 +701,29 @@ def parse_args(argv=None):
         p.error("--vocab / --unlabeled go with --raw")
     if args.chunk_mb > 1024:
         p.error("--chunk_mb: at most 1024")
+    if args.bootstrap is None:
+        for flag in ("bootstrap_seed", "bootstrap_level", "bootstrap_by"):
+            if getattr(args, flag) is not None:
+                p.error(f"--{flag} goes with --bootstrap R")
+    else:
+        if args.unlabeled:
+            p.error("--bootstrap needs the labels of both classes: no labels (it does not go with --unlabeled)")
+        if args.bootstrap > ops.BOOT_MAX_REPLICATES:
+            p.error(f"--bootstrap: at most {ops.BOOT_MAX_REPLICATES} replicates")
+        seed = 0 if args.bootstrap_seed is None else args.bootstrap_seed
+        level = 0.95 if args.bootstrap_level is None else args.bootstrap_level
+        by = ROW_UNITS if args.bootstrap_by is None else args.bootstrap_by
+        if not 0 <= seed < 2 ** 64:
+            p.error("--bootstrap_seed: an unsigned 64-bit integer")
+        if not 0.0 < level < 1.0:
+            p.error("--bootstrap_level: between 0 and 1")
+        if args.raw is not None and by != ROW_UNITS:
+            from . import rawtext
+            schema = rawtext.SCHEMAS[args.dataset]
+            known = [c for c in schema.columns if c != schema.label]
+            if by not in known:
+                p.error(f"--bootstrap_by: {by!r} is not a field of {args.dataset} ({', '.join(known)}) or {ROW_UNITS}")
+        args.bootstrap_seed, args.bootstrap_level, args.bootstrap_by = seed, level, by
     if args.group_by:
         if args.unlabeled:
             p.error("--group_by needs labels: it does not go with --unlabeled")
@@ -576,6 +757,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("mapx.score runs on an MI355X only (no CPU path)")
     device = torch.device("cuda", 0)
+    boot = None if args.bootstrap is None else Bootstrap(args.bootstrap, args.bootstrap_seed, args.bootstrap_level,
+                                                          args.bootstrap_by)
     t0 = time.time()
     if args.raw is not None:
         from . import rawtext, vocab
@@ -583,13 +766,14 @@ def main(argv=None):
         voc = vocab.Vocabulary.from_meta(args.vocab, schema, device=device)
         model = build_model(args, voc.input_size, len(voc.fields), device)
         scorer = Scorer(model, args.batch_size, device, oov_id=[f.oov for f in voc.fields])
-        res = score_raw_file(scorer, args.raw, schema, voc, chunk_bytes=args.chunk_mb << 20, group_by=args.group_by)
+        res = score_raw_file(scorer, args.raw, schema, voc, chunk_bytes=args.chunk_mb << 20, group_by=args.group_by,
+                             bootstrap=boot)
     else:
         meta, feat_ids, labels = read_dataset(args.data_dir, args.dataset_name, args.split)
         names = [n for n in meta["field_names"] if n != "<rsv>"]
         model = build_model(args, len(meta["feat_map"]), len(meta["field_map"]) - 1, device)
         scorer = Scorer(model, args.batch_size, device, oov_id=oov_ids_of(meta, names))
-        res = score_dataset(scorer, meta, feat_ids, labels, names=names, group_by=args.group_by)
+        res = score_dataset(scorer, meta, feat_ids, labels, names=names, group_by=args.group_by, bootstrap=boot)
     doc = write_scores(args.out, res, top=args.top, model=args.model, compute_dtype=args.compute_dtype,
                        seconds=round(time.time() - t0, 3))
     m = doc["metrics"]
